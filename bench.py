@@ -6,6 +6,10 @@ BASELINE.json configs[1] (25-room gcp_tree, 64x64x3, seq_len 80, batch 16 per GP
 L=7 tree levels (posterior path), decoder over all B*127 tree nodes, balanced binding + matched/pruned gathers
 and the auxiliary heads — everything `model(inputs)` runs (train.py:205-214 / cem_simulator.py:29-31).
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only (with the head kernel's roofline, read from events inside the timed steps).  `--full`
+adds what takes runs of its own: the secondary workloads under "also" (training step, planning, adaptive and sequential models,
+graph / eager replay legs) and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -204,6 +208,50 @@ def _timed(fn, steps, warmup, world, dev):
         dist.barrier()
     torch.cuda.synchronize()
     return D.max_over_ranks(time.perf_counter() - t0, device=dev) / steps
+
+
+DUMP_SAMPLE = 1 << 20           # elements kept of a larger output: a fixed, seeded sample of its flat positions
+DUMP_LIMIT = 64 << 20           # bytes written in all
+
+
+def dump_outputs(out, losses, path):
+    """--dump-outputs: what a caller of the timed path holds after its last step — `model(inputs)` (decoded node frames, the tree's
+    latents, the auxiliary heads' outputs, the pruned prediction) and `model.loss()` — as <path>/<name>.npy.  The inputs and the seed
+    of the in-step noise are fixed: the same arguments give the same numbers.  Floating outputs are float32 (float64 stays float64),
+    integer ones float64.  An output of more than DUMP_SAMPLE elements is written as the elements at DUMP_SAMPLE positions drawn from
+    a generator seeded with 0 (same positions for the same size), sorted."""
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def put(name, t):
+        if not isinstance(t, torch.Tensor):
+            return
+        t = t.detach()
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE))
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        arrays[name] = t.cpu().numpy()
+
+    put("images_df", out.images_df)
+    for k in ("z", "p_z_mu", "p_z_log_sigma", "q_z_mu", "q_z_log_sigma", "e_g_prime", "hidden_state", "match_timesteps"):
+        put("tree.df." + k, out.tree.df[k])
+    for k in ("seq_len_logits", "soft_matched_estimates"):
+        put(k, out.get(k))
+    if "existence_predictor" in out:
+        put("existence_predictor.existence", out.existence_predictor.existence)
+    for k in ("model_enc_seq", "regressed_state", "actions", "cost", "cost_target"):
+        put(k, getattr(out, k, None))
+    put("pruned_prediction", torch.cat(list(out.pruned_prediction), 0))
+    for k, v in losses.items():
+        put("loss." + k.lstrip("_"), v.value if isinstance(v, dict) else v)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def extras(args, model, hp, dinp, dnoise, inputs, rank, world, dev, dinp_noloss):
@@ -533,8 +581,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16, help="sequences per GPU (configs[1]: 16)")
     ap.add_argument("--eval-bn", action="store_true", help="running-stat BatchNorm (planner mode) instead of batch stats")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (training step, CEM "
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements (\"also\": replay legs, training "
+                    "step, CEM planning, adaptive and sequential models) and the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (training step, CEM "
                     "planning iteration, adaptive-binding forward) reported under \"also\"")
     ap.add_argument("--backend", default="nccl", help='torch.distributed backend of the ranks ("nccl" = RCCL; "gloo" for --launch-check on CPU)')
     ap.add_argument("--launch-check", action="store_true", help="rendezvous + barrier + max-over-ranks only, no GPU work (tests)")
@@ -581,7 +632,10 @@ def main():
     dnoise = noise.to(dev)
     dinp_noloss = {k: dinp[k] for k in ("traj_seq", "I_0", "I_g", "end_ind", "start_ind")}
 
-    # the latent noise is DRAWN inside every timed step (noise=None: Gaussian.sample() of the reference draws per forward), not fed
+    # the latent noise is DRAWN inside every timed step (noise=None: Gaussian.sample() of the reference draws per forward), not fed;
+    # its stream starts from torch's CUDA seed, which torch draws at random per process unless seeded: seeded per rank, so that runs
+    # with the same arguments compute the same outputs (--dump-outputs)
+    torch.manual_seed(D.shard_seed(0, rank))
     for _ in range(max(args.warmup, 1)):
         model(dinp, "train")
     torch.cuda.synchronize()
@@ -607,6 +661,8 @@ def main():
     elapsed = D.max_over_ranks(elapsed, device=dev)
     total_loss = float(model.get_total_loss(dinp, losses).value)
     replay = model.replay_info()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, losses, args.dump_outputs)      # before any later call overwrites the plan's output buffers
 
     def replay_leg(mode):
         """the headline step (forward + loss, no events around the head) with every plan forced onto one way of replaying, same process"""
@@ -620,12 +676,12 @@ def main():
         dt = _timed(step, args.steps, 2, world, dev)
         return {"ms_per_step": round(1e3 * dt, 3), "value": round(world * hp.batch_size * hp.max_seq_len / dt, 1), "unit": "frames/s"}
     replay_legs = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         replay_legs = {"forward_graph": replay_leg("graph"), "forward_eager": replay_leg("eager")}
         model.force_replay("auto")
 
     also = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         also = extras(args, model, hp, dinp, dnoise, inputs, rank, world, dev, dinp_noloss)
         also = dict(replay_legs, **also)
 
@@ -694,7 +750,7 @@ def main():
                 for key in ("train_step", "planning_iteration"):
                     if isinstance(also.get(key), dict) and "error" not in also[key]:
                         line["scaling_" + key] = dict(also[key], n_gpus=world, scaling="weak")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and (args.full or args.cpu_baseline_full) and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(full=args.cpu_baseline_full)
         print(json.dumps(line), flush=True)
     if world > 1:

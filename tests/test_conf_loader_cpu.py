@@ -1,5 +1,6 @@
 """Experiment configuration in the reference's format (gcp_builder.py:112-147): a conf.py with `configuration` / `model_config`
 that imports blox / gcp / experiments names, loaded without those packages."""
+import json
 import os
 import textwrap
 
@@ -132,10 +133,15 @@ def test_conf_json_and_default(tmp_path):
     assert hp.max_seq_len == 80 and trainer == {}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/experiments/prediction/25room/gcp_tree"), reason="reference tree not present")
 def test_the_reference_25room_conf_itself():
-    hp, trainer, ignored = CL.load_conf("/root/reference/experiments/prediction/25room/gcp_tree", max_seq_len=200)
+    """the dicts the reference's experiments/prediction/25room/gcp_tree/conf.py defines, as recorded from that file by
+    tests/golden/make_ref_conf_goldens.py (tests/golden/ref_25room_gcp_tree_conf.json)"""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "ref_25room_gcp_tree_conf.json")) as f:
+        g = json.load(f)
+    hp, trainer, ignored = CL.hparams_from_conf(g["configuration"], g["model_config"], max_seq_len=200)
     assert trainer["lr"] == 2e-4 and hp.batch_size == 16 and hp.hierarchy_levels == 8 and hp.attach_cost_mdl
+    assert trainer["model"] == "tree" and trainer["metric_pruning_scheme"] == "basic" and "dataset_name" in ignored
+    assert hp.n_nodes == 255 and hp.matching_type == "balanced" and hp.attach_inv_mdl and hp.n_actions == 2
 
 
 def test_a_conf_that_keeps_the_pixel_copy_stream_is_refused(tmp_path):
