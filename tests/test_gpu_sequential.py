@@ -103,6 +103,34 @@ def test_sequential_gradients_match_autograd(variant):
         assert ks and any(float(got[k].abs().max()) > 0 for k in ks), pre
 
 
+def test_sequential_gradients_match_autograd_free_nats_burn_in():
+    """test_sequential_gradients_match_autograd under the reference's 25room gcp_sequential KL settings: free_nats = 1 (the
+    per-dimension clamp in the KL backward) and kl_weight_burn_in (gcpx_kl_bwd_scheduled with the flat model's node weights
+    pad_mask[:, 1:], training_sequential.py:198) after 3 model steps of an 8-step ramp; the oracle runs with the weight the model
+    reports.  Same bound: 1e-3 of the gradient's max-abs + 5e-7."""
+    import dataclasses
+    from oracle import gcp_sequential_oracle as S
+    hp, sd, model, tr = _train_setup(False, free_nats=1.0, kl_weight_burn_in=8)
+    for _ in range(3):
+        model.step()
+    assert abs(model.kl_weight_now - 3 / 8 * hp.kl_weight) < 1e-12
+    inputs, noise, _ = make_inputs(hp, seed=7, variant="B")
+    noise = noise[:, :hp.max_seq_len - 1].contiguous()
+    dev_in = {k: v.cuda() for k, v in inputs.items()}
+    out = tr.backward(dev_in, noise.cuda())
+    torch.cuda.synchronize()
+    hp_o = dataclasses.replace(hp, kl_weight=model.kl_weight_now, kl_weight_burn_in=None)
+    gref, res, total, _ = S.gradients(sd, hp_o, inputs, noise)
+    assert abs(float(out.raw["losses"][5]) - float(total)) <= 1e-4 * abs(float(total))
+    got = tr.named_grads()
+    bad = []
+    for k, g in gref.items():
+        err, scale = float((got[k].cpu() - g).abs().max()), float(g.abs().max())
+        if err > 1e-3 * scale + 5e-7:
+            bad.append((k, err, scale))
+    assert not bad, bad[:10]
+
+
 def test_sequential_cell_backward_in_the_gemm_epilogue_gives_the_same_gradient():
     """fuse_lstm_bwd (off by default: it does not pay, NOTEBOOK round 4): every LSTM cell backward of the 79-step chains rides in the
     epilogue of the data-gradient GEMM that feeds it (gcpx_gemm_args.lstm_bwd) — the same device function on the same values: the

@@ -54,6 +54,69 @@ def test_gradients_match_autograd_c1(graph):
         assert ks and all(float(got[k].abs().max()) > 0 for k in ks), pre
 
 
+def _quantized_inputs(hp, seed):
+    """make_inputs with the targets on the loader's 256 levels (k / 255 * 2 - 1, data_loader.py:220) and saturated bands at -1 / +1
+    (every 25-room frame has them): the x = -1 / +1 branches of the likelihood and its gradient run.  I_0 / I_g follow the new frames."""
+    inputs, noise, _ = make_inputs(hp, seed=seed, variant="B")
+    tr = torch.round((inputs["traj_seq"] + 1) * 127.5) / 127.5 - 1
+    tr[..., :3, :] = -1.0
+    tr[..., -3:, :] = 1.0
+    tr[..., 5, :] = 1 - 2 / 255.0
+    tr = tr * inputs["pad_mask"][:, :, None, None, None]
+    B = tr.shape[0]
+    inputs.update(traj_seq=tr, I_0=tr[:, 0].clone(), I_g=tr[torch.arange(B), inputs["end_ind"]].clone())
+    return inputs, noise
+
+
+@pytest.mark.parametrize("mode", ["materialize_distr", "exact_f32"])
+def test_gradients_match_autograd_c1_stored_params_likelihood(mode):
+    """The balanced model's training step through the stored-parameters likelihood backward (gcpx_gather_rows + gcpx_dlm_nll_bwd,
+    forward_plan.py:704-717) instead of the head's fused gradient: with materialize_distr=True, and on the exact-f32 build
+    (model.split_f16 = False, fused_head_nll = False).  Quantized targets with saturated regions.  Every parameter gradient within the
+    1e-3 of this file's header."""
+    import video_gcp_amd as V
+    from video_gcp_amd.model import GCPTreeModel
+    from video_gcp_amd.training import GCPTrainStep
+    from oracle import gcp_model_oracle as O
+    hp = V.config("c1")
+    sd = V.init_params(hp, seed=1, randomize_affine=True)
+    model = GCPTreeModel(hp, params=sd, device="cuda", materialize_distr=(mode == "materialize_distr"))
+    if mode == "exact_f32":
+        model.split_f16 = False
+        model.fused_head_nll = False
+    model.use_graph = False
+    tr = GCPTrainStep(model, lr=1e-3)
+    inputs, noise = _quantized_inputs(hp, 7)
+    assert bool((inputs["traj_seq"] == -1).any()) and bool((inputs["traj_seq"] == 1).any())
+    dev_in = {k: v.cuda() for k, v in inputs.items()}
+    out = tr.backward(dev_in, noise.cuda())
+    torch.cuda.synchronize()
+    gref, res, total, _ = O.gradients(sd, hp, inputs, noise)
+    assert abs(float(out.raw["losses"][5]) - float(total)) <= 2e-5 * abs(float(total))
+    _compare_grads(gref, tr.named_grads())
+
+
+def test_gradients_match_autograd_c1_free_nats_burn_in():
+    """The reference gcp_sequential configuration's KL settings on the tree model: free_nats = 1 (the per-dimension clamp of
+    kl_bwd_kernel runs: dimensions below the floor get no gradient) and kl_weight_burn_in (the weight read from device memory,
+    gcpx_kl_bwd_scheduled) after 4 model steps of a 10-step ramp.  The oracle runs with the weight the model reports.  Every
+    parameter gradient within the 1e-3 of this file's header."""
+    import dataclasses
+    from oracle import gcp_model_oracle as O
+    hp, sd, model, tr = _setup("c1", False, free_nats=1.0, kl_weight_burn_in=10)
+    for _ in range(4):
+        model.step()
+    assert abs(model.kl_weight_now - 0.4 * hp.kl_weight) < 1e-12
+    inputs, noise, _ = make_inputs(hp, seed=7, variant="B")
+    dev_in = {k: v.cuda() for k, v in inputs.items()}
+    out = tr.backward(dev_in, noise.cuda())
+    torch.cuda.synchronize()
+    hp_o = dataclasses.replace(hp, kl_weight=model.kl_weight_now, kl_weight_burn_in=None)
+    gref, res, total, _ = O.gradients(sd, hp_o, inputs, noise)
+    assert abs(float(out.raw["losses"][5]) - float(total)) <= 2e-5 * abs(float(total))
+    _compare_grads(gref, tr.named_grads())
+
+
 def _grad_errors(gref, got):
     """per parameter: max |difference| relative to the gradient's max-abs (parameters whose gradient is rounding noise skipped)"""
     return {k: float((got[k].cpu() - g).abs().max()) / float(g.abs().max()) for k, g in gref.items() if float(g.abs().max()) > 1e-6}
