@@ -932,6 +932,20 @@ int gcpx_comm_allreduce(void* comm, float* buf, int64_t n, void* stream);
 int gcpx_comm_allgather(void* comm, const float* send, float* recv, int64_t n, void* stream);
 int gcpx_comm_destroy(void* comm);
 
+/* ---- host-fed data path (video-gcp_amd/dataset.py): assembly of one uploaded batch into the model's f32 inputs, in place.
+ *   frames  uint8 [B][T][H][W][3]: per sequence the window raw[offset : offset + T] of its recorded frames (first n_frames valid);
+ *   info    int32 [B][8]: n_frames, n_states, n_actions, chop, zero_from, end_ind, 0, 0 (the host's draws, data_loader.py:131-211);
+ *   lut     f32 [256]: the reference's uint8 -> [-1, 1] conversion (data_loader.py:222) as a table; pad_in f32 [B][T];
+ *   states_in f32 [B][T][state_dim], actions_in f32 [B][T-1][n_actions]: windows like the frames (null when the size is 0);
+ *   states_mean / states_den f32 [state_dim] (both null: no standardisation): states = (s - mean) / den, den = 1e-6 + std.
+ *   Output frame t reads window frame s = min(t + chop, T - 1) when t < zero_from and s < n_frames, else uint8 0 (-> lut[0] = -1).
+ *   Writes traj_seq [B][T][3][H][W], I_0 / I_g [B][3][H][W] (frames 0 / end_ind), pad_mask [B][T], end_ind / start_ind int64 [B],
+ *   states [B][T][state_dim], actions [B][T-1][n_actions].  H * W % 4 == 0 needs 16-byte aligned frames and images. */
+int gcpx_assemble_batch(const uint8_t* frames, const int32_t* info, const float* lut, const float* pad_in, const float* states_in,
+                        const float* actions_in, const float* states_mean, const float* states_den, int32_t B, int32_t T, int32_t H,
+                        int32_t W, int32_t state_dim, int32_t n_actions, float* traj_seq, float* I_0, float* I_g, float* pad_mask,
+                        int64_t* end_ind, int64_t* start_ind, float* states, float* actions, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

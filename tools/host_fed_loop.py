@@ -1,0 +1,76 @@
+"""Host-fed against device-fed training steps at c2 (video-gcp_amd/dataset.py).
+
+Writes a seeded uint8 c2 dataset (B=16 sequences of up to 80 frames of 64x64x3 per batch) to a temporary directory, then times
+ModelTrainer.train_epoch over `--batches` batches in two ways, alternating (`--rounds` times each) so that noise of the shared host
+affects both alike:
+  host   — HostFedLoader: uint8 frames from a 2-slot pinned ring, H2D on its own stream, gcpx_assemble_batch into the input buffers;
+  device — the same batches assembled in numpy beforehand and resident on the device, fed through the existing staging copy.
+Prints one JSON line: steps/s of both, per round, and their ratio.  For the kernel trace run it under
+`rocprofv3 --kernel-trace --stats -- python tools/host_fed_loop.py --rounds 1`.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--workers", type=int, default=4)
+    ap.add_argument("--slots", type=int, default=2)
+    a = ap.parse_args()
+    import torch
+    import video_gcp_amd  # noqa: F401
+    from video_gcp_amd import dataset as DS
+    from video_gcp_amd.train import ModelTrainer, get_cmd_args
+    import dataset_fixture as FX
+
+    with tempfile.TemporaryDirectory() as tmp:
+        data, exp = os.path.join(tmp, "data"), os.path.join(tmp, "exp")
+        B, T = 16, 80
+        # 160 recorded sequences (about 190 MB) read over and over: every batch is still read, packed and uploaded
+        t0 = time.time()
+        FX.write_random_dataset(data, T=T, img=64, n_files=5, traj_per_file=32, phases=("train",), min_len=T)
+        FX.write_random_dataset(data, T=T, img=64, n_files=1, traj_per_file=B, phases=("val",), min_len=T)
+        t_write = time.time() - t0
+        os.makedirs(exp)
+        with open(os.path.join(exp, "conf.json"), "w") as f:
+            json.dump({"config": "c2", "num_epochs": 1}, f)
+        mt = ModelTrainer(get_cmd_args(["--path", exp, "--data_dir", data, "--log_outputs_interval", "1000000"]))
+        host = DS.HostFedLoader(mt.train_loader.ds, mt.model, B, n_repeat=-(-a.batches // 10), seed=0, n_slots=a.slots,
+                                n_workers=a.workers)
+        sched = host.schedule()[:a.batches]
+        host.schedule = lambda: sched
+        dev = [{k: torch.from_numpy(v).cuda() for k, v in DS.numpy_batch(host.ds, b, 0).items()} for b in sched]
+
+        def timed(loader):
+            mt.train_loader = loader
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            mt.train_epoch(0)
+            torch.cuda.synchronize()
+            return len(sched) / (time.perf_counter() - t)
+
+        timed(host)                                     # warm-up: plans, graphs, the ring's allocation
+        timed(dev)
+        rh, rd = [], []
+        for _ in range(a.rounds):
+            rh.append(timed(host))
+            rd.append(timed(dev))
+        mh, md = sorted(rh)[len(rh) // 2], sorted(rd)[len(rd) // 2]
+        print(json.dumps({"workload": "host_fed_loop", "config": "c2", "batches": len(sched), "slots": a.slots, "workers": a.workers,
+                          "host_fed_steps_per_s": round(mh, 3), "device_fed_steps_per_s": round(md, 3),
+                          "host_over_device": round(mh / md, 4), "rounds_host": [round(x, 3) for x in rh],
+                          "rounds_device": [round(x, 3) for x in rd], "dataset_write_s": round(t_write, 1)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -98,13 +98,29 @@ class _Finder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
 def exec_conf_py(path):
     """Run a reference-style conf.py; returns (configuration, model_config) as plain dicts."""
+    ns = _exec_with_placeholders(path, "conf")
+    if "configuration" not in ns or "model_config" not in ns:
+        raise ValueError(f"{path}: a configuration file defines `configuration` and `model_config` (gcp_builder.py:136-143)")
+    return dict(ns["configuration"]), dict(ns["model_config"])
+
+
+def exec_dataset_spec(path):
+    """Run a reference-style `<data_dir>/dataset_spec.py` (data_loader.py:100-102, gcp_builder.py:149-152) with the same
+    placeholder imports as conf.py; returns its `dataset_spec` as a plain dict (a dataset class arrives as a named placeholder)."""
+    ns = _exec_with_placeholders(path, "dataset_spec")
+    if "dataset_spec" not in ns:
+        raise ValueError(f"{path}: a dataset spec file defines `dataset_spec`")
+    return dict(ns["dataset_spec"])
+
+
+def _exec_with_placeholders(path, name):
     finder = _Finder()
     saved = {k: v for k, v in sys.modules.items() if k.split(".")[0] in _Finder.ROOTS}
     for k in saved:
         del sys.modules[k]
     sys.meta_path.insert(0, finder)
     try:
-        ns = {"__file__": os.path.abspath(path), "__name__": "conf"}
+        ns = {"__file__": os.path.abspath(path), "__name__": name}
         with open(path) as f:
             exec(compile(f.read(), path, "exec"), ns)
     finally:
@@ -112,9 +128,7 @@ def exec_conf_py(path):
         for k in [k for k in sys.modules if k.split(".")[0] in _Finder.ROOTS]:
             del sys.modules[k]
         sys.modules.update(saved)
-    if "configuration" not in ns or "model_config" not in ns:
-        raise ValueError(f"{path}: a configuration file defines `configuration` and `model_config` (gcp_builder.py:136-143)")
-    return dict(ns["configuration"]), dict(ns["model_config"])
+    return ns
 
 
 # trainer keys (gcp_builder.py:_default_hparams) that the device trainer reads

@@ -1,0 +1,407 @@
+"""Recorded video datasets and the host-fed loader.
+
+Reader: the reference's VarLenVideoDataset family (gcp/datasets/data_loader.py:23-290) over the same group layout,
+stored as `.npz` instead of HDF5: one file holds `traj_per_file` and, per trajectory i, `traj{i}/images` (uint8 [T_raw, H, W, 3], or
+[T_raw, n_cam, H, W, 3] of which camera 0 is used), `traj{i}/states`, `traj{i}/actions` and `traj{i}/pad_mask`.  The directory
+rules are the reference's: FolderSplitVarLenVideoDataset reads `<data_dir>/hdf5/<phase>/*`, GlobalSplitVarLenVideoDataset walks the
+tree (sorted here: the reference's order follows the file system's listing) and splits by `dataset_spec['split']`; both shuffle the
+file list with `random.Random(2)`.  `<data_dir>/dataset_spec.py` is executed with conf_loader's placeholder imports.
+
+Per item the host makes the reference's draws, in the reference's order and from a numpy RandomState (same generator as the
+reference's global np.random): end_ind from pad_mask, randomize_start, the random offset of the train phase, _maybe_pad, actions[:-1],
+randomize_length (data_loader.py:131-211).  It does not build f32 images: it packs the raw uint8 window raw[offset : offset + T] and a
+few integers per sequence (n_frames, chop, zero_from, end_ind); csrc/batch_assemble.hip turns them into the model's f32 inputs on
+the device, in place in `model.input_buffer(...)` (the zero-copy hand-over of replay.py).  `assemble_numpy` is the same assembly in
+numpy, bit for bit (tests, and the device-fed comparison of tools/host_fed_loop.py).
+
+Not here: reading `.h5` (h5py), resizing (blox.vis.resize_video: frames must already be img_sz), the nav datasets' MiniWorld
+re-rendering (MazeTopRendered...).
+"""
+import glob
+import os
+import random
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import runtime as rt
+
+# data_loader.py:222 `images.astype(np.float32) / 255 * 2 - 1` as a table: the kernel's values are these, whatever its build flags
+LUT = np.arange(256, dtype=np.uint8).astype(np.float32) / 255 * 2 - 1
+
+_CLASSES = ("FolderSplitVarLenVideoDataset", "GlobalSplitVarLenVideoDataset")
+N_INFO = 8          # int32 per sequence read by gcpx_assemble_batch
+
+
+def load_spec(data_dir):
+    """`<data_dir>/dataset_spec.py` -> dict (data_loader.py:100-102)."""
+    from .conf_loader import exec_dataset_spec
+    path = os.path.join(data_dir, "dataset_spec.py")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path}: a dataset directory holds a dataset_spec.py (data_loader.py:100-102)")
+    return exec_dataset_spec(path)
+
+
+def spec_overrides(spec, fields):
+    """the spec's non-list entries that are model hyper-parameters (gcp_builder.py:68 copies every non-list entry into the model's
+    conf; the ones this build has no field for have nothing to override)"""
+    return {k: v for k, v in spec.items() if not isinstance(v, (list, tuple)) and k in fields}
+
+
+def dataset_class_name(spec):
+    """the spec's `dataset_class` (gcp_builder.py:105-113; FolderSplit when absent).  Any other class raises: the nav datasets'
+    MazeTopRendered... re-renders frames with MiniWorld, and training on un-rendered frames without saying so is worse than stopping."""
+    c = spec.get("dataset_class")
+    if c is None:
+        return _CLASSES[0]
+    name = c if isinstance(c, str) else getattr(c, "__name__", repr(c))
+    name = name.rsplit(".", 1)[-1]
+    if name not in _CLASSES:
+        raise ValueError(f"dataset_spec['dataset_class'] = {name}: only {' and '.join(_CLASSES)} are built (the nav datasets' "
+                         "top-down re-rendering needs MiniWorld, which is not part of this build)")
+    return name
+
+
+class _FileCache(threading.local):
+    def __init__(self):
+        self.files = {}
+
+    def get(self, path):
+        f = self.files.get(path)
+        if f is None:
+            f = self.files[path] = np.load(path)
+        return f
+
+
+class VideoDataset:
+    """FolderSplit / GlobalSplit VarLenVideoDataset (data_loader.py:104-290) over `.npz` files."""
+
+    def __init__(self, data_dir, spec, phase, img_sz, randomize_length=False, randomize_start=False, dataset_size=-1):
+        self.data_dir, self.spec, self.phase, self.img_sz = data_dir, spec, phase, int(img_sz)
+        self.T = int(spec["max_seq_len"])
+        self.randomize_length, self.randomize_start = bool(randomize_length), bool(randomize_start)
+        self.dataset_size = dataset_size
+        self.kind = dataset_class_name(spec)
+        self.filenames = self._get_filenames()
+        self._cache = _FileCache()
+        self.traj_per_file = int(self._cache.get(self.filenames[0])["traj_per_file"])
+        self.states_mean = self.states_den = None
+        if "states_mean" in spec:                                     # data_loader.py:127-129, standardize :97-98
+            self.states_mean = np.asarray(spec["states_mean"]).astype(np.float32)
+            self.states_den = np.asarray(1e-6 + np.asarray(spec["states_std"])).astype(np.float32)
+
+    def _get_filenames(self):
+        if self.kind == _CLASSES[0]:                                  # data_loader.py:264-272
+            names = sorted(glob.glob(os.path.join(self.data_dir, "hdf5", self.phase + "/*")))
+        else:                                                         # :275-290 (.npz instead of .h5)
+            names = [os.path.join(r, f) for r, fs in _sorted_walk(self.data_dir) for f in fs
+                     if f.endswith(".npz") and f != "dataset_info.npz"]
+        if not names:
+            raise RuntimeError(f"No filenames found in {self.data_dir}")
+        random.Random(2).shuffle(names)                               # _shuffle_with_seed, :251-255
+        if self.kind == _CLASSES[1]:
+            names = self._split_with_percentage(self.spec["split"], names)
+        return names
+
+    def _split_with_percentage(self, frac, names):                   # :226-236
+        assert sum(frac.values()) <= 1.0 and self.phase in frac
+        if self.phase == "train":
+            s, e = 0, frac["train"]
+        elif self.phase == "val":
+            s, e = frac["train"], frac["train"] + frac["val"]
+        else:
+            s, e = frac["train"] + frac["val"], frac["train"] + frac["val"] + frac["test"]
+        return names[int(len(names) * s):int(len(names) * e)]
+
+    def __len__(self):
+        return self.dataset_size if self.dataset_size != -1 else len(self.filenames) * self.traj_per_file
+
+    def read(self, index):
+        """the raw arrays of item `index` (images uint8 [T_raw, H, W, 3] of camera 0, states / actions / pad_mask f32)"""
+        path = self.filenames[index // self.traj_per_file]
+        F = self._cache.get(path)
+        key = f"traj{index % self.traj_per_file}"
+        raw = {}
+        for name in ("images", "states", "actions", "pad_mask"):
+            k = f"{key}/{name}"
+            if k in F.files:
+                raw[name] = F[k] if name == "images" else F[k].astype(np.float32)
+        im = raw["images"]
+        if im.ndim == 5:
+            im = im[:, 0]                                             # number of cameras, data_loader.py:214-216
+        if im.dtype != np.uint8:
+            raise ValueError(f"{path}:{key}/images: frames are stored as uint8 (data_loader.py:217)")
+        if im.shape[1:] != (self.img_sz, self.img_sz, 3):
+            raise ValueError(f"{path}:{key}/images: frames are {im.shape[1]}x{im.shape[2]}, the model reads {self.img_sz}x{self.img_sz}. "
+                             "The reference resizes with blox.vis.resize_video, which is not part of this build: store the frames "
+                             "at the model's resolution")
+        raw["images"] = im
+        return raw
+
+    def draw(self, raw, rs):
+        """the reference's per-item draws (data_loader.py:144-156,175-211) from RandomState rs, in its order.  Returns the plan:
+        offset (window start in the raw arrays), chop, zero_from (frames >= it are zero), end_ind and the pad mask [T]."""
+        T = self.T
+        pm = raw["pad_mask"]
+        end_ind = int(np.argmax(pm * np.arange(pm.shape[0], dtype=np.float32), 0))
+        start_ind = rs.randint(0, end_ind - 1) if self.randomize_start else 0
+        extra = (end_ind - start_ind + 1) - T                         # sample_max_len_video
+        offset = max(0, int(rs.rand() * (extra + 1))) + start_ind if self.phase == "train" else 0
+        end_ind = min(end_ind - offset, T - 1)
+        chop, zero_from = 0, T
+        pad_mask = _maybe_pad(pm, offset, T)
+        if self.randomize_length:                                     # _randomize_length (start_ind is 0 here by design)
+            length = 3 + int(rs.rand() * (end_ind - 2))
+            chop = int(rs.rand() * (end_ind + 1 - length))
+            end_ind = length - 1
+            pad_mask = (np.arange(T) <= end_ind).astype(np.float32)
+            zero_from = end_ind + 1
+            if chop < 0:
+                raise ValueError(f"sequence too short for randomize_length (end_ind {end_ind})")
+        return dict(offset=offset, chop=chop, zero_from=zero_from, end_ind=end_ind, pad_mask=pad_mask)
+
+    def item(self, index, rs):
+        raw = self.read(index)
+        return raw, self.draw(raw, rs)
+
+
+def _sorted_walk(top):
+    for r, ds, fs in os.walk(top):
+        ds.sort()
+        yield r, sorted(fs)
+
+
+def _maybe_pad(val, offset, T):                                       # data_loader.py:239-248
+    val = val[offset:]
+    if val.shape[0] >= T:
+        return val[:T]
+    return np.concatenate((val, np.zeros([T - val.shape[0]] + list(val.shape[1:]), dtype=val.dtype)))
+
+
+def _time_map(a, plan, L):
+    """randomize_length's chop + repeat of the last step and zeroing after end_ind (data_loader.py:203-206) on a padded array of L"""
+    idx = np.minimum(np.arange(L) + plan["chop"], L - 1)
+    out = a[idx]
+    out[plan["zero_from"]:] = 0
+    return out
+
+
+def assemble_numpy(items, T, states_mean=None, states_den=None):
+    """[(raw, plan)] -> the model's inputs as numpy arrays, by the reference's own steps (pad, chop, convert) — what
+    gcpx_assemble_batch computes, bit for bit."""
+    out = {k: [] for k in ("traj_seq", "pad_mask", "end_ind", "start_ind", "traj_seq_states", "actions")}
+    for raw, p in items:
+        im = _time_map(_maybe_pad(raw["images"], p["offset"], T), p, T)
+        im = np.transpose(im, (0, 3, 1, 2)).astype(np.float32) / 255 * 2 - 1
+        out["traj_seq"].append(im)
+        out["pad_mask"].append(p["pad_mask"].astype(np.float32))
+        out["end_ind"].append(p["end_ind"])
+        out["start_ind"].append(0)
+        if "states" in raw:
+            s = _time_map(_maybe_pad(raw["states"], p["offset"], T), p, T)
+            if states_mean is not None:
+                s = (s - states_mean) / states_den
+            out["traj_seq_states"].append(s.astype(np.float32))
+        if "actions" in raw:
+            out["actions"].append(_time_map(_maybe_pad(raw["actions"], p["offset"], T)[:-1], p, T - 1))
+    res = {k: np.stack(v) if k not in ("end_ind", "start_ind") else np.array(v, dtype=np.int64) for k, v in out.items() if len(v)}
+    B = len(items)
+    res["I_0"] = res["traj_seq"][:, 0].copy()
+    res["I_g"] = res["traj_seq"][np.arange(B), res["end_ind"]].copy()
+    return res
+
+
+def item_rng(seed, cycle, pos):
+    """the draws of the item at position `pos` of cycle `cycle` of a loader seeded `seed`: keyed, so a resumed run draws the same"""
+    return np.random.RandomState(np.random.SeedSequence([int(seed), int(cycle), int(pos)]).generate_state(4))
+
+
+def batch_schedule(n_items, batch_size, seed, cycle, shuffle, rank=0, world=1):
+    """[(dataset index, position)] per batch of this rank for one pass over the data (drop_last): one order shared by all ranks, rank r
+    of W takes items [r·B, (r+1)·B) of each global batch of W·B — together they consume what one process with batch W·B would."""
+    order = np.arange(n_items)
+    if shuffle:
+        order = np.random.RandomState(np.random.SeedSequence([int(seed), int(cycle)]).generate_state(4)).permutation(n_items)
+    gb = batch_size * world
+    return [[(int(order[g * gb + rank * batch_size + j]), g * gb + rank * batch_size + j) for j in range(batch_size)]
+            for g in range(n_items // gb)]
+
+
+def epoch_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank=0, world=1):
+    """one epoch = n_repeat passes (RepeatedDataLoader, data_loader.py:83-88): [[(dataset index, position, cycle)] per batch]"""
+    out = []
+    for r in range(n_repeat):
+        cycle = epoch * n_repeat + r
+        out += [[(i, p, cycle) for i, p in b] for b in batch_schedule(n_items, batch_size, seed, cycle, shuffle, rank, world)]
+    return out
+
+
+def numpy_batch(ds, batch, seed):
+    """one scheduled batch assembled on the host by assemble_numpy"""
+    return assemble_numpy([ds.item(i, item_rng(seed, c, p)) for i, p, c in batch], ds.T, ds.states_mean, ds.states_den)
+
+
+def pack_item(item, j, frames, aux, info, B, T, S, A):
+    """sequence j of a staging slot (numpy views): the uint8 window raw[offset : offset + T], pad mask / state / action windows in
+    aux = [pad_mask B*T | states B*T*S | actions B*(T-1)*A], and the per-sequence integers of gcpx_assemble_batch"""
+    raw, p = item
+    o = p["offset"]
+    fr = raw["images"][o:o + T]
+    frames[j, :fr.shape[0]] = fr
+    aux[j * T:(j + 1) * T] = p["pad_mask"]
+    n_s = n_a = 0
+    if S:
+        s = raw["states"][o:o + T]
+        aux[B * T:B * T * (1 + S)].reshape(B, T, S)[j, :s.shape[0]] = s
+        n_s = s.shape[0]
+    if A:
+        a = raw["actions"][o:o + T - 1]
+        aux[B * T * (1 + S):].reshape(B, T - 1, A)[j, :a.shape[0]] = a
+        n_a = a.shape[0]
+    info[j] = (fr.shape[0], n_s, n_a, p["chop"], p["zero_from"], p["end_ind"], 0, 0)
+
+
+def assemble_into(lib, frames, aux, info, lut, mean, den, out, S, A, stream):
+    """gcpx_assemble_batch from device staging tensors into the device tensors of `out` (the model's input names)"""
+    B, T, H, W, _ = frames.shape
+    a = aux.data_ptr()
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    rt.check(lib.gcpx_assemble_batch(frames.data_ptr(), info.data_ptr(), lut.data_ptr(), a, a + 4 * B * T if S else None,
+                                     a + 4 * B * T * (1 + S) if A else None, mean.data_ptr() if mean is not None else None,
+                                     den.data_ptr() if den is not None else None, B, T, H, W, S, A, ptr("traj_seq"), ptr("I_0"),
+                                     ptr("I_g"), ptr("pad_mask"), ptr("end_ind"), ptr("start_ind"), ptr("traj_seq_states"),
+                                     ptr("actions"), stream), "assemble_batch")
+
+
+class _Streams:
+    """the H2D copy stream and the ring's events.  copy_done[s]: slot s's last upload finished (its pinned slot may be refilled);
+    assembled[s]: the assembly kernel that read device slot s has run (the slot may be overwritten)."""
+
+    def __init__(self, device, n):
+        self.copy = torch.cuda.Stream(device=device)
+        self.copy_done = [torch.cuda.Event() for _ in range(n)]
+        self.assembled = [torch.cuda.Event() for _ in range(n)]
+
+
+class HostFedLoader:
+    """Yields the model's input dicts, assembled on the device from uint8 frames uploaded from a ring of pinned host slots.  The
+    tensors it yields ARE `model.input_buffer(...)` (no staging copy in the forward); each batch is assembled on the caller's current
+    stream when the next one is asked for, i.e. behind the previous training step.  RepeatedDataLoader semantics (n_repeat passes
+    per epoch, data_loader.py:83-88), drop_last, shuffle in the train phase only."""
+
+    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None):
+        if rank is None or world is None:
+            d = torch.distributed
+            on = d.is_available() and d.is_initialized()
+            rank = d.get_rank() if on else 0
+            world = d.get_world_size() if on else 1
+        assert n_slots >= 2
+        self.ds, self.model, self.B = dataset, model, int(batch_size)
+        self.n_repeat, self.seed, self.rank, self.world = int(n_repeat), int(seed), int(rank), int(world)
+        self.shuffle = (dataset.phase == "train") if shuffle is None else bool(shuffle)
+        self.n_slots, self.epoch = n_slots, 0
+        self.pool = ThreadPoolExecutor(max_workers=n_workers)
+        hp = model._hp
+        if hp.max_seq_len != dataset.T or hp.img_sz != dataset.img_sz:
+            raise ValueError(f"dataset (T={dataset.T}, {dataset.img_sz}px) and model (T={hp.max_seq_len}, {hp.img_sz}px) differ")
+        if hp.batch_size != self.B:
+            raise ValueError(f"loader batch {self.B} != model batch {hp.batch_size}")
+        raw0 = dataset.read(0)
+        self.S = raw0["states"].shape[-1] if "states" in raw0 else 0
+        self.A = raw0["actions"].shape[-1] if "actions" in raw0 else 0
+        self._bufs = None
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return self.n_repeat * (len(self.ds) // (self.B * self.world))
+
+    def schedule(self):
+        """this rank's batches of the current epoch: [(dataset index, position, cycle)]"""
+        return epoch_schedule(len(self.ds), self.B, self.n_repeat, self.seed, self.epoch, self.shuffle, self.rank, self.world)
+
+    def numpy_batches(self):
+        """the same batches as numpy arrays assembled on the host (the device-fed path of the tests and of tools/host_fed_loop.py)"""
+        for b in self.schedule():
+            yield numpy_batch(self.ds, b, self.seed)
+
+    # ---- the ring ----
+    def _alloc(self):
+        dev, B, T, n = self.model.device, self.B, self.ds.T, self.n_slots
+        H = W = self.ds.img_sz
+        S, A = self.S, self.A
+        naux = B * T + B * T * S + B * (T - 1) * A
+        pin = dict(frames=[torch.empty(B, T, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(n)],
+                   aux=[torch.empty(naux, dtype=torch.float32, pin_memory=True) for _ in range(n)],
+                   info=[torch.zeros(B, N_INFO, dtype=torch.int32, pin_memory=True) for _ in range(n)])
+        devs = dict(frames=[torch.empty(B, T, H, W, 3, dtype=torch.uint8, device=dev) for _ in range(n)],
+                    aux=[torch.empty(naux, dtype=torch.float32, device=dev) for _ in range(n)],
+                    info=[torch.empty(B, N_INFO, dtype=torch.int32, device=dev) for _ in range(n)])
+        lut = torch.from_numpy(LUT).to(dev)
+        mean = den = None
+        if self.ds.states_mean is not None and S:
+            mean = torch.from_numpy(self.ds.states_mean).to(dev)
+            den = torch.from_numpy(self.ds.states_den).to(dev)
+        self._bufs = (pin, devs, lut, mean, den, _Streams(dev, n))
+
+    def _fill_item(self, slot, j, index, pos, cycle):
+        pin, _, _, _, _, st = self._bufs
+        st.copy_done[slot].synchronize()              # rule 1: the slot's previous upload has completed (a worker thread waits)
+        item = self.ds.item(index, item_rng(self.seed, cycle, pos))
+        pack_item(item, j, pin["frames"][slot].numpy(), pin["aux"][slot].numpy(), pin["info"][slot].numpy(), self.B, self.ds.T,
+                  self.S, self.A)
+
+    def _submit(self, slot, batch):
+        return [self.pool.submit(self._fill_item, slot, j, i, p, c) for j, (i, p, c) in enumerate(batch)]
+
+    def _upload(self, slot):
+        pin, devs, _, _, _, st = self._bufs
+        with torch.cuda.stream(st.copy):
+            st.copy.wait_event(st.assembled[slot])    # rule 2: the assembly that read this device slot has run
+            for k in ("frames", "aux", "info"):
+                devs[k][slot].copy_(pin[k][slot], non_blocking=True)
+            st.copy_done[slot].record(st.copy)
+
+    def _assemble(self, slot):
+        m = self.model
+        pin, devs, lut, mean, den, st = self._bufs
+        B, T, S, A, H = self.B, self.ds.T, self.S, self.A, self.ds.img_sz
+        caller = torch.cuda.current_stream(m.device)
+        caller.wait_event(st.copy_done[slot])
+        ib = m.input_buffer
+        out = dict(traj_seq=ib("traj_seq", (B, T, 3, H, H)), I_0=ib("I_0", (B, 3, H, H)), I_g=ib("I_g", (B, 3, H, H)),
+                   pad_mask=ib("pad_mask", (B, T)), end_ind=ib("end_ind", (B,)), start_ind=ib("start_ind", (B,), torch.int64))
+        if S:
+            out["traj_seq_states"] = ib("traj_seq_states", (B, T, S))
+        if A:
+            out["actions"] = ib("actions", (B, T - 1, A))
+        assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out, S, A, caller.cuda_stream)
+        st.assembled[slot].record(caller)
+        return out
+
+    def __iter__(self):
+        if self._bufs is None:
+            self._alloc()
+        batches = self.schedule()
+        n = self.n_slots
+        futs = {k: self._submit(k % n, batches[k]) for k in range(min(n, len(batches)))}
+        uploaded = set()
+        for k in range(len(batches)):
+            s = k % n
+            if k not in uploaded:
+                for f in futs.pop(k):
+                    f.result()
+                self._upload(s)
+            out = self._assemble(s)
+            if k + n < len(batches):
+                futs[k + n] = self._submit(s, batches[k + n])
+            # the next batch's upload goes out now if its slot is filled: it then runs under this step
+            if k + 1 < len(batches) and all(f.done() for f in futs[k + 1]):
+                for f in futs.pop(k + 1):
+                    f.result()
+                self._upload((k + 1) % n)
+                uploaded.add(k + 1)
+            yield out

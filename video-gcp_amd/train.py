@@ -6,10 +6,13 @@ What is replaced: `output = model(inputs); losses = model.loss(...); total.backw
 runs as `GCPTrainStep.step` (HIP forward + explicit backward + RAdam, training.py); data-parallel training is one process
 per GPU (launch with `python -m torch.distributed.run --nproc-per-node N -m video_gcp_amd.train ...`), every rank on its own
 shard, gradients averaged with ONE RCCL all-reduce over the flat gradient vector (gcp_builder.py:71-78 used nn.DataParallel).
-What is NOT here (out of the hot path): HDF5 datasets, TensorBoard logging, the control evaluation.  The
-experiment directory holds `conf.json` ({"config": "c2", "overrides": {...}, "num_epochs": n, "lr": x, "batches_per_epoch": k});
-`--feed_random_data 1` (the reference's own debug flag, gcp_builder.py:239) feeds the seeded synthetic batches of SURVEY §8d,
-which is the only data source this build ships; `dataset` may also be any iterable of input dicts passed to ModelTrainer.
+What is NOT here: reading HDF5 files directly, TensorBoard logging, the control evaluation.  The experiment directory
+holds `conf.json` ({"config": "c2", "overrides": {...}, "num_epochs": n, "lr": x, "batches_per_epoch": k}) or a reference-style conf.py.
+Data: `--data_dir DIR` (or `configuration['data_dir']`, or `$GCP_DATA_DIR/<dataset_name>` as gcp_builder.py:118,152 resolve it)
+trains and validates on a recorded dataset in the reference's layout stored as `.npz` (dataset.py: uint8 frames uploaded from pinned
+host memory and assembled on the device); its dataset_spec.py overrides the model hyper-parameters (gcp_builder.py:68).  Without a
+data directory, `--feed_random_data 1` (the reference's own debug flag, gcp_builder.py:239, on by default) feeds the seeded
+synthetic batches of SURVEY §8d; `dataset` may also be any iterable of input dicts passed to ModelTrainer.
 """
 import argparse
 import json
@@ -35,7 +38,45 @@ def get_cmd_args(argv=None):
     p.add_argument("--verbose_timing", default=False, type=int)
     p.add_argument("--num_epochs", default=None, type=int)
     p.add_argument("--batches_per_epoch", default=None, type=int)
+    p.add_argument("--data_dir", default=None, type=str, help="dataset directory (dataset_spec.py + hdf5/<phase>/*.npz, dataset.py)")
     return p.parse_args(argv)
+
+
+def _raw_conf(path):
+    """(configuration, model_config) of the experiment directory as written (conf.py or conf.json), {} / {} without one"""
+    import glob
+    from .conf_loader import exec_conf_py
+    if path and os.path.isdir(path):
+        py = sorted(glob.glob(os.path.join(os.path.abspath(path), "*.py")))
+        if len(py) == 1:
+            return exec_conf_py(py[0])
+        js = os.path.join(path, "conf.json")
+        if os.path.exists(js):
+            return json.load(open(js)), {}
+    return {}, {}
+
+
+def load_conf_with_data(path, config, data_dir=None, use_data=True):
+    """load_conf plus the dataset: (hp, trainer settings, ignored keys, data_dir or None, dataset spec, reader options).  The data
+    directory is `data_dir`, else configuration['data_dir'], else $GCP_DATA_DIR/<configuration['dataset_name']> (gcp_builder.py:118,152,
+    utils.py:74-76); its spec's non-list entries override the model hyper-parameters (gcp_builder.py:68)."""
+    from .conf_loader import load_conf
+    from .hparams import GCPHParams
+    configuration, model_config = _raw_conf(path)
+    if use_data and data_dir is None:
+        data_dir = configuration.get("data_dir")
+        name = configuration.get("dataset_name")
+        if data_dir is None and isinstance(name, str) and os.environ.get("GCP_DATA_DIR"):
+            data_dir = os.path.join(os.environ["GCP_DATA_DIR"], name)
+    if not use_data or not data_dir:
+        hp, conf, ignored = load_conf(path, default="c2", name=config)
+        return hp, conf, ignored, None, None, {}
+    from .dataset import load_spec, spec_overrides
+    spec = load_spec(data_dir)
+    hp, conf, ignored = load_conf(path, default="c2", name=config, **spec_overrides(spec, set(GCPHParams.__dataclass_fields__)))
+    # randomize_length / randomize_start: model hyper-parameters of the reference (the dataset reads them from the model's hparams)
+    opts = {k: bool(spec.get(k, model_config.get(k, configuration.get(k, False)))) for k in ("randomize_length", "randomize_start")}
+    return hp, conf, ignored, data_dir, spec, opts
 
 
 class SyntheticLoader:
@@ -66,11 +107,11 @@ class ModelTrainer:
         from .params import init_params
         from .training import GCPTrainStep
         self.cmd_args = args = args if args is not None else get_cmd_args()
-        from .conf_loader import load_conf
         # <path>/conf.py in the reference's format (`configuration` + `model_config`, gcp_builder.py:129-147) or <path>/conf.json
         name = args.config or "c2"
         # an explicit --config wins over conf.json's "config" entry (and names the default experiment directory below)
-        self.hp, conf, self.ignored_conf_keys = load_conf(args.path, default="c2", name=args.config)
+        self.hp, conf, self.ignored_conf_keys, self.data_dir, spec, data_opts = load_conf_with_data(
+            args.path, args.config, getattr(args, "data_dir", None))
         for k in self.ignored_conf_keys:
             if k.startswith("defaulted:"):
                 print(f"[train] {k[10:]} is not in the configuration file (the reference reads it from the dataset spec): "
@@ -106,6 +147,14 @@ class ModelTrainer:
         self.trainer = step_cls(self.model, lr=lr, betas=(conf.get("adam_beta", 0.9), 0.999), process_group=pg,
                                 optimizer=conf.get("optimizer", "radam"), momentum=conf.get("momentum", 0),
                                 gradient_clip=conf.get("gradient_clip"))                   # gcp_builder.py:174-186,255-263
+        if self.data_dir and (train_loader is None or val_loader is None):
+            # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val unshuffled
+            from .dataset import HostFedLoader, VideoDataset
+            reps = int(conf.get("epoch_cycles_train", 1))
+            mk = lambda phase: HostFedLoader(VideoDataset(self.data_dir, spec, phase, hp.img_sz, **data_opts), self.model, hp.batch_size,
+                                             n_repeat=reps, seed=seed, rank=self.rank, world=max(self.world, 1))
+            train_loader = train_loader or mk("train")
+            val_loader = val_loader or mk("val")
         if not args.feed_random_data and train_loader is None:
             raise ValueError("no dataset reader ships with this build: pass --feed_random_data 1 or give ModelTrainer a loader")
         self.train_loader = train_loader or SyntheticLoader(hp, nb, 1000 + 100000 * self.rank, self.device)
@@ -159,6 +208,8 @@ class ModelTrainer:
     # ---- train.py:132-193 ----
     def train_epoch(self, epoch):
         self.model.train()
+        if hasattr(self.train_loader, "set_epoch"):
+            self.train_loader.set_epoch(epoch)          # the dataset loader's shuffle and draws are keyed on the epoch
         end = time.time()
         for batch_idx, inputs in enumerate(self.train_loader):
             out = self.trainer.step(inputs)            # zero_grad, forward, loss, backward, (all-reduce), optimizer.step
