@@ -468,6 +468,19 @@ int gcpx_sample_length(const float* logits, const float* u, int32_t B, int32_t T
 int gcpx_image_metrics(const float* est, const float* tgt, const int32_t* frame_map, const int32_t* first, const int32_t* last,
                        int32_t B, int32_t T, int32_t C, int32_t H, int32_t W, double* scratch, float* out, void* stream);
 
+/* Top-of-N accumulation (csrc/topn.hip), one launch pair per prior sample n of N: the per-sample buffer update and best-sample
+ * bookkeeping of Evaluator.eval_single / _is_better / _get_best_idxs (gcp/evaluation/compute_metrics.py:89-120,236-250), called by
+ * Evaluator.eval inside ModelTrainer.val (gcp/prediction/train.py:205-210).
+ *   metrics [B][3] (gcpx_image_metrics' out) -> all[b][n][:]; best[b] = n when metrics[b][comp] is better than the best of samples 0..n-1
+ *   (strictly lower if lower_is_better, else strictly higher; a NaN beats any number: np.argmin / np.argmax order), best[b] = 0 at n = 0.
+ *   When sample n becomes best, its frames are copied: best_frames[b][t] = pool[frame_map[b*T + t]] for first[b] <= t < last[b]
+ *   (first / last NULL: no bound), best_full[b][j] = full_pool[full_map[b*F + j]]; a negative or >= *_rows row gives a zero frame.
+ *   Frames are rows of row_floats floats (a multiple of 4, 16-byte aligned).  T = 0 / F = 0: no such set (its pointers may be NULL). */
+int gcpx_topn_accumulate(const float* metrics, int32_t B, int32_t n, int32_t N, int32_t comp, int32_t lower_is_better, float* all,
+                         int32_t* best, const float* pool, int32_t pool_rows, const int32_t* frame_map, const int32_t* first,
+                         const int32_t* last, int32_t T, float* best_frames, const float* full_pool, int32_t full_rows,
+                         const int32_t* full_map, int32_t F, float* best_full, int64_t row_floats, void* stream);
+
 
 /* ===================================================================================================
  * Training step: explicit backward pass, optimizer.

@@ -13,6 +13,12 @@ trains and validates on a recorded dataset in the reference's layout stored as `
 host memory and assembled on the device); its dataset_spec.py overrides the model hyper-parameters (gcp_builder.py:68).  Without a
 data directory, `--feed_random_data 1` (the reference's own debug flag, gcp_builder.py:239, on by default) feeds the seeded
 synthetic batches of SURVEY §8d; `dataset` may also be any iterable of input dicts passed to ModelTrainer.
+Prediction metrics (gcp_builder.py:84-95, train.py:205-226): with `--skip_top100_val 0` every validation batch is also scored by
+evaluation.Evaluator (best of `--top_of` prior samples by mse, psnr and ssim after the configuration's `metric_pruning_scheme`, when
+`top_of_100_eval`), and <path>/metrics/results_<global_step>.txt / .npz plus the best samples' frames are written after each validation.
+`--metric 1` evaluates the `test` split, unshuffled, writes the results and returns: no training, no optimizer step, no checkpoint.
+Deviation: the reference defaults `--skip_top100_val` to 0; here it defaults to 1, so that a plain validation is what it was (the
+prior-sampled forward and the NLL).  `--top_of` (the reference's fixed `_top_of = 100`) is this build's.
 """
 import argparse
 import json
@@ -39,6 +45,10 @@ def get_cmd_args(argv=None):
     p.add_argument("--num_epochs", default=None, type=int)
     p.add_argument("--batches_per_epoch", default=None, type=int)
     p.add_argument("--data_dir", default=None, type=str, help="dataset directory (dataset_spec.py + hdf5/<phase>/*.npz, dataset.py)")
+    p.add_argument("--skip_top100_val", default=True, type=int, help="if 0, scores the best of --top_of prior samples at every validation "
+                   "(the reference's default is 0)")
+    p.add_argument("--metric", default=False, type=int, help="if 1, evaluates the test split, writes the metrics and returns")
+    p.add_argument("--top_of", default=100, type=int, help="prior samples per sequence of the top-of-N evaluation")
     return p.parse_args(argv)
 
 
@@ -77,6 +87,18 @@ def load_conf_with_data(path, config, data_dir=None, use_data=True):
     # randomize_length / randomize_start: model hyper-parameters of the reference (the dataset reads them from the model's hparams)
     opts = {k: bool(spec.get(k, model_config.get(k, configuration.get(k, False)))) for k in ("randomize_length", "randomize_start")}
     return hp, conf, ignored, data_dir, spec, opts
+
+
+def val_phase(args):
+    """the split validation reads (gcp_builder.py:84): `test` under --metric, `val` otherwise; both unshuffled (:119)"""
+    return "test" if getattr(args, "metric", False) else "val"
+
+
+def make_loader(data_dir, spec, phase, hp, model, data_opts, n_repeat=1, seed=0, rank=0, world=1):
+    """the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, shuffled in the train phase only"""
+    from .dataset import HostFedLoader, VideoDataset
+    return HostFedLoader(VideoDataset(data_dir, spec, phase, hp.img_sz, **data_opts), model, hp.batch_size, n_repeat=n_repeat, seed=seed,
+                         rank=rank, world=world)
 
 
 class SyntheticLoader:
@@ -148,25 +170,33 @@ class ModelTrainer:
                                 optimizer=conf.get("optimizer", "radam"), momentum=conf.get("momentum", 0),
                                 gradient_clip=conf.get("gradient_clip"))                   # gcp_builder.py:174-186,255-263
         if self.data_dir and (train_loader is None or val_loader is None):
-            # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val unshuffled
-            from .dataset import HostFedLoader, VideoDataset
+            # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val / test unshuffled
             reps = int(conf.get("epoch_cycles_train", 1))
-            mk = lambda phase: HostFedLoader(VideoDataset(self.data_dir, spec, phase, hp.img_sz, **data_opts), self.model, hp.batch_size,
-                                             n_repeat=reps, seed=seed, rank=self.rank, world=max(self.world, 1))
+            mk = lambda phase: make_loader(self.data_dir, spec, phase, hp, self.model, data_opts, n_repeat=reps, seed=seed, rank=self.rank,
+                                           world=max(self.world, 1))
             train_loader = train_loader or mk("train")
-            val_loader = val_loader or mk("val")
+            val_loader = val_loader or mk(val_phase(args))
         if not args.feed_random_data and train_loader is None:
             raise ValueError("no dataset reader ships with this build: pass --feed_random_data 1 or give ModelTrainer a loader")
         self.train_loader = train_loader or SyntheticLoader(hp, nb, 1000 + 100000 * self.rank, self.device)
         self.val_loader = val_loader or SyntheticLoader(hp, max(1, nb // 5), 500000 + 100000 * self.rank, self.device)
         self.global_step = 0
         self.log = []
+        # gcp_builder.py:91-95 (both models have a dense_rec here): the top-of-N evaluator, on --metric or --skip_top100_val 0
+        self.evaluator = None
+        if getattr(args, "metric", False) or not getattr(args, "skip_top100_val", True):
+            from .evaluation import Evaluator
+            self.evaluator = Evaluator(self.model, pruning_scheme=conf.get("metric_pruning_scheme", "dtw"),
+                                       top_of_100=bool(conf.get("top_of_100_eval", True)), top_of=int(getattr(args, "top_of", 100)))
 
     # ---- train.py:28-54 ----
     def run(self):
         start_epoch = 0
         if self.cmd_args.resume:
             start_epoch = self.resume(self.cmd_args.resume)
+        if getattr(self.cmd_args, "metric", False):
+            self.val()                                 # train.py:222-226: one evaluation pass of the test split, then stop
+            return
         if self.cmd_args.train:
             self.train(start_epoch)
         else:
@@ -230,16 +260,38 @@ class ModelTrainer:
         start = time.time()
         for inputs in self.val_loader:
             with self.model.val_mode(pred_length=False):
-                self.model(inputs, "test")
+                output = self.model(inputs, "test")
+                if self.evaluator is not None:         # train.py:208-209: every batch, prior samples of the model's own noise stream
+                    self.evaluator.eval(inputs, output, self.model)
             out = self.model(inputs)
             losses = self.model.loss(inputs, out)
             tot += float(self.model.get_total_loss(inputs, losses).value)
             n += 1
         avg = tot / max(n, 1)
         self.last_val = avg
+        if self.evaluator is not None:
+            self.dump_results()
+            if self.cmd_args.metric:
+                if self.rank == 0:
+                    print("Finished Evaluation! Exiting...", flush=True)
+                return avg
         if self.rank == 0:
             print("\nTest set: Average loss: {:.4f} in {:.2f}s\n".format(avg, time.time() - start), flush=True)
         return avg
+
+
+    # ---- train.py:217-219, compute_metrics.py:143-150: the evaluation of this validation, gathered on rank 0 and written there ----
+    def dump_results(self):
+        from .evaluation import gather_evaluation, write_results
+        ev = self.evaluator.collected()
+        self.evaluator.reset()
+        if ev is None or self.cmd_args.dont_save:
+            return None
+        pg = torch.distributed.group.WORLD if self.world > 1 else None
+        ev = gather_evaluation(ev, self.model._hp.batch_size, pg)
+        if self.rank != 0:
+            return None
+        return write_results(self.exp_path, self.global_step, ev, top_of_100=self.evaluator._top_of_100)
 
 
 if __name__ == "__main__":
