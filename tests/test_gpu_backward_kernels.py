@@ -908,3 +908,686 @@ def test_gn_lrelu_bwd_vs_float64(env, C_, cpg, M):
     # (+ 1e-12 of sum |dy|: float64 autograd leaves ~1e-16 where x_hat is exactly 0 — one channel per group, the constant row)
     _within(dgb[:C_], gg, ns * EPS * gsum_abs + EPS * gsum_c + 1e-12 * bsum_abs + 1e-30, "d gamma")
     _within(dgb[C_:2 * C_], gb, ns * EPS * bsum_abs + 1e-30, "d beta")
+
+
+def _gamma(n):
+    """n roundings: (1 + eps)^n - 1 <= n eps / (1 - n eps)"""
+    return n * EPS / (1.0 - n * EPS)
+
+
+def _same_bits(got, want, name):
+    """bit-for-bit equality of two f32 / int32 buffers, NaN sentinels included (an untouched NaN keeps its bits)"""
+    a, b = got.contiguous().view(torch.int32), want.contiguous().view(torch.int32)
+    if not torch.equal(a, b):
+        bad = torch.nonzero((a != b).flatten())[:, 0]
+        i = int(bad[0])
+        raise AssertionError(f"{name}: {len(bad)}/{a.numel()} elements differ in their bits; first at flat index {i}: got "
+                             f"{float(got.flatten()[i])} want {float(want.flatten()[i])}")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# i. LSTM cell backward (csrc/common.h: lstm_bwd_cell, launched by gcpx_lstm_bwd)
+# ------------------------------------------------------------------------------------------------------------------------------
+# (M, H, rpb, layout, inputs left NULL, scale of the pre-activations)
+_LSTM = [
+    (1, 64, 1, "flat", (), 1.0),
+    (37, 64, 3, "tree", (), 1.0),
+    (37, 128, 3, "tree", ("dh_dense",), 12.0),
+    (37, 128, 8, "tree", ("dh_pos",), 1.0),
+    (1000, 128, 8, "tree", ("dc_pos",), 12.0),
+    (1000, 256, 8, "tree", (), 12.0),
+    (37, 256, 1, "tree", (), 1.0),
+    (37, 64, 1, "flat", (), 12.0),
+    (37, 128, 1, "flat", ("dh_pos", "dc_pos"), 1.0),
+    (1000, 64, 1, "flat", (), 1.0),
+]
+
+
+@pytest.mark.parametrize("M,H,rpb,layout,nulls,scale", _LSTM)
+def test_lstm_bwd_vs_float64(env, M, H, rpb, layout, nulls, scale):
+    """gcpx_lstm_bwd against float64 autograd of c = f c_prev + i g, h = o tanh(c) for the loss sum h (dh_dense + dh_pos) + sum c dc_pos.
+    The kernel is handed what the forward stores — the activated gates rounded to f32 in the [M][H][4] (i, f, g, o) layout and c rounded
+    to f32 — so the reference differentiates the cell with respect to the stored activations by autograd (c pinned to the stored value)
+    and multiplies by s (1 - s) / 1 - t^2 evaluated at those stored values in float64: the function the backward differentiates.
+    Layouts: "tree" (backward_plan.py:203-213): rows (b, j) of a level in the position layout of Hid / dHid (pb, prow larger than the
+    rows they address, layer 1 of 2: c at column 3H, d h at 2H, d c at 3H of a 4H-wide slot), c_prev / dc_prev at column 3H of the 4H-wide
+    merged / dmerged rows; "flat" (training_sequential.py:130-142): rpb 1, pitch 2H with prow 0, dh_dense rows of stride 2H, dc_prev
+    written over dc_pos in place.  Every input element the kernel must not read is NaN (a stray read poisons an output), the gaps of
+    dc_prev's buffer must keep their NaN.  Each of dh_dense / dh_pos / dc_pos NULL in turn (and both recurrent terms, the flat model's
+    last step).  M H not a multiple of 256 except at H = 256.  Saturation: pre-activations at scale 12, planted gates of exactly 0, 1,
+    -1 and stored |c| up to 20 (tanh' underflows): those gradients are exactly 0 or tiny and finite.
+    Tolerance, per element, 18 eps x abs-terms + 2^-125, counted from lstm_bwd_cell: dh = dh_above + dh_pos rounds once (1); tanhf is
+    within 2 ulp = 4 eps, so t^2 is within 9 eps of itself and q = 1 - t^2 within 10 eps of its abs-terms 1 + t^2; dh o q adds two
+    products: 13 eps of A_dh o (1 + t^2) with A_dh = |dh_above| + |dh_pos|; adding dc_pos: dc within 14 eps of A_dc = |dc_pos| + A_dh o
+    (1 + t^2).  di = dc g i (1 - i): three products and the subtraction of a stored value from 1 (one relative rounding): 18 eps of
+    A_dc |g| i (1 - i); df likewise with c_prev; dg = dc i (1 - g^2): 17 eps of A_dc i (1 + g^2); do = dh t o (1 - o): 9 eps of
+    A_dh |t| o (1 - o); dc_prev = dc f: 15 eps of A_dc f.  2^-125: products below the normal range may flush.
+    The GEMM-epilogue form (gcpx_gemm_args.lstm_bwd) runs the same device function on the same values:
+    test_gemm_lstm_bwd_epilogue_equals_separate_launch (test_gpu_kernels.py) holds it bit for bit to this kernel, which carries this
+    result over to it."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(M * 131 + H + 7 * rpb + int(scale))
+    pre = torch.randn(4, M, H, device=dev, generator=g) * scale
+    p64 = pre.double()
+    gates = torch.stack([torch.sigmoid(p64[0]), torch.sigmoid(p64[1]), torch.tanh(p64[2]), torch.sigmoid(p64[3])], -1).float().contiguous()
+    cp = torch.randn(M, H, device=dev, generator=g) * (3.0 if scale > 1 else 1.0)
+    flat_i = torch.arange(M * H, device=dev).view(M, H)
+    # planted gates: every 8th element, six patterns in turn
+    pat = torch.where(flat_i % 8 == 0, (flat_i // 8) % 6, torch.full_like(flat_i, -1))
+    gates[..., 0][pat == 0] = 1.0
+    gates[..., 0][pat == 1] = 0.0
+    gates[..., 1][pat == 2] = 1.0
+    gates[..., 3][pat == 2] = 0.0
+    gates[..., 2][pat == 3] = 1.0
+    gates[..., 2][pat == 4] = -1.0
+    gates[..., 3][pat == 4] = 1.0
+    gates[..., 1][pat == 5] = 0.0
+    g64 = gates.double()
+    c_new = (g64[..., 1] * cp.double() + g64[..., 0] * g64[..., 2]).float()
+    cvals = torch.tensor([20.0, -20.0, 9.5, -9.5, 0.0, -0.0, 15.0, -12.0], device=dev)
+    csel = flat_i % 8 == 4
+    c_new[csel] = cvals[(flat_i[csel] // 8) % 8]
+    dhd = torch.randn(M, H, device=dev, generator=g)
+    dhp = torch.randn(M, H, device=dev, generator=g)
+    dcp = torch.randn(M, H, device=dev, generator=g)
+    r = torch.arange(M, device=dev)
+    if layout == "tree":
+        s, SD = 1, 4 * H
+        Bn, PS = (M + rpb - 1) // rpb, 2 * rpb + 3
+        c_col, dh_col, dc_col, cp_col, cp_ld, dhd_ld = 3 * H, 2 * H, 3 * H, 3 * H, SD, H
+    else:
+        assert rpb == 1
+        s, SD, Bn, PS = 0, 2 * H, M, 1
+        c_col, dh_col, dc_col, cp_col, cp_ld, dhd_ld = H, H, 0, H, 2 * H, 2 * H
+    bi, sl = r // rpb, s + 2 * s * (r % rpb)
+    pb, prow = PS * SD, 2 * s * SD
+    Hid, dHid = _nan(Bn, PS, SD), _nan(Bn, PS, SD)
+    dcbuf = dHid if layout == "tree" else _nan(Bn, PS, SD)             # flat: the dc buffer is its own [B][2H] block, dc_prev written in place
+    Hid[bi, sl, c_col:c_col + H] = c_new
+    if "dh_pos" not in nulls:
+        dHid[bi, sl, dh_col:dh_col + H] = dhp
+    if "dc_pos" not in nulls:
+        dcbuf[bi, sl, dc_col:dc_col + H] = dcp
+    merged = _nan(M, cp_ld)
+    merged[:, cp_col:cp_col + H] = cp
+    above = _nan(M, dhd_ld)
+    above[:, :H] = dhd
+    dgates = _nan(M, 4 * H)
+    if layout == "tree":
+        dmerged = _nan(M, SD)
+        dcp_ptr, dcp_stride = dmerged.data_ptr() + 4 * cp_col, SD
+    else:
+        dmerged = dcbuf
+        dcp_ptr, dcp_stride = dcbuf.data_ptr(), 2 * H
+    a = rt.LstmBwdArgs()
+    a.gates = gates.data_ptr()
+    a.c_prev, a.c_prev_stride = merged.data_ptr() + 4 * cp_col, cp_ld
+    a.c_new, a.pb, a.prow = Hid.data_ptr() + 4 * (s * SD + c_col), pb, prow
+    a.dh_dense, a.dh_stride = (None if "dh_dense" in nulls else above.data_ptr()), dhd_ld
+    a.dh_pos = None if "dh_pos" in nulls else dHid.data_ptr() + 4 * (s * SD + dh_col)
+    a.dc_pos = None if "dc_pos" in nulls else dcbuf.data_ptr() + 4 * (s * SD + dc_col)
+    a.dgates, a.dc_prev, a.dcp_stride = dgates.data_ptr(), dcp_ptr, dcp_stride
+    a.M, a.H, a.rpb = M, H, rpb
+    rt.check(lib.gcpx_lstm_bwd(C.byref(a), _st()), "lstm_bwd")
+    torch.cuda.synchronize()
+    # reference
+    zero = torch.zeros(M, H, device=dev, dtype=torch.float64)
+    dh_a = zero if "dh_dense" in nulls else dhd.double()
+    dh_p = zero if "dh_pos" in nulls else dhp.double()
+    dc_p = zero if "dc_pos" in nulls else dcp.double()
+    ga = gates.double().requires_grad_(True)
+    cp64 = cp.double().requires_grad_(True)
+    c_lin = ga[..., 1] * cp64 + ga[..., 0] * ga[..., 2]
+    c = c_lin + (c_new.double() - c_lin).detach()                     # the stored c, with the cell's dependence on its inputs
+    h = ga[..., 3] * torch.tanh(c)
+    gga, gcp = torch.autograd.grad((h * (dh_a + dh_p)).sum() + (c * dc_p).sum(), (ga, cp64))
+    with torch.no_grad():
+        si, sf, tg, so = g64[..., 0], g64[..., 1], g64[..., 2], g64[..., 3]
+        act_d = torch.stack([si * (1 - si), sf * (1 - sf), 1 - tg * tg, so * (1 - so)], 1)           # [M][4][H]
+        want = gga.permute(0, 2, 1) * act_d
+        t = torch.tanh(c_new.double())
+        A_dh = dh_a.abs() + dh_p.abs()
+        A_dc = dc_p.abs() + A_dh * so * (1 + t * t)
+        ab = torch.stack([A_dc * tg.abs() * si * (1 - si), A_dc * cp.double().abs() * sf * (1 - sf), A_dc * si * (1 + tg * tg),
+                          A_dh * t.abs() * so * (1 - so)], 1)
+        ab_cp = A_dc * sf
+    tiny = 2.0 ** -125
+    w1 = _within(dgates.view(M, 4, H), want, 18 * EPS * ab + tiny, "dgates (i | f | g | o)")
+    if layout == "tree":
+        got_cp = dmerged[:, cp_col:cp_col + H]
+        mask = torch.zeros_like(dmerged, dtype=torch.bool)
+        mask[:, cp_col:cp_col + H] = True
+    else:
+        got_cp = dcbuf[:, 0, :H]
+        mask = torch.zeros_like(dcbuf, dtype=torch.bool)
+        mask[:, 0, :H] = True
+    w2 = _within(got_cp, gcp, 18 * EPS * ab_cp + tiny, "dc_prev")
+    _untouched(dmerged[~mask], "gaps of the dc_prev buffer")
+    # the planted saturated elements: exactly-0 derivative factors give exactly 0
+    dg4 = dgates.view(M, 4, H)
+    assert bool((dg4[:, 0][(pat == 0) | (pat == 1)] == 0).all()) and bool((dg4[:, 2][(pat == 3) | (pat == 4)] == 0).all())
+    assert bool((dg4[:, 1][(pat == 2) | (pat == 5)] == 0).all()) and bool((dg4[:, 3][(pat == 2) | (pat == 4)] == 0).all())
+    print(f"lstm_bwd M={M} H={H} rpb={rpb} {layout} nulls={nulls} scale={scale}: worst err / tol {max(w1, w2):.3f}")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# j. tree and sequence bookkeeping
+# ------------------------------------------------------------------------------------------------------------------------------
+# (n, width, sources: (ld, off_left, off_right, off_ctx0, off_ctxg, dst_col)), row width of the destination
+_ACCUM = [
+    (1, 32, [(2 * 32, 0, 32, -1, -1, 0)], 32),                                                   # backward_plan.py:117 (length head)
+    (1, 32, [(4 * 32 + 8, 0, 32, 64, 96, 0)], 40),                                               # n = 1: slot 0 is left parent and e_0
+    (2, 100, [(4 * 100 + 4, 0, 100, 200, 300, 4), (2 * 100, 0, 100, -1, -1, 4)], 112),            # two sources into the same columns
+    (16, 128, [(2 * 128, 0, 128, -1, -1, j * 128) for j in range(4)], 4 * 128 + 16),              # backward_plan.py:300: disjoint columns
+    (16, 32, [(4 * 32 + 8, 0, 32, 72, 104, 0), (64, 0, 32, -1, -1, 0), (64, 32, 0, -1, -1, 0), (96, 0, 32, -1, -1, 0), (64, 0, 32, -1, -1, 0),
+              (64, -1, -1, 0, 32, 0)], 32),                                                      # backward_plan.py:366-372, nsrc 6
+    (64, 128, [(4 * 128, 0, 128, 256, 384, 0), (128, 0, 0, -1, -1, 0), (128, -1, 0, -1, -1, 0)], 128),   # :275 (sum tree: both offsets 0)
+    (64, 100, [(200, 100, 0, -1, -1, 0)], 100),
+]
+
+
+@pytest.mark.parametrize("n,width,srcs,roww", _ACCUM)
+def test_tree_accum_vs_float64(env, n, width, srcs, roww):
+    """gcpx_tree_accum as backward_ops.py:417-424 fills it, against float64 autograd of the forward it inverts: parents P[b][0..n] (row
+    dst + b dst_sb + k slot_stride, columns dst_col .. + width), the level's input row (b, k) of source s = [P[k] | P[k + 1] | P[0] |
+    P[n]] at off_left / off_right / off_ctx0 / off_ctxg of its ld-wide dense row (-1: absent), loss = sum over sources of src x input;
+    expected dst_after = dst_before + dP.  n = 1 (slot 0 is the left child's parent and e_0, slot 1 the right one's and e_g), 2, 16, 64;
+    1 to 6 sources; sources sharing a dst_col and sources on disjoint columns of a wider row; width 100 (the masked second 64-lane
+    workgroup); ld wider than the used columns (the unused ones NaN).  The slots between the level's parents, the slots behind them and
+    the destination rows' other columns hold NaN and must keep it.
+    Tolerance (n + nsrc + 1) eps x abs-terms: a source adds at most 2 + n terms in f32 before it is added to the slot, nsrc sources."""
+    rt, pk, lib, dev = env
+    B, step = 3, 2
+    g = torch.Generator(device=dev).manual_seed(n * 1000 + width + len(srcs))
+    PS = n * step + 2
+    dst = _nan(B, PS, roww)
+    covered = torch.zeros(roww, dtype=torch.bool, device=dev)
+    for s in srcs:
+        covered[s[5]:s[5] + width] = True
+    before = torch.randn(B, n + 1, roww, device=dev, generator=g)
+    par = torch.arange(n + 1, device=dev) * step
+    dst[:, par] = torch.where(covered, before, torch.full_like(before, NAN))
+    a = rt.TreeAccumArgs()
+    bufs = []
+    P = torch.zeros(B, n + 1, roww, device=dev, dtype=torch.float64, requires_grad=True)
+    loss, loss_abs = 0.0, 0.0
+    for i, (ld, ol, orr, c0, cg, dcol) in enumerate(srcs):
+        t = _nan(B * n, ld)
+        for off in (ol, orr, c0, cg):
+            if off >= 0:
+                t[:, off:off + width] = torch.randn(B * n, width, device=dev, generator=g)
+        bufs.append(t)
+        sa = a.src[i]
+        sa.ptr, sa.ld, sa.off_left, sa.off_right, sa.off_ctx0, sa.off_ctxg, sa.dst_col = t.data_ptr(), ld, ol, orr, c0, cg, dcol
+        t64 = t.double().view(B, n, ld)
+        Pc = P[..., dcol:dcol + width]
+        parts = ((ol, Pc[:, :n]), (orr, Pc[:, 1:]), (c0, Pc[:, :1].expand(B, n, width)), (cg, Pc[:, n:].expand(B, n, width)))
+        for off, inp in parts:
+            if off >= 0:
+                loss = loss + (t64[..., off:off + width] * inp).sum()
+                loss_abs = loss_abs + (t64[..., off:off + width].abs() * inp).sum()
+    a.dst, a.dst_sb, a.slot_stride, a.nsrc, a.B, a.n, a.width = dst.data_ptr(), PS * roww, step * roww, len(srcs), B, n, width
+    rt.check(lib.gcpx_tree_accum(C.byref(a), _st()), "tree_accum")
+    torch.cuda.synchronize()
+    (dP,) = torch.autograd.grad(loss, P, retain_graph=True)
+    (dPa,) = torch.autograd.grad(loss_abs, P)
+    got = dst[:, par]
+    w = _within(got[..., covered], (before.double() + dP)[..., covered], (n + len(srcs) + 1) * EPS * (before.double().abs() + dPa)[..., covered],
+                "parent slots")
+    _untouched(got[..., ~covered], "other columns of the parent rows")
+    other = torch.ones(PS, dtype=torch.bool, device=dev)
+    other[par] = False
+    _untouched(dst[:, other], "slots between and behind the level's parents")
+    print(f"tree_accum n={n} width={width} nsrc={len(srcs)}: worst err / tol {w:.3f}")
+
+
+@pytest.mark.parametrize("L,T,nz,pitch", [(5, 20, 32, 32), (5, 20, 200, 216), (7, 80, 32, 48), (7, 80, 200, 200)])
+def test_timestep_scatter_vs_float64(env, L, T, nz, pitch):
+    """gcpx_timestep_scatter as backward_plan.py:402 calls it (det = the position-layout gradient one slot in: batch stride PS x pitch,
+    node stride pitch; pitch = nz as there, and wider with NaN between the rows) with node_t from gcpx_balanced_binding for end_ind =
+    1, 2, T / 2, T - 1 in one batch: a short sequence maps many nodes to one timestep and most of its timesteps receive nothing — those are
+    written as 0, not left NaN.  nz = 200 > 128 threads: the column loop.  Reference: float64 index_add_ over the nodes whose timestep
+    lies in [0, T).  Tolerance: count eps x abs-terms, count = the nodes a timestep receives (a serial sum; one node is a copy)."""
+    rt, pk, lib, dev = env
+    B, N = 4, 2 ** L - 1
+    g = torch.Generator(device=dev).manual_seed(L * T + nz)
+    end = torch.tensor([1, 2, T // 2, T - 1], dtype=torch.long, device=dev)
+    node_t, leave = torch.zeros(B, N, dtype=torch.int32, device=dev), torch.zeros(B, N, dtype=torch.int32, device=dev)
+    f2n, et = torch.zeros(B, T, dtype=torch.int32, device=dev), torch.zeros(B * N, dtype=torch.int32, device=dev)
+    sl, n2r = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, N, dtype=torch.int32, device=dev)
+    rt.check(lib.gcpx_balanced_binding(end.data_ptr(), B, L, T, node_t.data_ptr(), leave.data_ptr(), f2n.data_ptr(), et.data_ptr(),
+                                       sl.data_ptr(), n2r.data_ptr(), _st()), "binding")
+    PS = N + 2
+    det = _nan(B, PS, pitch)
+    vals = torch.randn(B, N, nz, device=dev, generator=g)
+    det[:, 1:N + 1, :nz] = vals
+    out = _nan(B, T, nz)
+    rt.check(lib.gcpx_timestep_scatter(det.data_ptr() + 4 * pitch, PS * pitch, pitch, node_t.data_ptr(), out.data_ptr(), B, N, T, nz, _st()),
+             "timestep_scatter")
+    torch.cuda.synchronize()
+    want = torch.zeros(B, T, nz, dtype=torch.float64, device=dev)
+    wabs, cnt = torch.zeros_like(want), torch.zeros(B, T, dtype=torch.float64, device=dev)
+    for b in range(B):
+        ok = (node_t[b] >= 0) & (node_t[b] < T)
+        ti = node_t[b][ok].long()
+        want[b].index_add_(0, ti, vals[b][ok].double())
+        wabs[b].index_add_(0, ti, vals[b][ok].double().abs())
+        cnt[b].index_add_(0, ti, torch.ones(len(ti), dtype=torch.float64, device=dev))
+    assert float(cnt[0].max()) >= 2 and bool((cnt[0] == 0).any()), "the short sequence must share timesteps and leave some empty"
+    w = _within(out, want, cnt[..., None] * EPS * wabs, "d inference input per timestep")
+    assert bool((out[cnt == 0] == 0).all())
+    print(f"timestep_scatter L={L} T={T} nz={nz}: worst err / tol {w:.3f}; up to {int(cnt.max())} nodes per timestep")
+
+
+@pytest.mark.parametrize("B,rpb,width,dst_sr,with_src2", [(3, 7, 32, 32, False), (3, 7, 32, 64, True), (4, 15, 100, 100, True),
+                                                          (2, 11, 128, 128, False)])
+def test_add_rows_vs_float64(env, B, rpb, width, dst_sr, with_src2):
+    """gcpx_add_rows as backward_plan.py:156-161 / training_sequential.py:330 call it: dst rows (b, j) one slot into a [B][PS][width]
+    position buffer (dst_sr = width as there, and 2 width with NaN rows between), dense sources, src2 NULL or given; B rpb width not a
+    multiple of 256.  One source: dst + src is ONE correctly rounded f32 addition, so the result equals float32(float64(dst) +
+    float64(src)) bit for bit (the float64 sum of two f32 is exact).  Two sources: (src1 + src2) rounds first: 2 eps of |dst| + |src1| +
+    |src2|.  Rows the kernel does not address keep their NaN bits."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(B + rpb + width)
+    step = dst_sr // width
+    PS = rpb * step + 2
+    dst = _nan(B, PS, width)
+    rows = 1 + torch.arange(rpb, device=dev) * step
+    before = torch.randn(B, rpb, width, device=dev, generator=g)
+    dst[:, rows] = before
+    s1 = torch.randn(B * rpb, width, device=dev, generator=g)
+    s2 = torch.randn(B * rpb, width, device=dev, generator=g) if with_src2 else None
+    want = dst.clone()
+    rt.check(lib.gcpx_add_rows(dst.data_ptr() + 4 * width, PS * width, dst_sr, s1.data_ptr(), rt.ptr(s2), B, rpb, width, _st()), "add_rows")
+    torch.cuda.synchronize()
+    ref = before.double() + s1.double().view(B, rpb, width) + (s2.double().view(B, rpb, width) if with_src2 else 0.0)
+    if not with_src2:
+        want[:, rows] = ref.float()
+        _same_bits(dst, want, "dst += src1")
+    else:
+        ab = before.double().abs() + s1.double().abs().view(B, rpb, width) + s2.double().abs().view(B, rpb, width)
+        w = _within(dst[:, rows], ref, 2 * EPS * ab, "dst += src1 + src2")
+        print(f"add_rows B={B} rpb={rpb} width={width} two sources: worst err / tol {w:.3f}")
+        other = torch.ones(PS, dtype=torch.bool, device=dev)
+        other[rows] = False
+        _untouched(dst[:, other], "rows between / around the addressed ones")
+
+
+# (name, mode, B, rpb, width, dst offset, dst_sb, dst_sr, src offset, src_sb, src_sr)
+_ROWS = [
+    ("forward_plan.py:418 one zero-state row broadcast to a slot of every batch element", 0, 5, 1, 100, 200, 9 * 100, 0, 0, 0, 0),
+    ("forward_plan.py:359 left parents -> dense merged rows", 0, 3, 4, 64, 0, 4 * 64, 64, 0, 11 * 64, 2 * 64),
+    ("forward_plan.py:359 right parents added", 1, 3, 4, 64, 0, 4 * 64, 64, 2 * 64, 11 * 64, 2 * 64),
+    ("backward_ops.py:373 un-padding copy (B 1, width = dst pitch < src pitch)", 0, 1, 128, 5, 0, 0, 5, 0, 0, 16),
+    ("training_sequential.py:308 per-step input gradient slices", 1, 3, 9, 32, 0, 10 * 32, 32, 0, 9 * 80, 80),
+    ("training_sequential.py:228 one row per batch element", 1, 7, 1, 32, 0, 10 * 32, 0, 0, 64, 0),
+    ("training_sequential.py:419 copy behind the first step", 0, 3, 9, 32, 32, 10 * 32, 32, 0, 9 * 48, 48),
+    ("training_sequential.py:429 context gradient summed over the steps", 2, 3, 9, 32, 0, 10 * 32, 0, 40, 9 * 104, 104),
+    ("training_sequential.py:430 dense goal gradient, 33 steps", 2, 5, 33, 100, 0, 100, 0, 0, 33 * 100, 100),
+]
+
+
+@pytest.mark.parametrize("name,mode,B,rpb,width,doff,dst_sb,dst_sr,soff,src_sb,src_sr", _ROWS, ids=[r[0].split(" ")[0] + f"-m{r[1]}-{i}"
+                                                                                                   for i, r in enumerate(_ROWS)])
+def test_rows_strided_vs_float64(env, name, mode, B, rpb, width, doff, dst_sb, dst_sr, soff, src_sb, src_sr):
+    """gcpx_rows_strided with the strides of its call sites (named per case), the degenerate ones included: src_sb = src_sr = dst_sr = 0
+    with rpb 1 (one source row broadcast into a row of every batch element), dst_sb = src_sb = 0 with B 1 (the un-padding copy: width =
+    destination pitch < source pitch), mode 2's sum over j in order.  Against float64 index arithmetic on flat buffers whose unaddressed
+    elements are NaN (sources: a stray read poisons; destinations: must keep the NaN bits).  Mode 0 is a copy and mode 1 ONE correctly
+    rounded addition: both bit for bit (float32(float64(dst) + float64(src))); mode 2: rpb eps x abs-terms (rpb - 1 additions of the
+    ordered sum, one into dst).  Totals (B rpb width, B width for mode 2) not a multiple of 256 in most cases."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(B * rpb + width + mode)
+    b_, j_, c_ = torch.meshgrid(torch.arange(B, device=dev), torch.arange(rpb, device=dev), torch.arange(width, device=dev), indexing="ij")
+    si = soff + b_ * src_sb + j_ * src_sr + c_
+    di = doff + b_ * dst_sb + (0 if mode == 2 else j_ * dst_sr) + c_
+    src = _nan(int(si.max()) + 9)
+    vals = torch.randn(B, rpb, width, device=dev, generator=g)
+    src[si.flatten()] = vals.flatten()
+    vals = src[si]                                                    # (a broadcast source: every (b, j) sees the last value written)
+    dst = _nan(int(di.max()) + 9)
+    if mode != 0:
+        dst[di.flatten()] = torch.randn(di.numel(), device=dev, generator=g)
+    before = dst.clone()
+    rt.check(lib.gcpx_rows_strided(dst.data_ptr() + 4 * doff, dst_sb, dst_sr, src.data_ptr() + 4 * soff, src_sb, src_sr, B, rpb, width, mode,
+                                   _st()), "rows_strided")
+    torch.cuda.synchronize()
+    want = before.clone()
+    if mode == 0:
+        want[di.flatten()] = vals.flatten()
+        _same_bits(dst, want, name)
+    elif mode == 1:
+        assert di.unique().numel() == di.numel()
+        want[di.flatten()] = (before[di].double() + vals.double()).float().flatten()
+        _same_bits(dst, want, name)
+    else:
+        d0 = di[:, 0]
+        ref = before[d0].double() + vals.double().sum(1)
+        ab = before[d0].double().abs() + vals.double().abs().sum(1)
+        w = _within(dst[d0], ref, rpb * EPS * ab, name)
+        mask = torch.ones_like(dst, dtype=torch.bool)
+        mask[d0.flatten()] = False
+        _untouched(dst[mask], "unaddressed destination elements")
+        print(f"rows_strided mode 2 rpb={rpb}: worst err / tol {w:.3f}")
+
+
+@pytest.mark.parametrize("n", [1000, 256 * 5 + 1])
+def test_lrelu_bwd_bit_exact(env, n):
+    """gcpx_lrelu_bwd (backward_ops.py:334, backward_stages.py:230): dx = dy x (a > 0 ? 1 : slope) is ONE correctly rounded f32 product, so
+    it equals float32(float64(dy) x (a > 0 ? 1 : float64(float32(slope)))) bit for bit (the float64 product of two f32 is exact).  `a`
+    holds +0.0 and -0.0 (both take the slope), positive and negative denormals (a positive denormal is > 0), negatives; n is not a multiple
+    of 256."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(n)
+    a_host = torch.randn(n, generator=torch.Generator().manual_seed(n))      # planted on the host: no device kernel between the values and the test
+    a_host[0::10] = 0.0
+    a_host[1::10] = -0.0
+    a_host[2::10] = 1e-40
+    a_host[3::10] = -1e-40
+    a_host[4::10] = 2.0 ** -149
+    assert bool((a_host[2::10] > 0).all()) and bool((a_host[3::10] < 0).all()) and float(a_host[4]) > 0.0
+    a = a_host.to(dev)
+    dy = torch.randn(n, device=dev, generator=g)
+    slope = C.c_float(0.2)
+    dx = _nan(n + 8)
+    rt.check(lib.gcpx_lrelu_bwd(a.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, slope, _st()), "lrelu_bwd")
+    torch.cuda.synchronize()
+    want = _nan(n + 8)
+    mult = torch.where(a_host > 0, torch.tensor(1.0, dtype=torch.float64), torch.tensor(float(slope.value), dtype=torch.float64)).to(dev)
+    want[:n] = (dy.double() * mult).float()
+    _same_bits(dx, want, "lrelu_bwd")
+
+
+@pytest.mark.parametrize("B,rpb,width,s", [(3, 4, 32, 2), (5, 1, 32, 4), (2, 16, 100, 1)])
+def test_tanh_bwd_rows_vs_float64(env, B, rpb, width, s):
+    """gcpx_tanh_bwd_rows as backward_plan.py:189 calls it: dy and y rows (b, j) of a tree level in the position layout (base one level
+    offset s in, batch stride PS width, row stride 2 s width; every other element NaN), dx dense [B rpb][width]; y holds exactly +1 and
+    -1 (dx exactly 0 there).  Tolerance 3 eps of |dy| (1 + y^2): y^2, the subtraction against its abs-terms 1 + y^2, the product."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(B * rpb + width)
+    PS = 2 * s * rpb + s + 1
+    slots = s + 2 * s * torch.arange(rpb, device=dev)
+    Y, dY = _nan(B, PS, width), _nan(B, PS, width)
+    y = torch.tanh(torch.randn(B, rpb, width, device=dev, generator=g) * 3)
+    y[:, :, 0::7] = 1.0
+    y[:, :, 3::7] = -1.0
+    dy = torch.randn(B, rpb, width, device=dev, generator=g)
+    Y[:, slots], dY[:, slots] = y, dy
+    dx = _nan(B * rpb * width + 8)
+    rt.check(lib.gcpx_tanh_bwd_rows(dY.data_ptr() + 4 * s * width, Y.data_ptr() + 4 * s * width, dx.data_ptr(), PS * width, 2 * s * width, B, rpb,
+                                    width, _st()), "tanh_bwd_rows")
+    torch.cuda.synchronize()
+    _untouched(dx[B * rpb * width:], "past the dense output")
+    y64, dy64 = y.double(), dy.double()
+    got = dx[:B * rpb * width].view(B, rpb, width)
+    w = _within(got, dy64 * (1 - y64 * y64), 3 * EPS * dy64.abs() * (1 + y64 * y64), "dx")
+    assert bool((got[:, :, 0::7] == 0).all()) and bool((got[:, :, 3::7] == 0).all())
+    print(f"tanh_bwd_rows B={B} rpb={rpb} width={width}: worst err / tol {w:.3f}")
+
+
+@pytest.mark.parametrize("row_floats", [4, 32 * 32 * 112])
+@pytest.mark.parametrize("pattern", ["ends_mapped", "all_mapped", "none_mapped"])
+def test_zero_unmapped_rows_exact(env, row_floats, pattern):
+    """gcpx_zero_unmapped_rows (forward_plan.py:244, sequential.py:489): rows with row2frame < 0 become exactly 0, mapped rows are not
+    touched (they hold NaN before and after, bit for bit).  row_floats = 4 (one float4) and S S pitch of the 32 x 32 head (28672 float4 >
+    64 x 256 threads: the grid-stride loop); first and last row mapped / every row / none."""
+    rt, pk, lib, dev = env
+    rows = 6
+    r2f = {"ends_mapped": [3, -1, 0, -1, -1, 7], "all_mapped": [0, 1, 2, 3, 4, 5], "none_mapped": [-1] * 6}[pattern]
+    r2f = torch.tensor(r2f, dtype=torch.int32, device=dev)
+    buf = torch.randn(rows + 1, row_floats, device=dev)
+    buf[:rows][r2f >= 0] = NAN
+    buf[rows] = NAN                                                   # the row behind the last one
+    want = buf.clone()
+    want[:rows][r2f < 0] = 0.0
+    rt.check(lib.gcpx_zero_unmapped_rows(buf.data_ptr(), row_floats, r2f.data_ptr(), rows, _st()), "zero_unmapped_rows")
+    torch.cuda.synchronize()
+    _same_bits(buf, want, "zero_unmapped_rows")
+
+
+def test_index_offset_and_inverse_exact(env):
+    """gcpx_index_offset (backward_stages.py:56: out[b][t] = idx[b][t] + b stride, B T not a multiple of 256) and gcpx_index_inverse
+    (forward_plan.py:238, backward_stages.py:98) on node2row from gcpx_balanced_binding (negative entries for nodes that match no frame;
+    every non-negative entry < n_inv = B T, as the planner produces them): inv[r] = the node that maps to row r, -1 for rows nobody
+    maps to (padded frames), over a prefilled buffer.  Exact."""
+    rt, pk, lib, dev = env
+    L, T, B = 5, 20, 4
+    N = 2 ** L - 1
+    end = torch.tensor([1, 2, T // 2, T - 1], dtype=torch.long, device=dev)
+    node_t, leave = torch.zeros(B, N, dtype=torch.int32, device=dev), torch.zeros(B, N, dtype=torch.int32, device=dev)
+    f2n, et = torch.zeros(B, T, dtype=torch.int32, device=dev), torch.zeros(B * N, dtype=torch.int32, device=dev)
+    sl, n2r = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, N, dtype=torch.int32, device=dev)
+    rt.check(lib.gcpx_balanced_binding(end.data_ptr(), B, L, T, node_t.data_ptr(), leave.data_ptr(), f2n.data_ptr(), et.data_ptr(),
+                                       sl.data_ptr(), n2r.data_ptr(), _st()), "binding")
+    out = torch.full((B * T + 4,), -77, dtype=torch.int32, device=dev)
+    rt.check(lib.gcpx_index_offset(f2n.data_ptr(), out.data_ptr(), B, T, N, _st()), "index_offset")
+    inv = torch.full((B * T + 4,), 12345, dtype=torch.int32, device=dev)
+    rt.check(lib.gcpx_index_inverse(n2r.data_ptr(), B * N, inv.data_ptr(), B * T, _st()), "index_inverse")
+    torch.cuda.synchronize()
+    assert torch.equal(out[:B * T].view(B, T), f2n + torch.arange(B, device=dev, dtype=torch.int32)[:, None] * N)
+    assert bool((out[B * T:] == -77).all())
+    fwd = n2r.flatten().long()
+    assert bool((fwd < 0).any()) and int(fwd.max()) < B * T
+    want = torch.full((B * T,), -1, dtype=torch.int32, device=dev)
+    valid = torch.nonzero(fwd >= 0)[:, 0]
+    assert fwd[valid].unique().numel() == valid.numel()
+    want[fwd[valid]] = valid.int()
+    assert torch.equal(inv[:B * T], want) and bool((want == -1).any())
+    assert bool((inv[B * T:] == 12345).all())
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# k. encoder data gradient and first-layer patches
+# ------------------------------------------------------------------------------------------------------------------------------
+def _unfold_rows(x):
+    """F.unfold(x, 4, padding=1, stride=2) of NCHW x as rows [F Ho Wo][tap][ci] (tap = ky 4 + kx)"""
+    Fr, Ci = x.shape[:2]
+    u = F.unfold(x, 4, padding=1, stride=2)                           # [F][ci 16 + tap][Ho Wo]
+    return u.view(Fr, Ci, 16, -1).permute(0, 3, 2, 1)
+
+
+@pytest.mark.parametrize("H,W,Cin,Fr", [(4, 4, 4, 1), (4, 4, 64, 5), (8, 8, 16, 5), (8, 8, 64, 1), (64, 64, 4, 5), (64, 64, 64, 1),
+                                        (16, 8, 16, 5), (8, 16, 4, 1)])
+def test_col2im4x4s2_vs_float64(env, H, W, Cin, Fr):
+    """gcpx_col2im4x4s2 (backward_stages.py:319) against float64 autograd of F.unfold(x, 4, padding=1, stride=2) re-ordered to the
+    kernel's columns k = (tap, ci): dx = the gradient of sum(unfold(x) x dcol) w.r.t. x, NHWC.  4 x 4: every pixel is a border pixel (one
+    to four taps); H != W both ways.  At most 4 addends: 4 eps x abs-terms."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(H * W + Cin + Fr)
+    Ho, Wo = H // 2, W // 2
+    dcol = torch.randn(Fr * Ho * Wo, 16 * Cin, device=dev, generator=g)
+    dx = _nan(Fr * H * W * Cin + 8)
+    rt.check(lib.gcpx_col2im4x4s2(dcol.data_ptr(), dx.data_ptr(), Fr, H, W, Cin, _st()), "col2im4x4s2")
+    torch.cuda.synchronize()
+    _untouched(dx[Fr * H * W * Cin:], "past dx")
+    x = torch.zeros(Fr, Cin, H, W, dtype=torch.float64, device=dev, requires_grad=True)
+    u = _unfold_rows(x)
+    d64 = dcol.double().view(Fr, Ho * Wo, 16, Cin)
+    (gx,) = torch.autograd.grad((u * d64).sum(), x, retain_graph=True)
+    (ga,) = torch.autograd.grad((u * d64.abs()).sum(), x)
+    w = _within(dx[:Fr * H * W * Cin].view(Fr, H, W, Cin), gx.permute(0, 2, 3, 1), 4 * EPS * ga.permute(0, 2, 3, 1), "dx")
+    print(f"col2im4x4s2 {H}x{W} Cin={Cin} F={Fr}: worst err / tol {w:.3f}")
+
+
+@pytest.mark.parametrize("H,W", [(8, 8), (64, 64), (16, 8)])
+def test_im2col_image_exact(env, H, W):
+    """gcpx_im2col_image (backward_stages.py:345): col [F Ho Wo][48], k = (ci, ky, kx), equals F.unfold(x, 4, padding=1, stride=2) of the
+    NCHW image exactly; the image has no zero, so the padding taps are the only (exact) zeros."""
+    rt, pk, lib, dev = env
+    Fr = 3
+    g = torch.Generator(device=dev).manual_seed(H + W)
+    x = torch.rand(Fr, 3, H, W, device=dev, generator=g) + 0.5
+    n = Fr * (H // 2) * (W // 2) * 48
+    col = _nan(n + 8)
+    rt.check(lib.gcpx_im2col_image(x.data_ptr(), col.data_ptr(), Fr, H, W, _st()), "im2col_image")
+    torch.cuda.synchronize()
+    want = F.unfold(x, 4, padding=1, stride=2).permute(0, 2, 1).reshape(-1)
+    assert torch.equal(col[:n], want)
+    assert int((col[:n] == 0).sum()) == int((want == 0).sum()) > 0
+    _untouched(col[n:], "past col")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# l. column sums and partial reductions
+# ------------------------------------------------------------------------------------------------------------------------------
+def _colsum_terms(R, N, nsplit):
+    """additions on the longest path of gcpx_colsum (+ gcpx_reduce_partials): a thread sums ceil(rows of its chunk / rpi) values (the
+    4-way unrolled tree is shallower than serial; + 2 for its shape), the rpi row classes are combined serially, then the 16-way strided
+    reduction over the chunks; never more than R - 1 (adding an exact 0 does not round)"""
+    c4 = (N + 3) // 4
+    tl = 0
+    while (1 << tl) < c4 and tl < 8:
+        tl += 1
+    rpi = 256 >> tl
+    rows_per = -(-R // nsplit)
+    depth = -(-rows_per // rpi) + 2 + rpi + (0 if nsplit == 1 else -(-nsplit // 16) + 16)
+    return min(R, depth)
+
+
+@pytest.mark.parametrize("N,layout", [(N, "dense") for N in (1, 3, 16, 100, 112, 512, 2048)] + [(N, "batched") for N in (3, 16, 100, 512)])
+def test_colsum_vs_float64(env, N, layout):
+    """gcpx_colsum (+ gcpx_reduce_partials over its partials) as backward_ops.py:208-224 issues them, against float64 column sums.
+    N = 1, 3 (a partial float4, ldy 16), 100 (32 threads per row, 7 of them idle), 2048 (two column workgroups); R = 1, 5, 255, 1000, 4099
+    (fewer rows than row classes; a remainder after the 4-way unrolled loop); nsplit = 1 (direct, accumulate 0 and 1, with and without
+    dst2), 7, 64 (nsplit > R: the empty chunks write 0 partials, every partial finite); "batched": rows (b, j) of a tree level in the
+    position layout (dy_rpb 8, dy_sb, ldy = two slots: the `out` bias of backward_plan.py:195), R not a multiple of dy_rpb included.
+    Every column >= N of dy and every unaddressed row is NaN; dst's columns beyond N keep their NaN.
+    Tolerance: (terms + 1) eps x abs-terms with terms = the additions on the kernel's longest path, from the launch geometry
+    (_colsum_terms; <= R - 1), + 1 for the accumulation.  Chosen over the plain R eps: at R = 4099, N = 2048 the path is 4099 + 3 long
+    either way, but at N = 16 it is 4099 / 64 + 66 — the plain bound would be 30x looser there."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(N)
+    pitch = 16 if N < 16 else (N + 3) // 4 * 4 + 8
+    worst = 0.0
+    for R in (1, 5, 255, 1000, 4099):
+        vals = torch.randn(R, N, device=dev, generator=g) + 0.25
+        if layout == "dense":
+            dy = _nan(R, pitch)
+            dy[:, :N] = vals
+            ptr, ldy, rpb, sb = dy.data_ptr(), pitch, 0, 0
+        else:
+            rpb = 8
+            Bn, PS = (R + rpb - 1) // rpb, 2 * rpb + 2
+            dy = _nan(Bn, PS, pitch)
+            r = torch.arange(R, device=dev)
+            dy[r // rpb, 1 + 2 * (r % rpb), :N] = vals
+            ptr, ldy, sb = dy.data_ptr() + 4 * pitch, 2 * pitch, PS * pitch
+        ref, ab = vals.double().sum(0), vals.double().abs().sum(0)
+        for nsplit in (1, 7, 64):
+            for acc in (0, 1):
+                pre = torch.randn(2, N, device=dev, generator=g)
+                dst = _nan(2, N + 8)
+                if acc:
+                    dst[:, :N] = pre
+                use2 = bool(acc) or nsplit > 1
+                if nsplit == 1:
+                    rt.check(lib.gcpx_colsum(ptr, ldy, R, N, rpb, sb, 1, None, dst[0].data_ptr(), dst[1].data_ptr() if use2 else None, acc,
+                                             _st()), "colsum")
+                else:
+                    part = _nan(nsplit, N)
+                    rt.check(lib.gcpx_colsum(ptr, ldy, R, N, rpb, sb, nsplit, part.data_ptr(), None, None, 0, _st()), "colsum")
+                    rt.check(lib.gcpx_reduce_partials(part.data_ptr(), nsplit, N, N, dst[0].data_ptr(), acc, _st()), "reduce_partials")
+                    rt.check(lib.gcpx_reduce_partials(part.data_ptr(), nsplit, N, N, dst[1].data_ptr(), acc, _st()), "reduce_partials")
+                    torch.cuda.synchronize()
+                    assert bool(torch.isfinite(part).all()), "every partial is written"
+                    if nsplit > R:
+                        assert bool((part[R:] == 0).all()), "empty chunks write 0"
+                torch.cuda.synchronize()
+                k = _colsum_terms(R, N, nsplit) + 1
+                base = pre.double() if acc else torch.zeros(2, N, dtype=torch.float64, device=dev)
+                for d in range(2 if use2 else 1):
+                    worst = max(worst, _within(dst[d, :N], base[d] + ref, _gamma(k) * (base[d].abs() + ab),
+                                               f"colsum R={R} nsplit={nsplit} acc={acc} dst{d}"))
+                _untouched(dst[:, N:], "columns beyond N")
+                if not use2:
+                    _untouched(dst[1], "dst2 not given")
+    print(f"colsum N={N} {layout}: worst err / tol {worst:.3f}")
+
+
+def _wreduce_case(pk, case, dev):
+    """(N, K, map_mode, Cin, ntap, Cout, n_map or None, ldw, k_off, dst shape, scatter(S [N][K] float64 -> (index tuple, values)))"""
+    if case == "linear":
+        N, K, ldw, k_off = 7, 9, 20, 3
+        return N, K, 0, 0, 0, 0, None, ldw, k_off, (N, ldw), lambda S: ((slice(None), slice(k_off, k_off + K)), S)
+    if case == "conv":
+        Cout, Cin, ntap = 6, 5, 9                                     # Cin != ntap: an exchanged (tap, ci) lands elsewhere
+        return Cout, ntap * Cin, 1, Cin, ntap, 0, None, 0, 0, (Cout, Cin, ntap), lambda S: ((slice(None),), S.view(Cout, ntap, Cin).permute(0, 2, 1))
+    if case in ("conv_nmap", "bias_nmap"):
+        perm = torch.tensor(pk.dlm_channel_perm(10), dtype=torch.int32, device=dev)      # 112 kernel slots -> 100 channels, -1 = empty slot
+        Cin, ntap = (4, 9) if case == "conv_nmap" else (1, 1)
+        sl = torch.nonzero(perm >= 0)[:, 0]
+        ch = perm[sl].long()
+        return (len(perm), ntap * Cin, 1, Cin, ntap, 0, perm, 0, 0, (104, Cin, ntap),
+                lambda S: ((ch,), S.view(len(perm), ntap, Cin).permute(0, 2, 1)[sl]))
+    if case == "bias":
+        N = 37
+        return N, 1, 1, 1, 1, 0, None, 0, 0, (N, 1, 1), lambda S: ((slice(None),), S.view(N, 1, 1))
+    Cout, Cin, ntap = 3, 5, 16                                        # convt: n = (tap, co), k = ci -> w[ci][co][tap]
+    return ntap * Cout, Cin, 2, Cin, ntap, Cout, None, 0, 0, (Cin, Cout, ntap), lambda S: ((slice(None),), S.view(ntap, Cout, Cin).permute(2, 1, 0))
+
+
+@pytest.mark.parametrize("nsplit", [1, 15, 16, 17, 1024])
+@pytest.mark.parametrize("case", ["linear", "conv", "conv_nmap", "bias_nmap", "bias", "convt"])
+def test_wgrad_reduce_vs_float64(env, case, nsplit):
+    """gcpx_wgrad_reduce (backward_ops.py:170, :201-206, :227): partial [nsplit][N][K] summed over the splits and scattered into the
+    canonical parameter layout, against a float64 sum scattered by the documented maps written with torch indexing: LINEAR dst[n][k_off +
+    k] with ldw > K (the other columns keep the NaN); CONV k = (tap, ci) -> w[n_map[n]][ci][tap] (Cin 5 != 9 taps) without a map, with
+    the head's 112 slots -> 100 channels map (12 slots are -1: skipped; the rows of dst behind channel 99 keep the NaN) and the K = 1 bias
+    forms; CONVT n = (tap, co), k = ci -> w[ci][co][tap].  N K = 63, 270, 37 (not multiples of 16: the masked last workgroup), 112, 240, 4032.
+    accumulate 0 and 1.
+    Tolerance (nsplit / 16 + 16) eps x abs-terms: each of the 16 thread groups adds nsplit / 16 values, 16 partial sums, the
+    accumulation; never more than nsplit additions."""
+    rt, pk, lib, dev = env
+    N, K, mode, Cin, ntap, Cout, n_map, ldw, k_off, dshape, scatter = _wreduce_case(pk, case, dev)
+    g = torch.Generator(device=dev).manual_seed(nsplit + N * K)
+    part = torch.randn(nsplit, N, K, device=dev, generator=g)
+    S, Sa = part.double().sum(0), part.double().abs().sum(0)
+    idx, val = scatter(S)
+    _, vab = scatter(Sa)
+    worst = 0.0
+    for acc in (0, 1):
+        dst = _nan(*dshape)
+        pre = torch.randn(*dshape, device=dev, generator=g)
+        written = torch.zeros(dshape, dtype=torch.bool, device=dev)
+        written[idx] = True
+        if acc:
+            dst[written] = pre[written]
+        rt.check(lib.gcpx_wgrad_reduce(part.data_ptr(), nsplit, N, K, dst.data_ptr(), mode, Cin, ntap, Cout, rt.ptr(n_map), ldw, k_off, acc,
+                                       _st()), "wgrad_reduce")
+        torch.cuda.synchronize()
+        want = torch.zeros(dshape, dtype=torch.float64, device=dev)
+        wab = torch.zeros_like(want)
+        want[idx], wab[idx] = val, vab
+        if acc:
+            want, wab = want + pre.double(), wab + pre.double().abs()
+        k = min(nsplit, nsplit / 16 + 16)
+        worst = max(worst, _within(dst[written], want[written], k * EPS * wab[written], f"{case} nsplit={nsplit} acc={acc}"))
+        _untouched(dst[~written], "elements outside the map")
+    print(f"wgrad_reduce {case} nsplit={nsplit}: worst err / tol {worst:.3f}")
+
+
+@pytest.mark.parametrize("n", [1, 16, 17, 1000])
+@pytest.mark.parametrize("ln", [1, 16, 33])
+def test_reduce_partials_vs_float64(env, n, ln):
+    """gcpx_reduce_partials with stride > len and a pointer offset into the partial rows (backward_ops.py:357: the d beta half of the
+    GroupNorm partials), accumulate 0 and 1; everything outside the addressed columns is NaN, dst behind len keeps its NaN.
+    Tolerance (n / 16 + 16) eps x abs-terms, as gcpx_wgrad_reduce (the same reduction), never more than n additions."""
+    rt, pk, lib, dev = env
+    g = torch.Generator(device=dev).manual_seed(n * 100 + ln)
+    stride, off = 2 * ln + 5, ln + 2
+    part = _nan(n, stride)
+    vals = torch.randn(n, ln, device=dev, generator=g) + 0.25
+    part[:, off:off + ln] = vals
+    worst = 0.0
+    for acc in (0, 1):
+        pre = torch.randn(ln, device=dev, generator=g)
+        dst = _nan(ln + 8)
+        if acc:
+            dst[:ln] = pre
+        rt.check(lib.gcpx_reduce_partials(part.data_ptr() + 4 * off, n, stride, ln, dst.data_ptr(), acc, _st()), "reduce_partials")
+        torch.cuda.synchronize()
+        base = pre.double() if acc else torch.zeros(ln, dtype=torch.float64, device=dev)
+        k = min(n, n / 16 + 16)
+        worst = max(worst, _within(dst[:ln], base + vals.double().sum(0), k * EPS * (base.abs() + vals.double().abs().sum(0)), f"acc={acc}"))
+        _untouched(dst[ln:], "behind len")
+    print(f"reduce_partials n={n} len={ln}: worst err / tol {worst:.3f}")

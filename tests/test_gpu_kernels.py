@@ -143,6 +143,16 @@ def test_gemm_sources_shift_affine_stats(env):
     assert_close(shift, beta - mean * wsc, atol=1e-5, rtol=1e-4, name="bn shift")
 
 
+def _lstm_gates_ref(cell, x, h):
+    """the activated gates of torch.nn.LSTMCell in float64, in the [M][H][4] (i, f, g, o) layout gcpx_gemm_args.gates_out documents and
+    lstm_bwd_cell (csrc/common.h) reads"""
+    with torch.no_grad():
+        pre = (F.linear(x.double(), cell.weight_ih.double(), cell.bias_ih.double()) +
+               F.linear(h.double(), cell.weight_hh.double(), cell.bias_hh.double()))
+        i, f, g, o = pre.chunk(4, 1)                                    # torch's gate-major order
+        return torch.stack([torch.sigmoid(i), torch.sigmoid(f), torch.tanh(g), torch.sigmoid(o)], -1)
+
+
 def test_gemm_lstm_epilogue(env):
     rt, pk, lib, dev = env
     torch.manual_seed(5)
@@ -155,17 +165,22 @@ def test_gemm_lstm_epilogue(env):
     wp, bd = pk.pack_gemm(w).to(dev), b.to(dev)
     xd, hd, cd = x.to(dev), h.to(dev), c.to(dev)
     ho, co, hc = (torch.zeros(M, H, device=dev) for _ in range(3))
+    go = torch.full((M, H, 4), float("nan"), device=dev)
     a = rt.GemmArgs()
     a.src[0] = _rowsrc(rt, xd, 0, H, H)
     a.src[1] = _rowsrc(rt, hd, 0, H, H)
     a.nsrc, a.M, a.N, a.K, a.rpb = 2, M, 4 * H, 2 * H, M
     a.wpk, a.bias, a.epi = wp.data_ptr(), bd.data_ptr(), rt.EPI_LSTM
     a.c_prev, a.c_prev_stride, a.h_out, a.c_out, a.hb, a.hrow, a.h_copy = cd.data_ptr(), H, ho.data_ptr(), co.data_ptr(), 0, H, hc.data_ptr()
+    a.gates_out = go.data_ptr()
     rt.check(lib.gcpx_gemm(C.byref(a), _stream()), "gemm lstm")
     torch.cuda.synchronize()
     assert_close(ho, h1, atol=1e-5, name="h")
     assert_close(co, c1, atol=1e-5, name="c")
     assert_close(hc, h1, atol=1e-5, name="h_copy")
+    # the gates kept for the backward pass: [M][H][4] = (i, f, g, o) activated, the order lstm_bwd_cell reads
+    assert bool(torch.isfinite(go).all())
+    assert_close(go, _lstm_gates_ref(cell, x, h), atol=1e-5, name="gates_out (exact f32 form)")
 
 
 @pytest.mark.parametrize("case", ["unit", "tiny", "row_scales", "k_growth", "outlier", "zero_rows"])
@@ -233,6 +248,7 @@ def test_gemm_split_lstm_sources_and_batches(env):
     ws = ws.to(dev)
     pd, rd, hd, cd = pool.to(dev), ridx.to(dev), h.to(dev), c.to(dev)
     ho, co, hc = (torch.full((M, H), float("nan"), device=dev) for _ in range(3))
+    go = torch.full((M, H, 4), float("nan"), device=dev)
     a = rt.GemmArgs()
     a.src[0] = _rowsrc(rt, pd, 0, H, H, rowidx=rd)
     a.src[1] = _rowsrc(rt, hd, 0, H, H)
@@ -240,11 +256,15 @@ def test_gemm_split_lstm_sources_and_batches(env):
     a.wpk, a.bias, a.epi = wp.data_ptr(), bd.data_ptr(), rt.EPI_LSTM
     a.wpk_split, a.w_split_log2 = ws.data_ptr(), e
     a.c_prev, a.c_prev_stride, a.h_out, a.c_out, a.hb, a.hrow, a.h_copy = cd.data_ptr(), H, ho.data_ptr(), co.data_ptr(), 0, H, hc.data_ptr()
+    a.gates_out = go.data_ptr()
     rt.check(lib.gcpx_gemm(C.byref(a), _stream()), "gemm split lstm")
     torch.cuda.synchronize()
     assert_close(ho, h1, atol=1e-5, name="h")
     assert_close(co, c1, atol=1e-5, name="c")
     assert_close(hc, h1, atol=1e-5, name="h_copy")
+    # the gates kept for the backward pass, as the split-f16 form saves them: [M][H][4] = (i, f, g, o) activated
+    assert bool(torch.isfinite(go).all())
+    assert_close(go, _lstm_gates_ref(cell, x, h), atol=1e-5, name="gates_out (split-f16 form)")
     # the same cell over thousands of rows: the 128-row / 512-thread workgroups (gathered source, LSTM epilogue, masked last block)
     Mb = 16500
     ridx_b = torch.randint(0, 500, (Mb,), dtype=torch.int32)
@@ -430,6 +450,147 @@ def test_mlp_group_with_gemm(env, Mg, Ng, nb):
     want = torch.einsum("bmk,bnk->bmn", xg.cpu().double(), wg.double()) + bg.cpu().double()[:, None]
     assert_close(gouts[1], want.float(), atol=3e-5, rtol=2e-5, name="merge GEMM")
     assert torch.equal(gouts[0], gouts[1]) and torch.equal(pouts[0], pouts[1]) and torch.equal(qouts[0], qouts[1]) and torch.equal(qz[0], qz[1])
+
+
+def test_gemm_group_equals_single_launches(env):
+    """gcpx_gemm_group (gemm_group_kernel) on a table of the problems the planner groups (plan_ops.py:201-216, sequential.py:284-303): a
+    plain GEMM over two concatenated sources (M 37: a masked last row tile), an LSTM-cell problem (M 16, gates_out and h_copy set), an
+    LReLU problem with ONE row, a batched plain problem (nbatch 3) and a GCPX_EPI_GAUSS_SAMPLE problem (the reparametrised draw that rides
+    in the launch; rows (b, j) strided on all three operands, NaN between them) — different M, N, K >= 256.  gcpx_gemm_group_dims accepts
+    the table; the grouped launch writes BIT FOR BIT what one gcpx_gemm per problem (gcpx_gauss_sample for the draw) writes, NaN gaps
+    included; the plain problem is within test_gemm_plain's tolerance of float64 and the draw equals mu + exp(log_sigma) eps in float64
+    to 4 eps of its abs-terms |mu| + exp(log_sigma) |eps| (expf within 2 ulp).  gcpx_gemm_group_dims answers GCPX_ERR_UNSUPPORTED to a
+    problem outside the small-M regime (M = 1024) and to one with stats_partial set."""
+    rt, pk, lib, dev = env
+    torch.manual_seed(77)
+    nan = float("nan")
+    keep = []
+
+    def dev_(t):
+        t = t.to(dev)
+        keep.append(t)
+        return t
+
+    # plain: two sources
+    M0, N0, K0 = 37, 256, 512
+    x0a, x0b, w0, b0 = torch.randn(M0, 256), torch.randn(M0, 256), torch.randn(N0, K0) / K0 ** 0.5, torch.randn(N0)
+    x0ad, x0bd, wp0, b0d = dev_(x0a), dev_(x0b), dev_(pk.pack_gemm(w0)), dev_(b0)
+    # LSTM cell
+    M1, H = 16, 128
+    x1, h1_, c1_ = torch.randn(M1, H), torch.randn(M1, H), torch.randn(M1, H)
+    cell = torch.nn.LSTMCell(H, H)
+    with torch.no_grad():
+        hw, cw = cell(x1, (h1_, c1_))
+    w1, b1 = pk.lstm_gate_interleave(cell.weight_ih.detach(), cell.weight_hh.detach(), cell.bias_ih.detach(), cell.bias_hh.detach())
+    x1d, h1d, c1d, wp1, b1d = dev_(x1), dev_(h1_), dev_(c1_), dev_(pk.pack_gemm(w1)), dev_(b1)
+    # LReLU, one row
+    N2, K2 = 128, 256
+    x2, w2, b2 = torch.randn(1, K2), torch.randn(N2, K2) / K2 ** 0.5, torch.randn(N2)
+    x2d, wp2, b2d = dev_(x2), dev_(pk.pack_gemm(w2)), dev_(b2)
+    # batched plain
+    nb, M3, N3, K3 = 3, 16, 64, 256
+    x3, w3, b3 = torch.randn(nb, M3, K3), torch.randn(nb, N3, K3) / K3 ** 0.5, torch.randn(nb, N3)
+    x3d, wp3, b3d = dev_(x3), dev_(torch.stack([pk.pack_gemm(w3[i]) for i in range(nb)]).contiguous()), dev_(b3)
+    # reparametrised draw: rows (b, j), B 4 x rpb 3, nz 32; [mu | log_sigma] rows every second 64-float row, eps rows of pitch 40, out of pitch 48
+    Bs, rs, nz = 4, 3, 32
+    muls = torch.full((Bs, 2 * rs + 1, 2 * nz), nan)
+    mu, ls = torch.randn(Bs, rs, nz), torch.randn(Bs, rs, nz) * 0.7 - 0.5
+    muls[:, 1:2 * rs:2, :nz], muls[:, 1:2 * rs:2, nz:] = mu, ls
+    eps = torch.full((Bs, rs, 40), nan)
+    eps[..., :nz] = torch.randn(Bs, rs, nz)
+    mulsd, epsd = dev_(muls), dev_(eps)
+
+    def table():
+        """the five descriptors with output buffers of their own (NaN-prefilled)"""
+        o = dict(out0=torch.full((M0, N0), nan, device=dev), h=torch.full((M1, H), nan, device=dev), c=torch.full((M1, H), nan, device=dev),
+                 hc=torch.full((M1, H), nan, device=dev), gates=torch.full((M1, H, 4), nan, device=dev),
+                 out2=torch.full((1, N2), nan, device=dev), out3=torch.full((nb, M3, N3), nan, device=dev),
+                 z=torch.full((Bs, rs + 1, 48), nan, device=dev))
+        a0 = rt.GemmArgs()
+        a0.src[0], a0.src[1] = _rowsrc(rt, x0ad, 0, 256, 256), _rowsrc(rt, x0bd, 0, 256, 256)
+        a0.nsrc, a0.M, a0.N, a0.K, a0.rpb = 2, M0, N0, K0, M0
+        a0.wpk, a0.bias, a0.out, a0.ob, a0.orow = wp0.data_ptr(), b0d.data_ptr(), o["out0"].data_ptr(), 0, N0
+        a1 = rt.GemmArgs()
+        a1.src[0], a1.src[1] = _rowsrc(rt, x1d, 0, H, H), _rowsrc(rt, h1d, 0, H, H)
+        a1.nsrc, a1.M, a1.N, a1.K, a1.rpb = 2, M1, 4 * H, 2 * H, M1
+        a1.wpk, a1.bias, a1.epi = wp1.data_ptr(), b1d.data_ptr(), rt.EPI_LSTM
+        a1.c_prev, a1.c_prev_stride, a1.h_out, a1.c_out, a1.hb, a1.hrow = c1d.data_ptr(), H, o["h"].data_ptr(), o["c"].data_ptr(), 0, H
+        a1.h_copy, a1.gates_out = o["hc"].data_ptr(), o["gates"].data_ptr()
+        a2 = rt.GemmArgs()
+        a2.src[0] = _rowsrc(rt, x2d, 0, K2, K2)
+        a2.nsrc, a2.M, a2.N, a2.K, a2.rpb = 1, 1, N2, K2, 1
+        a2.wpk, a2.bias, a2.out, a2.ob, a2.orow, a2.epi = wp2.data_ptr(), b2d.data_ptr(), o["out2"].data_ptr(), 0, N2, rt.EPI_LRELU
+        a3 = rt.GemmArgs()
+        a3.src[0] = _rowsrc(rt, x3d, 0, K3, K3)
+        a3.nsrc, a3.M, a3.N, a3.K, a3.rpb = 1, M3, N3, K3, M3
+        a3.wpk, a3.bias, a3.out, a3.ob, a3.orow = wp3.data_ptr(), b3d.data_ptr(), o["out3"].data_ptr(), 0, N3
+        a3.nbatch, a3.z_src_off, a3.z_w_off, a3.z_bias_off, a3.z_out_off = nb, M3 * K3, N3 * K3, N3, M3 * N3
+        a4 = rt.GemmArgs()                                            # sequential.py:296-303: src[0] = [mu | log_sigma] rows, src[1] = eps rows
+        a4.src[0] = _rowsrc(rt, mulsd.data_ptr() + 4 * 2 * nz, (2 * rs + 1) * 2 * nz, 2 * 2 * nz, 2 * nz)
+        a4.src[1] = _rowsrc(rt, epsd, rs * 40, 40, nz)
+        a4.nsrc, a4.M, a4.N, a4.K, a4.rpb, a4.epi = 2, Bs * rs, nz, 3 * nz, rs, rt.EPI_GAUSS_SAMPLE
+        a4.out, a4.ob, a4.orow = o["z"].data_ptr() + 4 * 8, (rs + 1) * 48, 48
+        return [a0, a1, a2, a3, a4], o
+
+    single, so = table()
+    for a in single[:4]:
+        rt.check(lib.gcpx_gemm(C.byref(a), _stream()), "gemm")
+    a = single[4]
+    rt.check(lib.gcpx_gauss_sample(a.src[0].ptr, a.src[0].sb, a.src[0].sr, a.src[1].ptr, a.src[1].sb, a.src[1].sr, a.out, a.ob, a.orow,
+                                   a.M, a.rpb, a.N, _stream()), "gauss_sample")
+    grouped, go = table()
+    n = len(grouped)
+    tab = (rt.GemmArgs * n)(*grouped)
+    dims = (C.c_int32 * (4 * n))()
+    total = C.c_int32()
+    rt.check(lib.gcpx_gemm_group_dims(tab, n, dims, C.byref(total)), "gemm_group_dims")
+    assert total.value == 3 * 16 + 1 * 32 + 1 * 8 + 1 * 4 * nb + 1 * 2, total.value          # 16 x 16 tiles (row blocks x column tiles x batches)
+    raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    dd = torch.tensor(list(dims), dtype=torch.int32, device=dev)
+    rt.check(lib.gcpx_gemm_group(raw.data_ptr(), dd.data_ptr(), n, total.value, _stream()), "gemm_group")
+    torch.cuda.synchronize()
+    for k in so:
+        assert torch.equal(so[k].view(torch.int32), go[k].view(torch.int32)), f"{k}: the grouped launch differs from the single launch"
+    # ... and the values themselves
+    for k in ("out0", "h", "c", "hc", "gates", "out2", "out3"):
+        assert bool(torch.isfinite(go[k]).all()), k
+    want0 = F.linear(torch.cat([x0a, x0b], 1).double(), w0.double(), b0.double())
+    assert_close(go["out0"], want0.float(), atol=2e-5, rtol=1e-5, name="plain problem")
+    assert_close(go["h"], hw, atol=1e-5, name="h")
+    assert_close(go["c"], cw, atol=1e-5, name="c")
+    assert_close(go["hc"], hw, atol=1e-5, name="h_copy")
+    assert_close(go["gates"], _lstm_gates_ref(cell, x1, h1_), atol=1e-5, name="gates_out")
+    assert_close(go["out2"], F.leaky_relu(F.linear(x2.double(), w2.double(), b2.double()), 0.2).float(), atol=2e-5, rtol=1e-5, name="LReLU row")
+    assert_close(go["out3"], (torch.einsum("bmk,bnk->bmn", x3.double(), w3.double()) + b3.double()[:, None]).float(), atol=2e-5, rtol=1e-5,
+                 name="batched problem")
+    z = go["z"].cpu()
+    zr = z[:, :rs, 8:8 + nz].double()
+    assert bool(torch.isfinite(zr).all())
+    zw = mu.double() + torch.exp(ls.double()) * eps[..., :nz].double()
+    zab = mu.double().abs() + torch.exp(ls.double()) * eps[..., :nz].double().abs()
+    err = (zr - zw).abs()
+    print(f"gemm_group gauss sample: worst err / tol {float((err / (4 * 2.0 ** -24 * zab)).max()):.3f}")
+    assert bool((err <= 4 * 2.0 ** -24 * zab).all()), float((err / zab).max())
+    gap = torch.ones_like(z, dtype=torch.bool)
+    gap[:, :rs, 8:8 + nz] = False
+    assert bool(torch.isnan(z[gap]).all()), "the draw wrote outside its rows"
+    # outside the regime: refused, nothing to launch
+    big = rt.GemmArgs()
+    xb, wb = torch.zeros(1024, 256, device=dev), dev_(pk.pack_gemm(torch.zeros(512, 256)))
+    ob = torch.zeros(1024, 512, device=dev)
+    big.src[0] = _rowsrc(rt, xb, 0, 256, 256)
+    big.nsrc, big.M, big.N, big.K, big.rpb = 1, 1024, 512, 256, 1024
+    big.wpk, big.out, big.ob, big.orow = wb.data_ptr(), ob.data_ptr(), 0, 512
+    ERR_UNSUPPORTED = -2                                              # GCPX_ERR_UNSUPPORTED (include/gcpx.h)
+    for bad in (big, None):
+        probs, _ = table()
+        if bad is None:                                               # training-mode BatchNorm statistics: not a grouped problem
+            st = torch.zeros(lib.gcpx_gemm_row_blocks(M0, N0), 2, N0, device=dev)
+            probs[0].stats_partial = st.data_ptr()
+        else:
+            probs[2] = bad
+        tab2 = (rt.GemmArgs * n)(*probs)
+        assert lib.gcpx_gemm_group_dims(tab2, n, dims, C.byref(total)) == ERR_UNSUPPORTED
 
 
 def test_loss_pre_and_final_equal_the_single_combine(env):
@@ -1338,6 +1499,79 @@ def test_mlp_bwd_fused(env, mid, in_dims, out_dim, M, rpb):
         assert_close(parts[l][:, 0].sum(0), grads[len(in_dims)][l], atol=5e-4, rtol=1e-4, name=f"dgamma{l}")
         assert_close(parts[l][:, 1].sum(0), grads[len(in_dims) + 1][l], atol=5e-4, rtol=1e-4, name=f"dbeta{l}")
     assert not any(torch.isnan(t).any() for t in du)
+
+
+def test_mlp_bwd_group_equals_single_launches(env):
+    """gcpx_mlp_bwd_group (backward_ops.py:287-295: a tree level's posterior and prior Predictors, one hidden width, in ONE launch,
+    blockIdx.y = the Predictor) writes bit for bit what one gcpx_mlp_bwd per Predictor writes — every du_l, the GroupNorm partial sums and
+    the strided dx rows with their NaN gaps — for three Predictors of different M (37, 16, 5: the grid is sized by the largest, the
+    others' surplus row blocks must do nothing), input splits and output widths.  The values themselves are test_mlp_bwd_fused's."""
+    rt, pk, lib, dev = env
+    torch.manual_seed(21)
+    mid, n_mid = 128, 3
+    keep, probs = [], []
+    for in_dims, out_dim, M, rpb in (((256, 128), 512, 37, 37), ((128, 128, 128), 80, 16, 8), ((128,), 1, 5, 5)):
+        K, out_pad = sum(in_dims), (out_dim + 15) // 16 * 16
+        w_in, w_mid, w_out = torch.randn(mid, K) / K ** 0.5, torch.randn(n_mid, mid, mid) / mid ** 0.5, torch.randn(out_dim, mid) / mid ** 0.5
+        d = {k: v.to(dev) for k, v in dict(
+            w_in=pk.pack_gemm(w_in), b_in=torch.randn(mid) * 0.1, w_mid=torch.stack([pk.pack_gemm(w_mid[i]) for i in range(n_mid)]),
+            b_mid=torch.randn(n_mid, mid) * 0.1, g=torch.rand(n_mid, mid) + 0.5, be=torch.randn(n_mid, mid) * 0.1,
+            w_out=pk.pack_gemm(w_out), b_out=pk.pad_vec(torch.randn(out_dim) * 0.1, out_pad)).items()}
+        xd = [torch.randn(M, w, device=dev) for w in in_dims]
+        out, save = torch.zeros(M, out_dim, device=dev), torch.zeros(1 + 2 * n_mid, M, mid, device=dev)
+        a = rt.MlpArgs()
+        for i, x in enumerate(xd):
+            a.src[i] = _rowsrc(rt, x, 0, in_dims[i], in_dims[i])
+        a.nsrc, a.M, a.rpb, a.in_dim, a.mid, a.n_mid, a.out_dim = len(xd), M, M, K, mid, n_mid, out_dim
+        a.w_in, a.b_in, a.w_mid, a.b_mid = d["w_in"].data_ptr(), d["b_in"].data_ptr(), d["w_mid"].data_ptr(), d["b_mid"].data_ptr()
+        a.gn_gamma, a.gn_beta, a.w_out, a.b_out = d["g"].data_ptr(), d["be"].data_ptr(), d["w_out"].data_ptr(), d["b_out"].data_ptr()
+        a.gn_eps, a.lrelu_slope = 1e-5, 0.2
+        a.out, a.ob, a.orow, a.save = out.data_ptr(), 0, out_dim, save.data_ptr()
+        rt.check(lib.gcpx_mlp(C.byref(a), _stream()), "mlp")
+        wT_out = pk.pack_gemm(torch.cat([w_out, torch.zeros(out_pad - out_dim, mid)], 0).t().contiguous()).to(dev)
+        wT_mid = [pk.pack_gemm(w_mid[l].t().contiguous()).to(dev) for l in range(n_mid)]
+        wT_in, c0 = [], 0
+        for w in in_dims:
+            wT_in.append(pk.pack_gemm(w_in[:, c0:c0 + w].t().contiguous()).to(dev))
+            c0 += w
+        dout = torch.zeros(M, out_pad, device=dev)
+        dout[:, :out_dim] = torch.randn(M, out_dim, device=dev)
+        keep.extend([d, xd, out, save, wT_out, wT_mid, wT_in, dout])
+        probs.append((in_dims, out_pad, M, rpb, d, save, wT_out, wT_mid, wT_in, dout))
+
+    def descriptors():
+        args, outs = [], []
+        for in_dims, out_pad, M, rpb, d, save, wT_out, wT_mid, wT_in, dout in probs:
+            nb = lib.gcpx_mlp_bwd_blocks(M)
+            du = [torch.full((M, mid), float("nan"), device=dev) for _ in range(n_mid + 1)]
+            parts = [torch.full((nb, 2, mid), float("nan"), device=dev) for _ in range(n_mid)]
+            dxs = [torch.full((M // rpb, rpb + 3, w + 16), float("nan"), device=dev) for w in in_dims]
+            b = rt.MlpBwdArgs()
+            b.dout, b.save, b.wT_out, b.ldo = dout.data_ptr(), save.data_ptr(), wT_out.data_ptr(), out_pad
+            b.M, b.rpb, b.mid, b.n_mid, b.out_pad, b.ndx = M, rpb, mid, n_mid, out_pad, len(in_dims)
+            b.gn_eps, b.lrelu_slope = 1e-5, 0.2
+            b.du[0] = du[0].data_ptr()
+            for l in range(n_mid):
+                b.wT_mid[l], b.gn_gamma[l], b.gn_beta[l] = wT_mid[l].data_ptr(), d["g"][l].data_ptr(), d["be"][l].data_ptr()
+                b.du[1 + l], b.gn_partial[l] = du[1 + l].data_ptr(), parts[l].data_ptr()
+            for i, w in enumerate(in_dims):
+                b.dx[i].wT, b.dx[i].out, b.dx[i].ob, b.dx[i].orow, b.dx[i].width = wT_in[i].data_ptr(), dxs[i].data_ptr(), (rpb + 3) * (w + 16), w + 16, w
+            args.append(b)
+            outs.append(du + parts + dxs)
+        return args, outs
+
+    single, so = descriptors()
+    for b in single:
+        rt.check(lib.gcpx_mlp_bwd(C.byref(b), _stream()), "mlp_bwd")
+    grouped, go = descriptors()
+    tab = (rt.MlpBwdArgs * len(grouped))(*grouped)
+    rt.check(lib.gcpx_mlp_bwd_group(tab, len(grouped), _stream()), "mlp_bwd_group")
+    torch.cuda.synchronize()
+    for p, (s_, g_) in enumerate(zip(so, go)):
+        for i, (x0, x1) in enumerate(zip(s_, g_)):
+            assert torch.equal(x0.view(torch.int32), x1.view(torch.int32)), f"Predictor {p}, output {i}: the grouped launch differs"
+        assert all(bool(torch.isfinite(t).all()) for t in g_[:2 * n_mid + 1]), f"Predictor {p}: du / partial sums not written"
+        assert all(bool(torch.isfinite(t[:, :probs[p][3], :w]).all()) for t, w in zip(g_[2 * n_mid + 1:], probs[p][0])), "dx rows"
 
 
 def test_wgrad_group_matches_single_launches(env):

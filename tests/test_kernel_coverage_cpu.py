@@ -1,0 +1,99 @@
+"""A ledger of which C-ABI entry points of include/gcpx.h the GPU suite calls directly (no GPU, no library load: the test reads files).
+
+Every `int gcpx_*(` declaration must be either
+  (a) called in some tests/test_gpu_*.py — `.gcpx_name(` on the library handle, or passed as `lib.gcpx_name`; or
+  (b) listed below with a reason: INFRASTRUCTURE (no arithmetic of its own to compare with a reference), or INDIRECT (its only cover
+      today is the model-level test named beside it, which compares whole-model outputs or parameter gradients at 1e-3 of a tensor's
+      max-abs — the visible to-do list of kernel-level tests).
+The test also fails when a test named in INDIRECT does not exist, and when a listed name has gained a direct call (a stale entry).
+INDIRECT holds forward / planner glue only: every kernel the backward pass launches for its arithmetic has a kernel-level test
+(tests/test_gpu_backward_kernels.py, tests/test_gpu_kernels.py)."""
+import glob
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+INFRASTRUCTURE = {
+    "gcpx_version": "ABI version query (checked by build())",
+    "gcpx_conv_grid": "grid-size query",
+    "gcpx_graph_begin": "hipGraph capture", "gcpx_graph_end": "hipGraph capture", "gcpx_graph_launch": "hipGraph replay",
+    "gcpx_graph_destroy": "hipGraph handle",
+    "gcpx_stream_create": "stream handle", "gcpx_stream_create_priority": "stream handle", "gcpx_stream_destroy": "stream handle",
+    "gcpx_stream_wait_event": "stream ordering",
+    "gcpx_event_create": "event handle", "gcpx_event_create_sync": "event handle", "gcpx_event_record": "event handle",
+    "gcpx_event_elapsed_ms": "event timing", "gcpx_event_destroy": "event handle",
+}
+
+INDIRECT = {
+    "gcpx_bn_fold": "tests/test_gpu_model.py::test_posterior_forward_c1",
+    "gcpx_gather_rows_rest": "tests/test_gpu_model.py::test_losses_c1",
+    "gcpx_seq_pairs": "tests/test_gpu_planning.py::test_learned_cost_matches_oracle",
+    "gcpx_masked_row_sum": "tests/test_gpu_planning.py::test_learned_cost_matches_oracle",
+    "gcpx_rollout_cost": "tests/test_gpu_planning.py::test_hand_written_costs_on_device_rollouts",
+    "gcpx_copy_rows": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
+    "gcpx_seq_index": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
+    "gcpx_fill_zero": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
+    "gcpx_gauss_nll": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
+    "gcpx_aux_index_rows": "tests/test_gpu_training.py::test_gradients_match_autograd_c1",
+    "gcpx_path_cost": "tests/test_gpu_training.py::test_gradients_match_autograd_c1",
+    "gcpx_sample_length": "tests/test_gpu_model.py::test_sampled_sequence_length_c1",
+    # (called through video_gcp_amd.evaluation.image_metrics, which that test compares with the metrics oracle)
+    "gcpx_image_metrics": "tests/test_gpu_api.py::test_image_metrics_kernel_matches_oracle",
+    "gcpx_repack": "tests/test_gpu_training.py::test_two_training_steps_c1",
+    "gcpx_repack_blocks": "tests/test_gpu_training.py::test_step_with_slices_applied_during_the_backward_equals_the_late_step",
+    # (called through video_gcp_amd.dataset, which that test compares bit for bit with the reference loader's arithmetic)
+    "gcpx_assemble_batch": "tests/test_gpu_dataset.py::test_assembly_is_bit_exact_against_the_reference_loader",
+}
+
+# entry points the backward pass launches for their arithmetic: never acceptable in INDIRECT
+BACKWARD = ("_bwd", "gcpx_wgrad", "gcpx_colsum", "gcpx_reduce_partials", "gcpx_tree_accum", "gcpx_timestep_scatter", "gcpx_add_rows",
+            "gcpx_rows_strided", "gcpx_zero_unmapped_rows", "gcpx_index_offset", "gcpx_index_inverse", "gcpx_col2im4x4s2", "gcpx_im2col_image",
+            "gcpx_conv_stage", "gcpx_gemm_group")
+
+
+def _declared():
+    with open(os.path.join(ROOT, "include", "gcpx.h")) as f:
+        names = re.findall(r"^int (gcpx_\w+)\(", f.read(), re.M)
+    assert len(names) > 100 and len(set(names)) == len(names), "include/gcpx.h: declarations not found / duplicated"
+    return names
+
+
+def _gpu_test_sources():
+    files = sorted(glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py")))
+    assert files
+    text = ""
+    for p in files:
+        with open(p) as f:
+            text += f.read() + "\n"
+    return text
+
+
+def _called(name, text):
+    return re.search(r"\." + name + r"\b", text) is not None
+
+
+def test_every_entry_point_is_called_by_a_gpu_test_or_listed():
+    names, text = _declared(), _gpu_test_sources()
+    missing = [n for n in names if not _called(n, text) and n not in INFRASTRUCTURE and n not in INDIRECT]
+    assert not missing, (f"no tests/test_gpu_*.py calls {missing}: add a kernel-level test (preferred), or list the name in INDIRECT with the "
+                         "model-level test that covers it")
+
+
+def test_the_tables_are_current():
+    names, text = _declared(), _gpu_test_sources()
+    both = set(INFRASTRUCTURE) & set(INDIRECT)
+    assert not both, f"listed twice: {sorted(both)}"
+    for n in list(INFRASTRUCTURE) + list(INDIRECT):
+        assert n in names, f"{n} is listed but include/gcpx.h does not declare it"
+    stale = [n for n in INDIRECT if _called(n, text)]
+    assert not stale, f"{stale} now have a direct call in a GPU test: remove them from INDIRECT"
+    for n, ref in INDIRECT.items():
+        path, _, test = ref.partition("::")
+        with open(os.path.join(ROOT, path)) as f:
+            assert re.search(r"^def " + re.escape(test) + r"\(", f.read(), re.M), f"{n}: {ref} does not exist"
+
+
+def test_no_backward_kernel_is_covered_only_indirectly():
+    bad = [n for n in list(INDIRECT) + list(INFRASTRUCTURE) if any(k in n for k in BACKWARD) and not n.endswith(("_blocks", "_dims", "_grid"))]
+    assert not bad, f"backward-pass kernels need a kernel-level test of their own: {bad}"
