@@ -959,6 +959,24 @@ int gcpx_assemble_batch(const uint8_t* frames, const int32_t* info, const float*
                         int32_t W, int32_t state_dim, int32_t n_actions, float* traj_seq, float* I_0, float* I_g, float* pad_mask,
                         int64_t* end_ind, int64_t* start_ind, float* states, float* actions, void* stream);
 
+/* The same assembly for frames stored at Hs x Ws != H x W: between the time map and the conversion every frame is resized as the
+ *   reference's preprocess_images does (data_loader.py:213-220, resize_video(images, (img_sz, img_sz)); taken to be Pillow's 8-bit
+ *   bilinear Image.resize, see video-gcp_amd/dataset.py): a horizontal, then a vertical pass, each rounding to uint8,
+ *       out[xx] = clip((2^21 + sum_{x < bx[xx][1]} in[bx[xx][0] + x] * kx[xx][x]) >> 22, 0, 255)   (int32; likewise ky / by down a column),
+ *   over tables the host computes once per size pair in float64 (dataset.resize_coeffs) -- integer arithmetic only on the device.
+ *   frames  uint8 [B][T][Hs][Ws][3];  kx int32 [W][ksx], bx int32 [W][2] (first source column, tap count), ky int32 [H][ksy],
+ *   by int32 [H][2];  ksx = 2 * ceil(max(Ws / W, 1)) + 1, ksy likewise.  A pass whose lengths agree gets its (identity) table like any other.
+ *   A frame that is not valid under the time map is lut[0] without a read, as in gcpx_assemble_batch; every other argument and every
+ *   output is that function's, the images at H x W.
+ *   Limits (GCPX_ERR_INVALID_ARG otherwise): all four sides in [1, 512], W % 4 == 0, Hs <= 8 H and Ws <= 8 W, ksx / ksy as above,
+ *   frames and images 16-byte aligned. */
+int gcpx_resize_assemble_batch(const uint8_t* frames, const int32_t* info, const float* lut, const int32_t* kx, const int32_t* bx,
+                               const int32_t* ky, const int32_t* by, const float* pad_in, const float* states_in, const float* actions_in,
+                               const float* states_mean, const float* states_den, int32_t B, int32_t T, int32_t Hs, int32_t Ws, int32_t H,
+                               int32_t W, int32_t ksx, int32_t ksy, int32_t state_dim, int32_t n_actions, float* traj_seq, float* I_0,
+                               float* I_g, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states, float* actions,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

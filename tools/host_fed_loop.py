@@ -5,6 +5,9 @@ ModelTrainer.train_epoch over `--batches` batches in two ways, alternating (`--r
 affects both alike:
   host   — HostFedLoader: uint8 frames from a 2-slot pinned ring, H2D on its own stream, gcpx_assemble_batch into the input buffers;
   device — the same batches assembled in numpy beforehand and resident on the device, fed through the existing staging copy.
+`--source_size N` (default 64: frames stored at the model's size) stores the frames at N x N; with N != 64 the host loop uploads them
+at that size and resizes them in the assembly (gcpx_resize_assemble_batch, train.py --resize_frames 1), and the device-fed batches are
+resized by the numpy mirror beforehand.
 Prints one JSON line: steps/s of both, per round, and their ratio.  For the kernel trace run it under
 `rocprofv3 --kernel-trace --stats -- python tools/host_fed_loop.py --rounds 1`.
 """
@@ -26,6 +29,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--slots", type=int, default=2)
+    ap.add_argument("--source_size", type=int, default=64, help="side the frames are stored at (64: no resize)")
     a = ap.parse_args()
     import torch
     import video_gcp_amd  # noqa: F401
@@ -36,15 +40,17 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         data, exp = os.path.join(tmp, "data"), os.path.join(tmp, "exp")
         B, T = 16, 80
-        # 160 recorded sequences (about 190 MB) read over and over: every batch is still read, packed and uploaded
+        # 160 recorded sequences (about 190 MB at 64 x 64) read over and over: every batch is still read, packed and uploaded
         t0 = time.time()
-        FX.write_random_dataset(data, T=T, img=64, n_files=5, traj_per_file=32, phases=("train",), min_len=T)
-        FX.write_random_dataset(data, T=T, img=64, n_files=1, traj_per_file=B, phases=("val",), min_len=T)
+        N = a.source_size
+        FX.write_random_dataset(data, T=T, img=N, n_files=5, traj_per_file=32, phases=("train",), min_len=T)
+        FX.write_random_dataset(data, T=T, img=N, n_files=1, traj_per_file=B, phases=("val",), min_len=T)
         t_write = time.time() - t0
         os.makedirs(exp)
         with open(os.path.join(exp, "conf.json"), "w") as f:
             json.dump({"config": "c2", "num_epochs": 1}, f)
-        mt = ModelTrainer(get_cmd_args(["--path", exp, "--data_dir", data, "--log_outputs_interval", "1000000"]))
+        mt = ModelTrainer(get_cmd_args(["--path", exp, "--data_dir", data, "--log_outputs_interval", "1000000",
+                                        "--resize_frames", str(int(N != 64))]))
         host = DS.HostFedLoader(mt.train_loader.ds, mt.model, B, n_repeat=-(-a.batches // 10), seed=0, n_slots=a.slots,
                                 n_workers=a.workers)
         sched = host.schedule()[:a.batches]
@@ -67,6 +73,7 @@ def main():
             rd.append(timed(dev))
         mh, md = sorted(rh)[len(rh) // 2], sorted(rd)[len(rd) // 2]
         print(json.dumps({"workload": "host_fed_loop", "config": "c2", "batches": len(sched), "slots": a.slots, "workers": a.workers,
+                          "source_size": N,
                           "host_fed_steps_per_s": round(mh, 3), "device_fed_steps_per_s": round(md, 3),
                           "host_over_device": round(mh / md, 4), "rounds_host": [round(x, 3) for x in rh],
                           "rounds_device": [round(x, 3) for x in rd], "dataset_write_s": round(t_write, 1)}), flush=True)

@@ -14,10 +14,19 @@ few integers per sequence (n_frames, chop, zero_from, end_ind); csrc/batch_assem
 the device, in place in `model.input_buffer(...)` (the zero-copy hand-over of replay.py).  `assemble_numpy` is the same assembly in
 numpy, bit for bit (tests, and the device-fed comparison of tools/host_fed_loop.py).
 
-Not here: reading `.h5` (h5py), resizing (blox.vis.resize_video: frames must already be img_sz), the nav datasets' MiniWorld
-re-rendering (MazeTopRendered...).
+Resizing (data_loader.py:213-220, `preprocess_images` -> `resize_video(images, (img_sz, img_sz))`): opt-in, `VideoDataset(...,
+resize=True)` / `train.py --resize_frames 1`.  Frames stored at H_s x W_s != img_sz are then uploaded at their stored size and resized
+inside the batch assembly (gcpx_resize_assemble_batch), after pad / window / chop / zero and before the conversion, as the reference
+orders it.  blox.vis.resize_video is absent from the reference tree; that it is torchvision's `Resize` on a PIL image, i.e. Pillow's
+8-bit bilinear `Image.resize`, is inferred from data_loader.py:9,124.  That resampler is integer arithmetic over coefficient tables
+that depend on the sizes alone: `resize_coeffs` builds them in float64 as Pillow's Resample.c does, `resize_frames_numpy` is the
+integer restatement (bit-identical to Pillow on tests/golden/pil_resize.npz) and the kernel does the same integer arithmetic from the
+uploaded tables.  Pillow itself is not imported anywhere in the product.  Without the option a size mismatch raises, as before.
+
+Not here: reading `.h5` (h5py), the nav datasets' MiniWorld re-rendering (MazeTopRendered...), filters other than bilinear.
 """
 import glob
+import math
 import os
 import random
 import threading
@@ -33,6 +42,7 @@ LUT = np.arange(256, dtype=np.uint8).astype(np.float32) / 255 * 2 - 1
 
 _CLASSES = ("FolderSplitVarLenVideoDataset", "GlobalSplitVarLenVideoDataset")
 N_INFO = 8          # int32 per sequence read by gcpx_assemble_batch
+PRECISION_BITS = 22  # of the 8-bit resampler's fixed-point coefficients (Pillow, src/libImaging/Resample.c)
 
 
 def load_spec(data_dir):
@@ -78,8 +88,9 @@ class _FileCache(threading.local):
 class VideoDataset:
     """FolderSplit / GlobalSplit VarLenVideoDataset (data_loader.py:104-290) over `.npz` files."""
 
-    def __init__(self, data_dir, spec, phase, img_sz, randomize_length=False, randomize_start=False, dataset_size=-1):
+    def __init__(self, data_dir, spec, phase, img_sz, randomize_length=False, randomize_start=False, dataset_size=-1, resize=False):
         self.data_dir, self.spec, self.phase, self.img_sz = data_dir, spec, phase, int(img_sz)
+        self.resize = bool(resize)
         self.T = int(spec["max_seq_len"])
         self.randomize_length, self.randomize_start = bool(randomize_length), bool(randomize_start)
         self.dataset_size = dataset_size
@@ -91,6 +102,11 @@ class VideoDataset:
         if "states_mean" in spec:                                     # data_loader.py:127-129, standardize :97-98
             self.states_mean = np.asarray(spec["states_mean"]).astype(np.float32)
             self.states_den = np.asarray(1e-6 + np.asarray(spec["states_std"])).astype(np.float32)
+        # the size the frames are stored at: img_sz unless `resize`, then the size of item 0 (the loader's slots are sized once)
+        self.src_size = (self.img_sz, self.img_sz)
+        if self.resize:
+            im = self._cache.get(self.filenames[0])["traj0/images"]
+            self.src_size = tuple(int(x) for x in im.shape[-3:-1])
 
     def _get_filenames(self):
         if self.kind == _CLASSES[0]:                                  # data_loader.py:264-272
@@ -119,7 +135,8 @@ class VideoDataset:
         return self.dataset_size if self.dataset_size != -1 else len(self.filenames) * self.traj_per_file
 
     def read(self, index):
-        """the raw arrays of item `index` (images uint8 [T_raw, H, W, 3] of camera 0, states / actions / pad_mask f32)"""
+        """the raw arrays of item `index` (images uint8 [T_raw, H, W, 3] of camera 0 at their stored size, states / actions /
+        pad_mask f32)"""
         path = self.filenames[index // self.traj_per_file]
         F = self._cache.get(path)
         key = f"traj{index % self.traj_per_file}"
@@ -133,10 +150,15 @@ class VideoDataset:
             im = im[:, 0]                                             # number of cameras, data_loader.py:214-216
         if im.dtype != np.uint8:
             raise ValueError(f"{path}:{key}/images: frames are stored as uint8 (data_loader.py:217)")
-        if im.shape[1:] != (self.img_sz, self.img_sz, 3):
+        if self.resize:
+            if im.shape[1:] != self.src_size + (3,):
+                raise ValueError(f"{path}:{key}/images: frames are {im.shape[1]}x{im.shape[2]}, item 0 of the dataset has "
+                                 f"{self.src_size[0]}x{self.src_size[1]}: every trajectory of a resized dataset has one stored size")
+        elif im.shape[1:] != (self.img_sz, self.img_sz, 3):
             raise ValueError(f"{path}:{key}/images: frames are {im.shape[1]}x{im.shape[2]}, the model reads {self.img_sz}x{self.img_sz}. "
                              "The reference resizes with blox.vis.resize_video, which is not part of this build: store the frames "
-                             "at the model's resolution")
+                             "at the model's resolution. Or pass resize=True (train.py --resize_frames 1): the frames are then "
+                             "resized on the device as Pillow's bilinear Image.resize would")
         raw["images"] = im
         return raw
 
@@ -188,12 +210,70 @@ def _time_map(a, plan, L):
     return out
 
 
-def assemble_numpy(items, T, states_mean=None, states_den=None):
-    """[(raw, plan)] -> the model's inputs as numpy arrays, by the reference's own steps (pad, chop, convert) — what
-    gcpx_assemble_batch computes, bit for bit."""
+def resize_ksize(n_in, n_out):
+    """taps per output sample of one axis: Pillow's `(int)ceil(support) * 2 + 1` with the bilinear support 1.0 * max(n_in / n_out, 1)"""
+    return int(math.ceil(max(n_in / n_out, 1.0))) * 2 + 1
+
+
+def resize_coeffs(n_in, n_out):
+    """One axis of Pillow's 8-bit bilinear resampler (Resample.c: precompute_coeffs + normalize_coeffs_8bpc) -> (k int32 [n_out, ksize],
+    bounds int32 [n_out, 2]): output sample xx is clip((2^21 + sum_x in[bounds[xx, 0] + x] * k[xx, x]) >> 22, 0, 255) over
+    x < bounds[xx, 1]; taps past that count are 0.  Float64 in Pillow's order of operations (python floats are C doubles)."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = resize_ksize(n_in, n_out)
+    ss = 1.0 / fs
+    k = np.zeros((n_out, ksize), dtype=np.int32)
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)                   # int(): C truncation, the operands are positive or clamped
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x in range(xmax):
+            v = w[x] / ww if ww != 0.0 else w[x]
+            k[xx, x] = int(v * (1 << PRECISION_BITS) + 0.5)
+        bounds[xx] = (xmin, xmax)
+    return k, bounds
+
+
+def _resample_axis(a, axis, n_out):
+    """one pass of the resampler along `axis` of a uint8 array, rounding to uint8"""
+    n_in = a.shape[axis]
+    k, bounds = resize_coeffs(n_in, n_out)
+    a = np.moveaxis(a, axis, -1)
+    acc = np.full(a.shape[:-1] + (n_out,), 1 << (PRECISION_BITS - 1), dtype=np.int32)
+    for x in range(k.shape[1]):
+        acc += a[..., np.minimum(bounds[:, 0] + x, n_in - 1)].astype(np.int32) * k[:, x]     # k is 0 past bounds[:, 1]
+    out = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
+    return np.moveaxis(out, -1, axis)
+
+
+def resize_frames_numpy(frames, img_sz):
+    """uint8 [..., H_s, W_s, 3] -> [..., img_sz, img_sz, 3] as `Image.resize((img_sz, img_sz), BILINEAR)` of Pillow does per frame,
+    bit for bit: horizontal pass, then vertical pass, each rounding to uint8; a pass that keeps its length is skipped.  Integer
+    arithmetic (the int32 accumulator stays below 2^31: the coefficients of a sample sum to 2^22 up to rounding)."""
+    frames = np.asarray(frames)
+    assert frames.dtype == np.uint8 and frames.ndim >= 3 and frames.shape[-1] == 3
+    if frames.shape[-2] != img_sz:
+        frames = _resample_axis(frames, frames.ndim - 2, img_sz)
+    if frames.shape[-3] != img_sz:
+        frames = _resample_axis(frames, frames.ndim - 3, img_sz)
+    return np.ascontiguousarray(frames)
+
+
+def assemble_numpy(items, T, states_mean=None, states_den=None, img_sz=None):
+    """[(raw, plan)] -> the model's inputs as numpy arrays, by the reference's own steps (pad, chop, [resize to img_sz,] convert) —
+    what gcpx_assemble_batch (gcpx_resize_assemble_batch when the frames are resized) computes, bit for bit."""
     out = {k: [] for k in ("traj_seq", "pad_mask", "end_ind", "start_ind", "traj_seq_states", "actions")}
     for raw, p in items:
         im = _time_map(_maybe_pad(raw["images"], p["offset"], T), p, T)
+        if img_sz is not None and im.shape[1:3] != (img_sz, img_sz):          # data_loader.py:213-220: after the time map
+            im = resize_frames_numpy(im, img_sz)
         im = np.transpose(im, (0, 3, 1, 2)).astype(np.float32) / 255 * 2 - 1
         out["traj_seq"].append(im)
         out["pad_mask"].append(p["pad_mask"].astype(np.float32))
@@ -240,7 +320,8 @@ def epoch_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank=0, 
 
 def numpy_batch(ds, batch, seed):
     """one scheduled batch assembled on the host by assemble_numpy"""
-    return assemble_numpy([ds.item(i, item_rng(seed, c, p)) for i, p, c in batch], ds.T, ds.states_mean, ds.states_den)
+    return assemble_numpy([ds.item(i, item_rng(seed, c, p)) for i, p, c in batch], ds.T, ds.states_mean, ds.states_den,
+                          img_sz=ds.img_sz if ds.resize else None)
 
 
 def pack_item(item, j, frames, aux, info, B, T, S, A):
@@ -275,6 +356,29 @@ def assemble_into(lib, frames, aux, info, lut, mean, den, out, S, A, stream):
                                      ptr("actions"), stream), "assemble_batch")
 
 
+def resize_tables(Hs, Ws, img_sz):
+    """the int32 tables gcpx_resize_assemble_batch reads: (kx [img_sz, ksx], bx [img_sz, 2], ky [img_sz, ksy], by [img_sz, 2])"""
+    kx, bx = resize_coeffs(Ws, img_sz)
+    ky, by = resize_coeffs(Hs, img_sz)
+    return kx, bx, ky, by
+
+
+def resize_assemble_into(lib, frames, aux, info, lut, tables, mean, den, out, S, A, stream):
+    """gcpx_resize_assemble_batch from device staging tensors (frames at their stored size, `tables` = resize_tables on the device)
+    into the device tensors of `out` (the model's input names, at the model's size)"""
+    B, T, Hs, Ws, _ = frames.shape
+    H, W = out["traj_seq"].shape[-2:]
+    kx, bx, ky, by = tables
+    a = aux.data_ptr()
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    rt.check(lib.gcpx_resize_assemble_batch(frames.data_ptr(), info.data_ptr(), lut.data_ptr(), kx.data_ptr(), bx.data_ptr(),
+                                            ky.data_ptr(), by.data_ptr(), a, a + 4 * B * T if S else None,
+                                            a + 4 * B * T * (1 + S) if A else None, mean.data_ptr() if mean is not None else None,
+                                            den.data_ptr() if den is not None else None, B, T, Hs, Ws, H, W, kx.shape[1], ky.shape[1],
+                                            S, A, ptr("traj_seq"), ptr("I_0"), ptr("I_g"), ptr("pad_mask"), ptr("end_ind"),
+                                            ptr("start_ind"), ptr("traj_seq_states"), ptr("actions"), stream), "resize_assemble_batch")
+
+
 class _Streams:
     """the H2D copy stream and the ring's events.  copy_done[s]: slot s's last upload finished (its pinned slot may be refilled);
     assembled[s]: the assembly kernel that read device slot s has run (the slot may be overwritten)."""
@@ -289,7 +393,9 @@ class HostFedLoader:
     """Yields the model's input dicts, assembled on the device from uint8 frames uploaded from a ring of pinned host slots.  The
     tensors it yields ARE `model.input_buffer(...)` (no staging copy in the forward); each batch is assembled on the caller's current
     stream when the next one is asked for, i.e. behind the previous training step.  RepeatedDataLoader semantics (n_repeat passes
-    per epoch, data_loader.py:83-88), drop_last, shuffle in the train phase only."""
+    per epoch, data_loader.py:83-88), drop_last, shuffle in the train phase only.  A dataset read with resize=True whose frames are
+    stored at another size than the model's is uploaded at that size (the slots hold H_s x W_s frames) and resized in the assembly,
+    over tables uploaded once."""
 
     def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None):
         if rank is None or world is None:
@@ -331,7 +437,7 @@ class HostFedLoader:
     # ---- the ring ----
     def _alloc(self):
         dev, B, T, n = self.model.device, self.B, self.ds.T, self.n_slots
-        H = W = self.ds.img_sz
+        H, W = self.ds.src_size                        # the slots hold the frames as stored; the resize is part of the assembly
         S, A = self.S, self.A
         naux = B * T + B * T * S + B * (T - 1) * A
         pin = dict(frames=[torch.empty(B, T, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(n)],
@@ -345,6 +451,9 @@ class HostFedLoader:
         if self.ds.states_mean is not None and S:
             mean = torch.from_numpy(self.ds.states_mean).to(dev)
             den = torch.from_numpy(self.ds.states_den).to(dev)
+        self._tables = None
+        if (H, W) != (self.ds.img_sz, self.ds.img_sz):
+            self._tables = tuple(torch.from_numpy(t).to(dev) for t in resize_tables(H, W, self.ds.img_sz))
         self._bufs = (pin, devs, lut, mean, den, _Streams(dev, n))
 
     def _fill_item(self, slot, j, index, pos, cycle):
@@ -378,7 +487,11 @@ class HostFedLoader:
             out["traj_seq_states"] = ib("traj_seq_states", (B, T, S))
         if A:
             out["actions"] = ib("actions", (B, T - 1, A))
-        assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out, S, A, caller.cuda_stream)
+        if self._tables is None:
+            assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out, S, A, caller.cuda_stream)
+        else:
+            resize_assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, self._tables, mean, den, out,
+                                 S, A, caller.cuda_stream)
         st.assembled[slot].record(caller)
         return out
 

@@ -245,6 +245,8 @@ SYMBOLS = [
     ("gcpx_comm_allgather", C.c_int, [vp, vp, vp, i64, vp]),
     ("gcpx_comm_destroy", C.c_int, [vp]),
     ("gcpx_assemble_batch", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("gcpx_resize_assemble_batch", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 ]
 
 _lib = None

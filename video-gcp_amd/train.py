@@ -19,6 +19,10 @@ evaluation.Evaluator (best of `--top_of` prior samples by mse, psnr and ssim aft
 `--metric 1` evaluates the `test` split, unshuffled, writes the results and returns: no training, no optimizer step, no checkpoint.
 Deviation: the reference defaults `--skip_top100_val` to 0; here it defaults to 1, so that a plain validation is what it was (the
 prior-sampled forward and the NLL).  `--top_of` (the reference's fixed `_top_of = 100`) is this build's.
+Frame size: `--resize_frames 1` resizes recorded frames stored at another size than the model's img_sz inside the device-side batch
+assembly, as Pillow's bilinear Image.resize does (dataset.py), for the train, validation and `--metric` test loaders alike.
+Deviation: the reference resizes every item (data_loader.py:213-220); here it defaults to 0, so that a dataset of the wrong size
+stops the run as it did before the option existed.
 """
 import argparse
 import json
@@ -49,6 +53,8 @@ def get_cmd_args(argv=None):
                    "(the reference's default is 0)")
     p.add_argument("--metric", default=False, type=int, help="if 1, evaluates the test split, writes the metrics and returns")
     p.add_argument("--top_of", default=100, type=int, help="prior samples per sequence of the top-of-N evaluation")
+    p.add_argument("--resize_frames", default=0, type=int, help="if 1, frames stored at another size are resized to img_sz on the device "
+                   "(bilinear, as the reference's loader always does)")
     return p.parse_args(argv)
 
 
@@ -94,11 +100,12 @@ def val_phase(args):
     return "test" if getattr(args, "metric", False) else "val"
 
 
-def make_loader(data_dir, spec, phase, hp, model, data_opts, n_repeat=1, seed=0, rank=0, world=1):
-    """the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, shuffled in the train phase only"""
+def make_loader(data_dir, spec, phase, hp, model, data_opts, n_repeat=1, seed=0, rank=0, world=1, resize=False):
+    """the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, shuffled in the train phase only;
+    `resize`: frames stored at another size are resized to hp.img_sz in the batch assembly (--resize_frames)"""
     from .dataset import HostFedLoader, VideoDataset
-    return HostFedLoader(VideoDataset(data_dir, spec, phase, hp.img_sz, **data_opts), model, hp.batch_size, n_repeat=n_repeat, seed=seed,
-                         rank=rank, world=world)
+    return HostFedLoader(VideoDataset(data_dir, spec, phase, hp.img_sz, resize=resize, **data_opts), model, hp.batch_size,
+                         n_repeat=n_repeat, seed=seed, rank=rank, world=world)
 
 
 class SyntheticLoader:
@@ -173,7 +180,7 @@ class ModelTrainer:
             # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val / test unshuffled
             reps = int(conf.get("epoch_cycles_train", 1))
             mk = lambda phase: make_loader(self.data_dir, spec, phase, hp, self.model, data_opts, n_repeat=reps, seed=seed, rank=self.rank,
-                                           world=max(self.world, 1))
+                                           world=max(self.world, 1), resize=bool(getattr(args, "resize_frames", 0)))
             train_loader = train_loader or mk("train")
             val_loader = val_loader or mk(val_phase(args))
         if not args.feed_random_data and train_loader is None:
