@@ -977,6 +977,56 @@ int gcpx_resize_assemble_batch(const uint8_t* frames, const int32_t* info, const
                                float* I_g, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states, float* actions,
                                void* stream);
 
+/* ---- picture logs (video-gcp_amd/image_log.py): a whole panel composed by one launch out of f32 tensors on the device.
+ *   Replaces the host loops of the reference's logger: HierarchyLogger.log_hierarchy_image (logger.py:114-182), log_loss_gif
+ *   (logger.py:236-253), log_dense_gif / log_rows_gif + make_gif (logger.py:214-234, visualization.py:485-497), plot_balanced_tree
+ *   (visualization.py:232-262), plot_val_tree (:327-362), plot_gt_matching_overview (:365-400) and plot_greyscale_dist (:51-55).
+ *   The canvas is [n][H_c][W_c][3] (channel-last), first filled with `background`; then the tiles are applied IN TABLE ORDER (a later
+ *   tile overwrites an earlier one on the pixels they share: the reference's sequential assignment), then, if post_rescale, every
+ *   element becomes (x + 1) / 2 (logger.py:180).  A tile descriptor emits, for sample b < nb and frame f < nf, one h x w rectangle at
+ *       canvas index n0 + b n_b + f n_f,  row r0 + b r_b + f r_f,  column c0 + b c_b + f c_f  (+ index[b] * w, see below)
+ *   clipped to the canvas.  Kinds:
+ *     GCPX_PANEL_IMAGE     pixel (yy, xx) of channel ch = src[off + b s_b + f s_f + ch s_c + yy s_y + xx]  (channel-first f32 frames)
+ *     GCPX_PANEL_GREY      all three channels = src[off + b s_b + f s_f + (xx / tile_w) s_c]: nearest-tile expansion of a row of values
+ *     GCPX_PANEL_GREY_ADD  the same value ADDED to what the canvas holds (f32, table order): the gamma strips of logger.py:132-148
+ *     GCPX_PANEL_FILL      the constant `fill`
+ *   src / index / length are slots of the `srcs` array (-1: none); src_elems[slot] is the element count of that array and every read
+ *   is checked against it (an out-of-range read leaves the pixel as it was).
+ *   index  (int32, or int64 with GCPX_PANEL_INDEX_I64): v = index[index_off + b index_stride]; the rectangle of sample b is skipped
+ *          unless 0 <= v < index_count; v * w is added to the column (a node's matched time step, logger.py:145-154), or, with
+ *          GCPX_PANEL_INDEX_FRAME, v replaces f in the SOURCE address (batchwise_index, visualization.py:359).
+ *   length (int32, or int64 with GCPX_PANEL_LENGTH_I64; IMAGE / GREY): frames f > length[b] are multiplied by 0 (mask_extra,
+ *          logger.py:160-161, get_pad_mask utils.py:30-50); with GCPX_PANEL_LENGTH_STRICT frames f >= length[b] (pad_sequence's zeros).
+ *   GCPX_PANEL_RESCALE (IMAGE / GREY): (x + 1) / 2 (imgtensor2np, visualization.py:113), after the mask.
+ *   Outputs (either may be null, not both): canvas_f32, and canvas_u8 = trunc(clip(x, 0, 1) * 255), this build's own conversion.
+ *   The pointers of `srcs` travel as kernel arguments, so a cached device table serves every logging step; the host arrays are read
+ *   before the call returns.  Nothing is allocated, nothing synchronises. */
+#define GCPX_PANEL_MAX_SRCS 16
+#define GCPX_PANEL_IMAGE 0
+#define GCPX_PANEL_GREY 1
+#define GCPX_PANEL_GREY_ADD 2
+#define GCPX_PANEL_FILL 3
+#define GCPX_PANEL_RESCALE 1
+#define GCPX_PANEL_LENGTH_STRICT 2
+#define GCPX_PANEL_INDEX_FRAME 4
+#define GCPX_PANEL_INDEX_I64 8
+#define GCPX_PANEL_LENGTH_I64 16
+typedef struct gcpx_panel_tile {
+    int32_t kind, src, index, length, flags;
+    int32_t nb, nf;                    /* samples, frames */
+    int32_t h, w, tile_w;              /* rectangle in pixels; GREY kinds: pixels per value */
+    int32_t n0, n_b, n_f;              /* canvas index of (b, f) */
+    int32_t r0, r_b, r_f;              /* top row */
+    int32_t c0, c_b, c_f;              /* left column */
+    int32_t index_off, index_stride, index_count;
+    float fill;
+    int32_t _pad;
+    int64_t off, s_b, s_f, s_c, s_y;   /* source offset and strides in elements */
+} gcpx_panel_tile;
+int gcpx_panel_compose(const gcpx_panel_tile* tiles, int32_t n_tiles, const void* const* srcs, const int64_t* src_elems, int32_t n_srcs,
+                       int32_t n, int32_t H_c, int32_t W_c, float background, int32_t post_rescale, float* canvas_f32,
+                       uint8_t* canvas_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

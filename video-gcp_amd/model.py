@@ -367,6 +367,15 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         """base_gcp.py:294-304: sum of weight * value over weights > 0, divided by prod(traj_seq.shape[1:])."""
         return Outputs(value=losses["_total"])
 
+    # ---- picture logs (tree.py:79-108): composed on the device, written as PNG / APNG under self.log_dir (image_log.py) ----
+    log_dir = None
+
+    def log_outputs(self, outputs, inputs, losses, step, log_images, phase):
+        """TreeModel.log_outputs: the pictures of one logging step; returns the files written.  log_images false: nothing is
+        launched, copied or written (scalars are not logged by this build)."""
+        from . import image_log
+        return image_log.log_outputs(self, image_log.tree_panels, outputs, inputs, losses, step, log_images, phase)
+
     # ---- ragged views: these synchronise (they read seq_len on the host), keep them out of timed regions ----
     def pruned_prediction(self, out):
         """outputs.pruned_prediction: list of [len_b, 3, H, W] (tree.py:62-65)."""

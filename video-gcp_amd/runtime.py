@@ -111,6 +111,19 @@ class ActBwdArgs(C.Structure):
                 ("H", i32), ("W", i32), ("C", i32)]
 
 
+class PanelTile(C.Structure):
+    """gcpx_panel_tile: one tile descriptor of a picture-log panel (include/gcpx.h, csrc/panel.hip)"""
+    _fields_ = [("kind", i32), ("src", i32), ("index", i32), ("length", i32), ("flags", i32), ("nb", i32), ("nf", i32),
+                ("h", i32), ("w", i32), ("tile_w", i32), ("n0", i32), ("n_b", i32), ("n_f", i32), ("r0", i32), ("r_b", i32),
+                ("r_f", i32), ("c0", i32), ("c_b", i32), ("c_f", i32), ("index_off", i32), ("index_stride", i32),
+                ("index_count", i32), ("fill", C.c_float), ("_pad", i32), ("off", i64), ("s_b", i64), ("s_f", i64), ("s_c", i64),
+                ("s_y", i64)]
+
+
+PANEL_MAX_SRCS = 16
+PANEL_IMAGE, PANEL_GREY, PANEL_GREY_ADD, PANEL_FILL = 0, 1, 2, 3
+PANEL_RESCALE, PANEL_LENGTH_STRICT, PANEL_INDEX_FRAME, PANEL_INDEX_I64, PANEL_LENGTH_I64 = 1, 2, 4, 8, 16
+
 WG_ROWS, WG_CONV1D, WG_CONV3X3, WG_CONV4X4S2 = 0, 1, 2, 3
 WMAP_LINEAR, WMAP_CONV, WMAP_CONVT = 0, 1, 2
 
@@ -247,6 +260,7 @@ SYMBOLS = [
     ("gcpx_assemble_batch", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("gcpx_resize_assemble_batch", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                              vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("gcpx_panel_compose", C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp]),
 ]
 
 _lib = None

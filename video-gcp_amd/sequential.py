@@ -596,6 +596,11 @@ class GCPSequentialModel(GCPTreeModel):
             out.seq_len_logits = o["seq_len_logits"]
         return out
 
+    def log_outputs(self, outputs, inputs, losses, step, log_images, phase):
+        """SequentialModel.log_outputs (sequential.py:116-121): the dense_rec video; returns the files written"""
+        from . import image_log
+        return image_log.log_outputs(self, image_log.sequential_panels, outputs, inputs, losses, step, log_images, phase)
+
     def pruned_prediction(self, out):
         lens = out.raw["seq_len"].tolist()
         return [out.raw["images"][b, :lens[b]] for b in range(len(lens))]

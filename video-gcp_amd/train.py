@@ -23,6 +23,11 @@ Frame size: `--resize_frames 1` resizes recorded frames stored at another size t
 assembly, as Pillow's bilinear Image.resize does (dataset.py), for the train, validation and `--metric` test loaders alike.
 Deviation: the reference resizes every item (data_loader.py:213-220); here it defaults to 0, so that a dataset of the wrong size
 stops the run as it did before the option existed.
+Picture logs: `--log_images 1` writes the reference's prediction panels (model.log_outputs, image_log.py) as PNG / animated PNG to
+<path>/images/<name>_<phase>_<step>.png|.apng, on rank 0, unless --dont_save: in training every int(epoch_len / --imepoch) steps
+(train.py:125-130,147,170-172), in validation for the last batch's prior-sampled prediction (train.py:229-230).
+Deviation: the reference defaults `--log_images` to 1 (gcp_builder.py:231); here it defaults to 0, and the loop then issues no launch,
+copy or sync it did not issue before.
 """
 import argparse
 import json
@@ -55,6 +60,9 @@ def get_cmd_args(argv=None):
     p.add_argument("--top_of", default=100, type=int, help="prior samples per sequence of the top-of-N evaluation")
     p.add_argument("--resize_frames", default=0, type=int, help="if 1, frames stored at another size are resized to img_sz on the device "
                    "(bilinear, as the reference's loader always does)")
+    p.add_argument("--imepoch", default=4, type=int, help="number of times pictures are logged per epoch")
+    p.add_argument("--log_images", default=0, type=int, help="if 1, writes prediction panels to <path>/images (the reference's "
+                   "default is 1)")
     return p.parse_args(argv)
 
 
@@ -190,6 +198,10 @@ class ModelTrainer:
         self.global_step = 0
         self.log = []
         # gcp_builder.py:91-95 (both models have a dense_rec here): the top-of-N evaluator, on --metric or --skip_top100_val 0
+        self.log_images = bool(getattr(args, "log_images", 0)) and not args.dont_save and self.rank == 0
+        if self.log_images:
+            self.model.log_dir = os.path.join(self.exp_path, "images")
+        self.image_files = []
         self.evaluator = None
         if getattr(args, "metric", False) or not getattr(args, "skip_top100_val", True):
             from .evaluation import Evaluator
@@ -248,9 +260,13 @@ class ModelTrainer:
         if hasattr(self.train_loader, "set_epoch"):
             self.train_loader.set_epoch(epoch)          # the dataset loader's shuffle and draws are keyed on the epoch
         end = time.time()
+        # train.py:147 (an epoch shorter than --imepoch batches logs every step instead of dividing by zero)
+        images_interval = max(1, int(len(self.train_loader) / max(1, getattr(self.cmd_args, "imepoch", 4)))) if self.log_images else 0
         for batch_idx, inputs in enumerate(self.train_loader):
             out = self.trainer.step(inputs)            # zero_grad, forward, loss, backward, (all-reduce), optimizer.step
             self.model.step()                          # train.py:163
+            if self.log_images and self.global_step % images_interval == 0:          # train.py:125-126,170-172
+                self.image_files += self.model.log_outputs(out, inputs, None, self.global_step, True, "train")
             if self.global_step % self.cmd_args.log_outputs_interval == 0:
                 total = float(out.raw["losses"][5])    # the only host sync of the loop, on logging steps
                 self.log.append((self.global_step, total))
@@ -265,9 +281,14 @@ class ModelTrainer:
     def val(self):
         tot, n = 0.0, 0
         start = time.time()
-        for inputs in self.val_loader:
+        n_val = len(self.val_loader) if self.log_images and hasattr(self.val_loader, "__len__") else -1
+        for i_val, inputs in enumerate(self.val_loader):
             with self.model.val_mode(pred_length=False):
                 output = self.model(inputs, "test")
+                # train.py:229-230: the pictures of the last batch's prediction -- taken here, before the training-mode forward below
+                # reuses the buffers `output` views
+                if self.log_images and i_val == n_val - 1 and not getattr(self.cmd_args, "metric", False):
+                    self.image_files += self.model.log_outputs(output, inputs, None, self.global_step, True, "val")
                 if self.evaluator is not None:         # train.py:208-209: every batch, prior samples of the model's own noise stream
                     self.evaluator.eval(inputs, output, self.model)
             out = self.model(inputs)
