@@ -1027,6 +1027,48 @@ int gcpx_panel_compose(const gcpx_panel_tile* tiles, int32_t n_tiles, const void
                        int32_t n, int32_t H_c, int32_t W_c, float background, int32_t post_rescale, float* canvas_f32,
                        uint8_t* canvas_u8, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Scalar logs (video-gcp_amd/scalar_log.py; csrc/train_stats.hip).
+ *
+ * gcpx_grad_segment_norms: log_gradients (base_model.py:139-146): `torch.norm(p.grad)` of every parameter with a gradient, their mean
+ *   and maximum.  grad: the trainer's flat f32 gradient of n elements, laid out like theta (segments on 16-byte boundaries, any
+ *   length).  chunks [n_chunks]: every counted segment cut into pieces of at most GCPX_GRAD_NORM_CHUNK elements, the pieces of one
+ *   segment adjacent; seg_chunk0 [n_seg + 1]: the first chunk of every segment (a prefix sum; seg_chunk0[n_seg] = n_chunks).  Both
+ *   tables live on the device and are built once per model (scalar_log.grad_tables).  Only the elements the chunks name are read, and
+ *   a chunk outside [0, n) or longer than GCPX_GRAD_NORM_CHUNK is skipped.
+ *   seg_norm[s] = |grad_scale| * coef * || segment s ||_2, with grad_scale as gcpx_grad_clip_coef takes it (1 / world when the buffer
+ *   holds the ranks' sum) and coef = *clip_coef (NULL or a value of 0: 1) -- the clipping coefficient the step kernels apply to the
+ *   gradient they read, where the reference's clip_grad_norm_ has scaled p.grad itself before it is logged.
+ *   A segment whose elements are all exactly zero is NOT counted (this build's `p.grad is None`: a parameter off the graph gets no
+ *   gradient write and keeps the zeros of the step's clear).  stats[0..3] = mean of the counted norms, their maximum (a NaN stays, as in
+ *   torch.max), the number counted, the number of counted norms that are not finite; mean and maximum are 0 when nothing is counted.
+ *   partial: caller's scratch of n_partial >= 2 * n_chunks floats.  Two launches on `stream`; nothing is allocated, nothing
+ *   synchronises.  Deterministic and bit-repeatable: a thread of the 256 of a chunk's workgroup adds at most GCPX_GRAD_NORM_SERIAL
+ *   squares into one f32 accumulator, a fixed tree of depth GCPX_GRAD_NORM_TREE_DEPTH adds the accumulators, and the chunks of a segment
+ *   are added in table order in f64; the root and the scale are applied in f64 and rounded to f32 once.  So the relative error of a
+ *   norm is at most (GCPX_GRAD_NORM_SERIAL + GCPX_GRAD_NORM_TREE_DEPTH + 2) / 2 * 2^-24 (as long as no square leaves the f32 range:
+ *   elements below 1e-19 or above 1e19 in magnitude underflow / overflow, as they do in torch.norm of an f32 tensor).
+ *
+ * gcpx_kl_layerwise: the layer-wise KL of TreeModule._log_outputs (tree_module.py:159-169).  q_z / p_z rows [mu | log_sigma] at
+ *   base + b * batch_stride + n * node_stride for the N = 2^L - 1 nodes in depth-first order, as gcpx_kl_gauss reads them.
+ *   node_v[b * N + n] = mean over the nz latent dimensions of max(KL_elem, free_nats), KL_elem being the element gcpx_kl_gauss sums;
+ *   out[l] = mean of node_v over (b, the 2^l nodes of level l) counting only entries != 0, NaN when none remain (`l[l != 0].mean()`).
+ *   The level of depth-first position p is L - 1 - ctz(p + 1).  Two launches on `stream`, fixed summation order. */
+#define GCPX_GRAD_NORM_THREADS 256
+#define GCPX_GRAD_NORM_CHUNK 16384
+#define GCPX_GRAD_NORM_SERIAL (GCPX_GRAD_NORM_CHUNK / GCPX_GRAD_NORM_THREADS + 1)
+#define GCPX_GRAD_NORM_TREE_DEPTH 8
+typedef struct gcpx_grad_chunk {
+    int64_t first;                     /* first element of the chunk in the flat vector */
+    int32_t seg;                       /* the segment it belongs to */
+    int32_t length;                    /* 1 .. GCPX_GRAD_NORM_CHUNK */
+} gcpx_grad_chunk;
+int gcpx_grad_segment_norms(const float* grad, int64_t n, const gcpx_grad_chunk* chunks, int32_t n_chunks, const int32_t* seg_chunk0,
+                            int32_t n_seg, float grad_scale, const float* clip_coef, float* partial, int64_t n_partial, float* seg_norm,
+                            float* stats, void* stream);
+int gcpx_kl_layerwise(const float* qz, const float* pz, int32_t B, int32_t L, int32_t nz, int64_t batch_stride, int64_t node_stride,
+                      float free_nats, float* node_v, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

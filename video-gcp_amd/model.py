@@ -367,13 +367,20 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         """base_gcp.py:294-304: sum of weight * value over weights > 0, divided by prod(traj_seq.shape[1:])."""
         return Outputs(value=losses["_total"])
 
-    # ---- picture logs (tree.py:79-108): composed on the device, written as PNG / APNG under self.log_dir (image_log.py) ----
+    # ---- logs (base_model.py:86-108, tree.py:79-108): pictures composed on the device, written as PNG / APNG under self.log_dir
+    # (image_log.py); scalars through self.scalar_log, a scalar_log.ScalarLogger (the trainer's --log_scalars) ----
     log_dir = None
+    scalar_log = None
 
     def log_outputs(self, outputs, inputs, losses, step, log_images, phase):
-        """TreeModel.log_outputs: the pictures of one logging step; returns the files written.  log_images false: nothing is
-        launched, copied or written (scalars are not logged by this build)."""
+        """TreeModel.log_outputs: the scalars and the pictures of one logging step; returns the picture files written.
+        Scalars (when self.scalar_log is set and `losses` is given): every loss term as `<name>_loss`, `total_loss`, and the
+        layer-wise KL `kl_loss_layerwise/level_<l>` of a posterior forward in phase train / val.  With no scalar logger and
+        log_images false: nothing is launched, copied or written."""
         from . import image_log
+        if self.scalar_log is not None:
+            from . import scalar_log
+            scalar_log.log_scalars(self, outputs, losses, step, phase, layerwise=True)
         return image_log.log_outputs(self, image_log.tree_panels, outputs, inputs, losses, step, log_images, phase)
 
     # ---- ragged views: these synchronise (they read seq_len on the host), keep them out of timed regions ----

@@ -597,8 +597,12 @@ class GCPSequentialModel(GCPTreeModel):
         return out
 
     def log_outputs(self, outputs, inputs, losses, step, log_images, phase):
-        """SequentialModel.log_outputs (sequential.py:116-121): the dense_rec video; returns the files written"""
+        """SequentialModel.log_outputs (sequential.py:116-121): the loss terms as scalars (when self.scalar_log is set and `losses` is
+        given) and the dense_rec video; returns the picture files written"""
         from . import image_log
+        if self.scalar_log is not None:
+            from . import scalar_log
+            scalar_log.log_scalars(self, outputs, losses, step, phase)
         return image_log.log_outputs(self, image_log.sequential_panels, outputs, inputs, losses, step, log_images, phase)
 
     def pruned_prediction(self, out):

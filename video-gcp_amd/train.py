@@ -28,6 +28,15 @@ Picture logs: `--log_images 1` writes the reference's prediction panels (model.l
 (train.py:125-130,147,170-172), in validation for the last batch's prior-sampled prediction (train.py:229-230).
 Deviation: the reference defaults `--log_images` to 1 (gcp_builder.py:231); here it defaults to 0, and the loop then issues no launch,
 copy or sync it did not issue before.
+Scalar logs: `--log_scalars 1` writes, on rank 0 unless --dont_save, a TensorBoard event file and scalar_data.json under <path>/events
+(scalar_log.py; gcp_builder.py:41-54, logger.py:43-44,98-100).  On the steps that already synchronise (global_step %
+--log_outputs_interval == 0): every loss term of the step as `<name>_loss_train`, `total_loss_train`, the tree's
+`kl_loss_layerwise/level_<l>_train`, `gradients/mean_norm_train`, `gradients/max_norm_train` (base_model.py:139-146) and
+`gradients/nonfinite_train` over the per-parameter gradient norms, `time/batch_train` and `time/data_load_train` (the clocks of
+train.py:182-186).  After a validation: the averages of every term over its batches, once, at global_step, as `..._val`
+(train.py:229-230), the layer-wise KL of the last batch, and scalar_data.json is rewritten.  Under a process group the loss terms are
+rank 0's shard (the reference's DataParallel saw the whole batch); the gradient norms are of the all-reduced gradient, identical on
+every rank.  Deviation: the reference always logs; `--log_scalars` defaults to 0, and nothing then changes anywhere.
 """
 import argparse
 import json
@@ -63,6 +72,8 @@ def get_cmd_args(argv=None):
     p.add_argument("--imepoch", default=4, type=int, help="number of times pictures are logged per epoch")
     p.add_argument("--log_images", default=0, type=int, help="if 1, writes prediction panels to <path>/images (the reference's "
                    "default is 1)")
+    p.add_argument("--log_scalars", default=0, type=int, help="if 1, writes loss terms, gradient norms and the layer-wise KL to "
+                   "<path>/events (event file + scalar_data.json; the reference always does)")
     return p.parse_args(argv)
 
 
@@ -202,6 +213,10 @@ class ModelTrainer:
         if self.log_images:
             self.model.log_dir = os.path.join(self.exp_path, "images")
         self.image_files = []
+        self.scalar_log = None
+        if bool(getattr(args, "log_scalars", 0)) and not args.dont_save and self.rank == 0:
+            from .scalar_log import ScalarLogger
+            self.scalar_log = self.model.scalar_log = ScalarLogger(os.path.join(self.exp_path, "events"))
         self.evaluator = None
         if getattr(args, "metric", False) or not getattr(args, "skip_top100_val", True):
             from .evaluation import Evaluator
@@ -213,13 +228,18 @@ class ModelTrainer:
         start_epoch = 0
         if self.cmd_args.resume:
             start_epoch = self.resume(self.cmd_args.resume)
-        if getattr(self.cmd_args, "metric", False):
-            self.val()                                 # train.py:222-226: one evaluation pass of the test split, then stop
-            return
-        if self.cmd_args.train:
-            self.train(start_epoch)
-        else:
-            self.val()
+        try:
+            if getattr(self.cmd_args, "metric", False):
+                self.val()                             # train.py:222-226: one evaluation pass of the test split, then stop
+                return
+            if self.cmd_args.train:
+                self.train(start_epoch)
+            else:
+                self.val()
+        finally:
+            if self.scalar_log is not None:
+                self.scalar_log.dump_scalars()
+                self.scalar_log.close()
 
     # ---- train.py:56-70, checkpoint_handler.py:31-74 ----
     def resume(self, ckpt, path=None):
@@ -262,7 +282,11 @@ class ModelTrainer:
         end = time.time()
         # train.py:147 (an epoch shorter than --imepoch batches logs every step instead of dividing by zero)
         images_interval = max(1, int(len(self.train_loader) / max(1, getattr(self.cmd_args, "imepoch", 4)))) if self.log_images else 0
+        slog = self.scalar_log
+        tick, data_time, n_timed = time.time(), 0.0, 0          # (--log_scalars only) time spent waiting for the loader
         for batch_idx, inputs in enumerate(self.train_loader):
+            if slog is not None:
+                data_time, n_timed = data_time + time.time() - tick, n_timed + 1
             out = self.trainer.step(inputs)            # zero_grad, forward, loss, backward, (all-reduce), optimizer.step
             self.model.step()                          # train.py:163
             if self.log_images and self.global_step % images_interval == 0:          # train.py:125-126,170-172
@@ -270,16 +294,35 @@ class ModelTrainer:
             if self.global_step % self.cmd_args.log_outputs_interval == 0:
                 total = float(out.raw["losses"][5])    # the only host sync of the loop, on logging steps
                 self.log.append((self.global_step, total))
+                batch_time = (time.time() - end) / max(1, self.cmd_args.log_outputs_interval)
                 if self.rank == 0:
                     print("itr: {} Train Epoch: {} [{}/{}]\tLoss: {:.6f}\t{:.3f}s/batch".format(
-                        self.global_step, epoch, batch_idx, len(self.train_loader), total,
-                        (time.time() - end) / max(1, self.cmd_args.log_outputs_interval)), flush=True)
+                        self.global_step, epoch, batch_idx, len(self.train_loader), total, batch_time), flush=True)
+                if slog is not None:
+                    self.log_train_scalars(out, inputs, total, batch_time, data_time / max(n_timed, 1))
+                    data_time, n_timed = 0.0, 0
                 end = time.time()
             self.global_step += 1
+            if slog is not None:
+                tick = time.time()
+
+    def log_train_scalars(self, out, inputs, total, batch_time, data_time):
+        """the scalars of one logging step (base_model.py:86-108,139-146, train.py:170-186): loss terms, layer-wise KL, gradient norms
+        (one launch behind the step, read back in one copy) and the two host clocks"""
+        stats = self.trainer.gradient_stats().stats
+        losses = self.model.loss(inputs, out)
+        losses["_total"] = total
+        self.model.log_outputs(out, inputs, losses, self.global_step, False, "train")
+        mean, mx, _, nonfinite = stats.tolist()
+        for name, v in (("gradients/mean_norm", mean), ("gradients/max_norm", mx), ("gradients/nonfinite", nonfinite),
+                        ("time/batch", batch_time), ("time/data_load", data_time)):
+            self.scalar_log.log_scalar(v, name, self.global_step, "train")
+        self.scalar_log.flush()
 
     # ---- train.py:195-238: prior-sampled prediction (val_mode) + the training forward for the NLL, no gradient ----
     def val(self):
         tot, n = 0.0, 0
+        slog, term_names, term_sum = self.scalar_log, None, None
         start = time.time()
         n_val = len(self.val_loader) if self.log_images and hasattr(self.val_loader, "__len__") else -1
         for i_val, inputs in enumerate(self.val_loader):
@@ -295,8 +338,18 @@ class ModelTrainer:
             losses = self.model.loss(inputs, out)
             tot += float(self.model.get_total_loss(inputs, losses).value)
             n += 1
+            if slog is not None:                       # train.py:203,214: the meter of every term, kept on the device
+                term_names = [k for k in losses if k != "_total"]
+                vec = torch.stack([losses[k].value.reshape(()) for k in term_names])
+                term_sum = vec if term_sum is None else term_sum + vec
         avg = tot / max(n, 1)
         self.last_val = avg
+        if slog is not None and n and not getattr(self.cmd_args, "metric", False):
+            # train.py:229-230: the averages, once, at global_step; the layer-wise KL is the last batch's (its posterior forward `out`)
+            avg_terms = dict(zip(term_names, (term_sum / n).unbind(0)))
+            avg_terms["_total"] = avg
+            self.model.log_outputs(out, inputs, avg_terms, self.global_step, False, "val")
+            slog.dump_scalars()
         if self.evaluator is not None:
             self.dump_results()
             if self.cmd_args.metric:

@@ -359,5 +359,23 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
                 warnings.warn(f"checkpoint was trained with {k}={st[k]!r}, this trainer runs {k}={getattr(self, k)!r}")
         self._clip_state_dirty = True         # a restored clip coefficient must not outlive a trainer without clipping
 
+    def gradient_stats(self):
+        """log_gradients (base_model.py:139-146) after `step()` / `backward()`: the L2 norm of every parameter's gradient, their mean
+        and maximum -- one gcpx_grad_segment_norms on the caller's stream, no sync.  Returns device tensors:
+        Outputs(names, seg_norm [len(names)], stats [4] = mean, max, number counted, number of non-finite norms).  The gradient buffer
+        still holds the step's gradient (the optimizer kernels read it, the next backward clears it); under a process group it holds
+        the ranks' sum and is scaled by 1 / world here; the step's clipping coefficient (opt_state[1], 0 = none) is applied as the
+        step kernels apply it.  A parameter whose gradient is zero everywhere is not counted (`p.grad is None`)."""
+        from .plan_ops import Outputs
+        from .scalar_log import GradStats
+        if getattr(self, "_grad_stats", None) is None:
+            self._grad_stats = GradStats(self.m)
+        scale = 1.0
+        if self.buckets is not None and torch.distributed.is_initialized():
+            scale = 1.0 / torch.distributed.get_world_size(self.buckets.group)
+        st = torch.cuda.current_stream(self.m.device).cuda_stream
+        seg_norm, stats = self._grad_stats.launch(self.m.lib, self.grad, scale, self.opt_state.data_ptr() + 4, st)
+        return Outputs(names=self._grad_stats.names, seg_norm=seg_norm, stats=stats)
+
     def named_grads(self):
         return {k: self.grad[o:o + int(torch.tensor(shp).prod())].view(shp) for k, (o, shp) in self.m._poff.items()}
