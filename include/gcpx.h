@@ -977,6 +977,33 @@ int gcpx_resize_assemble_batch(const uint8_t* frames, const int32_t* info, const
                                float* I_g, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states, float* actions,
                                void* stream);
 
+/* The assembly for the nav datasets, whose frames are not recorded images but top-down pictures of the maze drawn from the states
+ *   (MazeTopRenderedGlobalSplitVarLenVideoDataset.process_data_dict, /root/reference/gcp/datasets/data_loader.py:299-319, calling
+ *   Multiroom3dEnv.render_pos_top_down, gcp/planning/infra/envs/miniworld_env/multiroom3d/multiroom3d_env.py:185-219).  Called by
+ *   video-gcp_amd/dataset.py: topdown_assemble_into (HostFedLoader._assemble).
+ *   background  uint8 [side][side][3]: the static picture padded by cw zeros on every side, after the reference's * 255 truncation;
+ *   agent_stamp / goal_stamp  uint8 [k][k] (non-zero: painted), k odd, entry [k / 2][k / 2] on the point; agent_rgb / goal_rgb: the dot
+ *   colours as r | g << 8 | b << 16;  coords int32 [B][T][2]: (x, y) of the agent in the padded picture for the frames of the window
+ *   states[offset : offset + T] (first n_frames = info[b][0] valid), goal int32 [B][2]: (x, y) of the goal (dataset.topdown_pixels).
+ *   Output frame t reads window frame s = min(t + chop, T - 1) when t <= end_ind, t < zero_from and s < n_frames (else lut[0], nothing
+ *   read: the reference renders frames up to end_ind and leaves zeros behind them, whatever zero_from says for states and actions):
+ *       the 2cw x 2cw block of the picture whose first pixel is (max(cw, x) - cw, max(cw, y) - cw), rows by y and columns by x,
+ *       with the agent stamp's colour written around (x, y), then the goal stamp's around the goal (the goal wins), both clipped to the
+ *       block (which lies inside the picture: the caller checks max(cw, x) + cw <= side, likewise y; the device clamps the block into the
+ *       picture, so a caller that does not check gets a wrong picture, never a wild read),
+ *   then resized 2cw -> H x W with the two integer passes of gcpx_resize_assemble_batch over its tables for (Hs, Ws) = (2cw, 2cw), and
+ *   converted through lut.  info, lut, the tables, the auxiliary windows and every output are that function's.
+ *   Limits (GCPX_ERR_INVALID_ARG otherwise, nothing launched): no null table, background, stamp or coordinate pointer, 2cw in [4, 128],
+ *   side in [2cw, 16384], k odd and <= 31, H and W in [1, 512], W % 4 == 0, 2cw <= 8 H and 8 W, ksx / ksy the tap counts of the sizes,
+ *   background 4-byte and images 16-byte aligned. */
+int gcpx_topdown_assemble_batch(const uint8_t* background, int32_t side, int32_t cw, const uint8_t* agent_stamp, const uint8_t* goal_stamp,
+                                int32_t k, int32_t agent_rgb, int32_t goal_rgb, const int32_t* coords, const int32_t* goal,
+                                const int32_t* info, const float* lut, const int32_t* kx, const int32_t* bx, const int32_t* ky,
+                                const int32_t* by, const float* pad_in, const float* states_in, const float* actions_in,
+                                const float* states_mean, const float* states_den, int32_t B, int32_t T, int32_t H, int32_t W, int32_t ksx,
+                                int32_t ksy, int32_t state_dim, int32_t n_actions, float* traj_seq, float* I_0, float* I_g, float* pad_mask,
+                                int64_t* end_ind, int64_t* start_ind, float* states, float* actions, void* stream);
+
 /* ---- picture logs (video-gcp_amd/image_log.py): a whole panel composed by one launch out of f32 tensors on the device.
  *   Replaces the host loops of the reference's logger: HierarchyLogger.log_hierarchy_image (logger.py:114-182), log_loss_gif
  *   (logger.py:236-253), log_dense_gif / log_rows_gif + make_gif (logger.py:214-234, visualization.py:485-497), plot_balanced_tree

@@ -14,14 +14,11 @@
 // (dataset.resize_coeffs).  Integer only here, so the pixels are Pillow's whatever the compiler flags.
 // Limits (invalid argument otherwise): sides of source and output in [1, 512], W a multiple of 4, Hs / H and Ws / W at most 8 (no limit on
 // up-sampling inside the side limits), tap counts equal to Pillow's for the sizes, 16-byte aligned frames and images.
-#include <algorithm>
+#include "resize_passes.h"
 
-#include "common.h"
+using namespace gcpx_resize;   // kThreads, kInfo, the two passes of the resampler and the choice of the band
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kInfo = 8;     // int32 per sequence: n_frames, n_states, n_actions, chop, zero_from, end_ind, -, -
 
 // one thread = four consecutive pixels of one frame: 12 bytes read, one float4 written to each of the three channel planes
 __global__ void __launch_bounds__(kThreads) assemble_frames_kernel(const uint8_t* __restrict__ frames, const int32_t* __restrict__ info,
@@ -104,80 +101,6 @@ __global__ void __launch_bounds__(kThreads) assemble_small_kernel(const int32_t*
 }
 
 // ---- resize + assembly --------------------------------------------------------------------------------------------------------
-constexpr int kPrecisionBits = 22;            // Pillow's PRECISION_BITS for 8-bit channels
-constexpr int kResizeMaxSide = 512;
-constexpr int kResizeMaxScale = 8;
-constexpr int kResizeLdsTarget = 24 * 1024;   // per workgroup when a band can be made that small: six workgroups to a CU
-constexpr int kResizeLdsMax = 64 * 1024;
-
-// taps per output sample of one axis: Pillow's (int)ceil(support) * 2 + 1, support = max(n_in / n_out, 1)
-inline int resize_ksize(const int n_in, const int n_out) {
-    return (n_in <= n_out ? 1 : (n_in + n_out - 1) / n_out) * 2 + 1;
-}
-
-// source rows output rows [r0, r1) read, by the host table's own float64 arithmetic (dataset.resize_coeffs)
-inline int resize_span(const int n_in, const int n_out, const int r0, const int r1) {
-    const double scale = (double)n_in / n_out, support = scale < 1.0 ? 1.0 : scale;
-    int lo = (int)((r0 + 0.5) * scale - support + 0.5), hi = (int)((r1 - 1 + 0.5) * scale + support + 0.5);
-    if (lo < 0) lo = 0;
-    if (hi > n_in) hi = n_in;
-    return hi - lo;
-}
-
-// LDS of one workgroup: lut f32[256] | kx i32[W * ksx] | bx i32[2 W] | ky i32[R * ksy] | by i32[2 R] | raw u8 | hres u8
-struct ResizeLds {
-    int raw_off, raw_cap, hres_off, total;
-};
-__host__ __device__ inline ResizeLds resize_lds(const int Ws, const int W, const int ksx, const int ksy, const int R, const int cap) {
-    ResizeLds l;
-    l.raw_off = ((256 + W * ksx + 2 * W + R * ksy + 2 * R) * 4 + 15) & ~15;
-    l.raw_cap = (cap * Ws * 3 + 32) & ~15;    // the band's source rows from the 16-byte boundary below their first byte
-    l.hres_off = l.raw_off + l.raw_cap;
-    l.total = l.hres_off + ((cap * W * 3 + 15) & ~15) + 64;    // + what zero-weight taps of the last row may read (resize_rows)
-    return l;
-}
-
-__device__ __forceinline__ int clip8(const int acc) { return min(max(acc >> kPrecisionBits, 0), 255); }
-
-// The horizontal pass of one band.  A thread keeps one output column xx (kThreads / W rows are in flight; all columns in turn when
-// W >= kThreads): first source column, tap count and the KS coefficients stay in registers while it walks down the staged rows.  The
-// 3 KS bytes a row contributes are read as the ND aligned dwords around them and shifted down to the first byte (v_alignbyte), a third
-// of the LDS reads that byte loads take.  Taps past the count have coefficient 0; what they read lies inside the workgroup's LDS (at
-// most 4 ND <= 56 bytes past the staged rows: hres and the slack behind it) and is multiplied by it.
-template <int KS>
-__device__ __forceinline__ void resize_rows(const uint8_t* __restrict__ raw, const int shift, uint8_t* __restrict__ hres,
-                                            const int32_t* __restrict__ skx, const int32_t* __restrict__ sbx, const int nrows,
-                                            const int Ws, const int W, const int tid) {
-    constexpr int ND = (3 * KS + 3) / 4 + 1;
-    const bool wide = W >= kThreads;
-    const int rp = wide ? 1 : kThreads / W, rr = wide ? 0 : tid / W;
-    if (rr >= rp) return;
-    const int row_bytes = Ws * 3, hrow = W * 3;
-    const uint32_t* raw32 = reinterpret_cast<const uint32_t*>(raw);
-    for (int xx = wide ? tid : tid - rr * W; xx < W; xx += kThreads) {
-        const int xmin = min(max(sbx[2 * xx], 0), Ws - 1);
-        const int cnt = min(max(sbx[2 * xx + 1], 0), min(KS, Ws - xmin));
-        int k[KS];
-#pragma unroll
-        for (int x = 0; x < KS; ++x) k[x] = x < cnt ? skx[xx * KS + x] : 0;
-        int o = shift + rr * row_bytes + xmin * 3;
-        uint8_t* q = hres + rr * hrow + xx * 3;
-        for (int r = rr; r < nrows; r += rp, o += rp * row_bytes, q += rp * hrow) {
-            const uint32_t* d = raw32 + (o >> 2);
-            uint32_t w[ND];
-#pragma unroll
-            for (int i = 0; i < ND; ++i) w[i] = d[i];
-#pragma unroll
-            for (int i = 0; i + 1 < ND; ++i) w[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], (uint32_t)(o & 3));
-            int a[3] = {1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1)};
-#pragma unroll
-            for (int j = 0; j < 3 * KS; ++j) a[j % 3] += __mul24((int)((w[j >> 2] >> (8 * (j & 3))) & 255), k[j / 3]);
-            q[0] = (uint8_t)clip8(a[0]);
-            q[1] = (uint8_t)clip8(a[1]);
-            q[2] = (uint8_t)clip8(a[2]);
-        }
-    }
-}
 
 // one workgroup = R output rows (a band) of one output frame.  The band's `nrows` <= cap source rows are one contiguous run of bytes:
 // 16-byte loads into LDS, horizontal pass LDS -> LDS as bytes (resize_rows),
@@ -211,16 +134,7 @@ __global__ void __launch_bounds__(kThreads) resize_assemble_frames_kernel(
     float* dg = t == end_ind ? Ig + (size_t)b * 3 * HW + (size_t)r0 * W : nullptr;
     tab[tid] = lut[tid];
     if (!valid) {                                 // a padded frame resizes to zeros: lut[0], nothing read
-        const float pad = lut[0];
-        const float4 v = make_float4(pad, pad, pad, pad);
-        for (int i = tid; i < nr * W4; i += kThreads) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                *reinterpret_cast<float4*>(dst + (size_t)c * HW + 4 * i) = v;
-                if (d0) *reinterpret_cast<float4*>(d0 + (size_t)c * HW + 4 * i) = v;
-                if (dg) *reinterpret_cast<float4*>(dg + (size_t)c * HW + 4 * i) = v;
-            }
-        }
+        store_pad_band(lut[0], nr, W4, HW, dst, d0, dg, tid);
         return;
     }
     for (int i = tid; i < W * ksx; i += kThreads) skx[i] = kx[i];
@@ -252,60 +166,20 @@ __global__ void __launch_bounds__(kThreads) resize_assemble_frames_kernel(
     }
     __syncthreads();
     // horizontal pass: hres[r][xx][c] for the nrows staged rows
-    switch (ksx) {
-        case 3: resize_rows<3>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        case 5: resize_rows<5>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        case 7: resize_rows<7>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        case 9: resize_rows<9>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        case 11: resize_rows<11>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        case 13: resize_rows<13>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        case 15: resize_rows<15>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
-        default: resize_rows<17>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;   // 2 * kResizeMaxScale + 1
-    }
+    resize_rows_any(ksx, raw, shift, hres, skx, sbx, nrows, Ws, W, tid);
     __syncthreads();
     // vertical pass, conversion and stores
-    {
-        const int dy = kThreads / W4, dgp = kThreads - dy * W4;
-        int yy = tid / W4, g = tid - yy * W4;
-        const int hrow4 = (W * 3) >> 2;
-        while (yy < nr) {
-            const int ymin = min(max(sby[2 * yy], y_lo), y_lo + nrows - 1);
-            const int cnt = min(max(sby[2 * yy + 1], 0), min(ksy, y_lo + nrows - ymin));
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(hres) + (ymin - y_lo) * hrow4 + g * 3;
-            const int32_t* k = sky + yy * ksy;
-            int a[12];
-#pragma unroll
-            for (int j = 0; j < 12; ++j) a[j] = 1 << (kPrecisionBits - 1);
-            for (int y = 0; y < cnt; ++y) {
-                const int kk = k[y];
-                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
-                q += hrow4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    a[j] += __mul24((int)((w0 >> (8 * j)) & 255), kk);
-                    a[4 + j] += __mul24((int)((w1 >> (8 * j)) & 255), kk);
-                    a[8 + j] += __mul24((int)((w2 >> (8 * j)) & 255), kk);
-                }
-            }
-            const size_t o = (size_t)yy * W + 4 * g;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {         // bytes RGBR GBRG BRGB: channel c of pixel j is byte 3 j + c
-                const float4 v = make_float4(tab[clip8(a[c])], tab[clip8(a[3 + c])], tab[clip8(a[6 + c])], tab[clip8(a[9 + c])]);
-                *reinterpret_cast<float4*>(dst + (size_t)c * HW + o) = v;
-                if (d0) *reinterpret_cast<float4*>(d0 + (size_t)c * HW + o) = v;
-                if (dg) *reinterpret_cast<float4*>(dg + (size_t)c * HW + o) = v;
-            }
-            g += dgp;
-            yy += dy;
-            if (g >= W4) {
-                g -= W4;
-                ++yy;
-            }
-        }
-    }
+    resize_cols_store(hres, sky, sby, tab, y_lo, nrows, nr, W, ksy, HW, dst, d0, dg, tid);
 }
 
 }  // namespace
+
+void gcpx_resize::launch_assemble_small(hipStream_t stream, const int32_t* info, const float* pad_in, const float* states_in,
+                                        const float* actions_in, const float* mean, const float* den, const int B, const int T, const int S,
+                                        const int A, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states, float* actions) {
+    hipLaunchKernelGGL(assemble_small_kernel, dim3(B), dim3(kThreads), 0, stream, info, pad_in, S ? states_in : nullptr,
+                       A ? actions_in : nullptr, mean, den, T, S, A, pad_mask, end_ind, start_ind, states, actions);
+}
 
 extern "C" int gcpx_assemble_batch(const uint8_t* frames, const int32_t* info, const float* lut, const float* pad_in,
                                    const float* states_in, const float* actions_in, const float* states_mean, const float* states_den,
@@ -324,9 +198,8 @@ extern "C" int gcpx_assemble_batch(const uint8_t* frames, const int32_t* info, c
                    "frames / outputs not 16-byte aligned");
     const dim3 grid((unsigned)(B * T), (unsigned)(((HW + 3) / 4 + kThreads - 1) / kThreads));
     hipLaunchKernelGGL(assemble_frames_kernel, grid, dim3(kThreads), 0, stream, frames, info, lut, T, HW, traj_seq, I_0, I_g);
-    hipLaunchKernelGGL(assemble_small_kernel, dim3(B), dim3(kThreads), 0, stream, info, pad_in, state_dim ? states_in : nullptr,
-                       n_actions ? actions_in : nullptr, states_mean, states_den, T, state_dim, n_actions, pad_mask, end_ind,
-                       start_ind, states, actions);
+    launch_assemble_small(stream, info, pad_in, states_in, actions_in, states_mean, states_den, B, T, state_dim, n_actions, pad_mask,
+                          end_ind, start_ind, states, actions);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }
@@ -351,25 +224,16 @@ extern "C" int gcpx_resize_assemble_batch(const uint8_t* frames, const int32_t* 
     GCPX_CHECK_ARG(!states_mean == !states_den, "states_mean and states_den go together");
     GCPX_CHECK_ARG(((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(traj_seq) | reinterpret_cast<uintptr_t>(I_0) |
                      reinterpret_cast<uintptr_t>(I_g)) & 15) == 0, "frames / outputs not 16-byte aligned");
-    // the bands: the fewest equal bands of output rows whose source rows and horizontal result fit the LDS target, else single rows
-    // inside the LDS limit
-    int R = 0, cap = 0;
+    int cap = 0;
     ResizeLds L{};
-    for (int nb = 1; nb <= H && !R; ++nb) {
-        const int r = (H + nb - 1) / nb;
-        int c = 0;
-        for (int r0 = 0; r0 < H; r0 += r) c = std::max(c, resize_span(Hs, H, r0, std::min(r0 + r, H)));
-        L = resize_lds(Ws, W, ksx, ksy, r, c);
-        if (L.total <= (r > 1 ? kResizeLdsTarget : kResizeLdsMax)) R = r, cap = c;
-    }
+    const int R = resize_choose_band(Hs, Ws, H, W, ksx, ksy, &cap, &L);
     GCPX_CHECK_ARG(R > 0, "one output row's source rows do not fit the LDS");    // (the limits above keep the worst case at 62 KB)
     const long long total_bytes = (long long)B * T * Hs * Ws * 3;
     const dim3 grid((unsigned)(B * T), (unsigned)((H + R - 1) / R));
     hipLaunchKernelGGL(resize_assemble_frames_kernel, grid, dim3(kThreads), (size_t)L.total, stream, frames, info, lut, kx, bx, ky, by, T,
                        Hs, Ws, H, W, ksx, ksy, R, cap, total_bytes, traj_seq, I_0, I_g);
-    hipLaunchKernelGGL(assemble_small_kernel, dim3(B), dim3(kThreads), 0, stream, info, pad_in, state_dim ? states_in : nullptr,
-                       n_actions ? actions_in : nullptr, states_mean, states_den, T, state_dim, n_actions, pad_mask, end_ind,
-                       start_ind, states, actions);
+    launch_assemble_small(stream, info, pad_in, states_in, actions_in, states_mean, states_den, B, T, state_dim, n_actions, pad_mask,
+                          end_ind, start_ind, states, actions);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

@@ -23,7 +23,17 @@ that depend on the sizes alone: `resize_coeffs` builds them in float64 as Pillow
 integer restatement (bit-identical to Pillow on tests/golden/pil_resize.npz) and the kernel does the same integer arithmetic from the
 uploaded tables.  Pillow itself is not imported anywhere in the product.  Without the option a size mismatch raises, as before.
 
-Not here: reading `.h5` (h5py), the nav datasets' MiniWorld re-rendering (MazeTopRendered...), filters other than bilinear.
+Top-down rendering (data_loader.py:299-319, multiroom3d_env.py:185-219): the nav datasets (`dataset_class` Nav9Rooms, Nav25Rooms or
+MazeTopRenderedGlobalSplitVarLenVideoDataset; GlobalSplit file rules) do not train on recorded frames.  Every frame t <= end_ind is a crop
+of 2cw x 2cw pixels of a static picture of the maze around the agent's state, with a dot on the agent and one on the goal (the state at
+end_ind), resized to img_sz; later frames are zero.  The picture and the dot's shape are made by OpenCV from the dataset's textures in
+the reference; both are constant for a dataset and enter as data, `<data_dir>/topdown_assets.npz` (INTEGRATION.md has the recipe).  From
+those arrays on the renderer is integer work: `topdown_pixels` is the reference's float32 state -> pixel arithmetic, `render_topdown_numpy`
+the crop and the two dots.  Recorded images are neither read nor uploaded: an item carries the agent's pixel per window frame and the
+goal's pixel, and gcpx_topdown_assemble_batch (csrc/topdown_assemble.hip) renders, resizes and converts in the launch that writes the
+model's inputs.  The model gets states[..., :2] (MazeGlobalSplit..., data_loader.py:292-296).
+
+Not here: reading `.h5` (h5py), building the top-down picture from textures, filters other than bilinear.
 """
 import glob
 import math
@@ -41,6 +51,9 @@ from . import runtime as rt
 LUT = np.arange(256, dtype=np.uint8).astype(np.float32) / 255 * 2 - 1
 
 _CLASSES = ("FolderSplitVarLenVideoDataset", "GlobalSplitVarLenVideoDataset")
+# datasets whose frames are rendered top-down from the states (gcp/datasets/configs/nav_9rooms.py, nav_25rooms.py)
+_TOPDOWN_CLASSES = ("MazeTopRenderedGlobalSplitVarLenVideoDataset", "Nav9Rooms", "Nav25Rooms")
+TOPDOWN_ASSETS = "topdown_assets.npz"
 N_INFO = 8          # int32 per sequence read by gcpx_assemble_batch
 PRECISION_BITS = 22  # of the 8-bit resampler's fixed-point coefficients (Pillow, src/libImaging/Resample.c)
 
@@ -60,18 +73,119 @@ def spec_overrides(spec, fields):
     return {k: v for k, v in spec.items() if not isinstance(v, (list, tuple)) and k in fields}
 
 
+def _spec_class(spec):
+    """the last component of the name of the spec's `dataset_class` (a string, or the placeholder class a spec file imports), or None"""
+    c = spec.get("dataset_class")
+    if c is None:
+        return None
+    name = c if isinstance(c, str) else getattr(c, "__name__", repr(c))
+    return name.rsplit(".", 1)[-1]
+
+
 def dataset_class_name(spec):
     """the spec's `dataset_class` (gcp_builder.py:105-113; FolderSplit when absent).  Any other class raises: the nav datasets'
     MazeTopRendered... re-renders frames with MiniWorld, and training on un-rendered frames without saying so is worse than stopping."""
-    c = spec.get("dataset_class")
-    if c is None:
+    name = _spec_class(spec)
+    if name is None:
         return _CLASSES[0]
-    name = c if isinstance(c, str) else getattr(c, "__name__", repr(c))
-    name = name.rsplit(".", 1)[-1]
     if name not in _CLASSES:
         raise ValueError(f"dataset_spec['dataset_class'] = {name}: only {' and '.join(_CLASSES)} are built (the nav datasets' "
                          "top-down re-rendering needs MiniWorld, which is not part of this build)")
     return name
+
+
+def load_topdown_assets(data_dir):
+    """`<data_dir>/topdown_assets.npz` -> dict: background uint8 [S + 2cw, S + 2cw, 3], cw, n_rooms, scale, S, agent_stamp / goal_stamp
+    bool [k, k], agent_color / goal_color uint8 [3].  S = int(table_size * scale) with table_size = (1 / 3) * int(sqrt(n_rooms)) as the
+    reference computes it (multiroom3d layout; 256 for 9 rooms, 426 for 25 at the reference's scale of 256)."""
+    path = os.path.join(data_dir, TOPDOWN_ASSETS)
+    if not os.path.exists(path):
+        raise ValueError(f"{path} not found: a MazeTopRendered... dataset (Nav9Rooms, Nav25Rooms) trains on top-down pictures drawn from "
+                         "the states; the static picture and the dot stamps come from the reference's OpenCV renderer and are dumped "
+                         "once, with the .h5 -> .npz conversion (INTEGRATION.md, 'Top-down assets')")
+    with np.load(path) as z:
+        a = dict(background=np.ascontiguousarray(z["background"]), cw=int(z["crop_window"]), n_rooms=int(z["n_rooms"]),
+                 scale=int(z["render_scale"]), agent_stamp=np.ascontiguousarray(z["agent_stamp"]).astype(bool),
+                 goal_stamp=np.ascontiguousarray(z["goal_stamp"]).astype(bool), agent_color=z["agent_color"].astype(np.uint8).reshape(3),
+                 goal_color=z["goal_color"].astype(np.uint8).reshape(3))
+    a["S"] = int(topdown_table_size(a["n_rooms"]) * a["scale"])
+    side, k = a["S"] + 2 * a["cw"], a["agent_stamp"].shape[0]
+    if a["background"].dtype != np.uint8 or a["background"].shape != (side, side, 3):
+        raise ValueError(f"{path}: background is {a['background'].dtype} {a['background'].shape}, expected uint8 {(side, side, 3)} "
+                         f"(n_rooms {a['n_rooms']}, render_scale {a['scale']}, crop_window {a['cw']})")
+    if not 4 <= 2 * a["cw"] <= 128:
+        raise ValueError(f"{path}: crop_window {a['cw']}: the window side 2 * crop_window must be in [4, 128]")
+    if a["agent_stamp"].shape != (k, k) or a["goal_stamp"].shape != (k, k) or k % 2 == 0 or k > 31:
+        raise ValueError(f"{path}: the stamps are {a['agent_stamp'].shape} and {a['goal_stamp'].shape}: both [k, k], k odd, at most 31")
+    return a
+
+
+def topdown_table_size(n_rooms):
+    """side of the maze in render units: `(1 / 3) * rooms_per_side`, a Python float as in the reference"""
+    return (1 / 3) * int(math.sqrt(n_rooms))
+
+
+def topdown_pixels(states_xy, n_rooms, scale, S, cw):
+    """states [n, >= 2] -> int32 [n, 2]: (x, y) of each state in the padded top-down picture (convert_sim2topdown plus the crop-window
+    correction, multiroom3d_env.py:194-208), in float32 as numpy evaluates the reference's expressions on float32 states;
+    int() truncates toward zero."""
+    p = np.asarray(states_xy, dtype=np.float32)[..., :2].reshape(-1, 2)
+    q = (p * np.array([1, -1], dtype=np.float32)) / np.float32(27.0) + np.float32(0.5 * topdown_table_size(n_rooms))
+    v = np.trunc(q * np.float32(scale)).astype(np.int64)
+    out = np.stack([v[:, 0] + cw, (S + cw) - v[:, 1]], axis=1)
+    return np.clip(out, -2 ** 31, 2 ** 31 - 1).astype(np.int32)
+
+
+def _paint(win, stamp, color, px, py, lx, ly):
+    """stamp centred on picture pixel (px, py) into the window whose first pixel is (lx, ly); the window lies inside the picture, so
+    clipping to the window clips to the picture as well"""
+    k, D = stamp.shape[0], win.shape[0]
+    x0, y0 = px - k // 2 - lx, py - k // 2 - ly                     # the stamp's first entry in window coordinates
+    xs, xe, ys, ye = max(x0, 0), min(x0 + k, D), max(y0, 0), min(y0 + k, D)
+    if xs < xe and ys < ye:
+        win[ys:ye, xs:xe][stamp[ys - y0:ye - y0, xs - x0:xe - x0]] = color
+
+
+def topdown_fits(assets, xy):
+    """bool [n]: the crop around pixel (x, y) lies inside the padded picture (where it does not, the reference fails on a shape mismatch)"""
+    xy = np.asarray(xy).reshape(-1, 2).astype(np.int64)
+    cw, side = assets["cw"], assets["background"].shape[0]
+    return (np.maximum(xy, cw) + cw <= side).all(axis=1)
+
+
+def render_topdown_numpy(assets, xy, goal_xy):
+    """agent pixels int [n, 2] and the goal pixel [2] (topdown_pixels) -> uint8 [n, 2cw, 2cw, 3]: render_pos_top_down
+    (multiroom3d_env.py:185-219) after its uint8 conversion.  The agent's dot, then the goal's, are painted on the padded picture and
+    clipped at its border; the crop is centred on (max(cw, x), max(cw, y)).  Only the crop is copied."""
+    xy = np.asarray(xy).reshape(-1, 2)
+    if not topdown_fits(assets, xy).all():
+        raise ValueError(f"top-down crop outside the padded picture for pixels {xy[~topdown_fits(assets, xy)].tolist()}")
+    bg, cw = assets["background"], assets["cw"]
+    gx, gy = (int(v) for v in goal_xy)
+    out = np.empty((xy.shape[0], 2 * cw, 2 * cw, 3), dtype=np.uint8)
+    for i, (x, y) in enumerate(xy.tolist()):
+        lx, ly = max(cw, x) - cw, max(cw, y) - cw
+        out[i] = bg[ly:ly + 2 * cw, lx:lx + 2 * cw]
+        _paint(out[i], assets["agent_stamp"], assets["agent_color"], x, y, lx, ly)
+        _paint(out[i], assets["goal_stamp"], assets["goal_color"], gx, gy, lx, ly)
+    return out
+
+
+def topdown_item_pixels(item, T, assets):
+    """(raw, plan) of a top-rendered dataset -> (agent pixels int32 [n, 2] of the window states[offset : offset + T], goal pixel int32
+    [2]): output frame t <= end_ind shows window frame min(t + chop, T - 1), the goal is the state shown at end_ind.  Raises when a
+    frame's crop does not fit the padded picture."""
+    raw, p = item
+    pix = topdown_pixels(raw["states"][p["offset"]:p["offset"] + T], assets["n_rooms"], assets["scale"], assets["S"], assets["cw"])
+    shown = np.minimum(np.arange(p["end_ind"] + 1) + p["chop"], T - 1)
+    if shown[-1] >= pix.shape[0]:
+        raise ValueError(f"{raw.get('name', 'item')}: end_ind {p['end_ind']} with chop {p['chop']} reads past the {pix.shape[0]} states")
+    bad = ~topdown_fits(assets, pix[shown])
+    if bad.any():
+        t = int(np.argmax(bad))
+        raise ValueError(f"{raw.get('name', 'item')}: the top-down crop of frame {t} (state {raw['states'][p['offset'] + shown[t], :2].tolist()}"
+                         f", pixel {pix[shown[t]].tolist()}) does not fit the padded {assets['background'].shape[0]} px picture")
+    return pix, pix[shown[-1]].copy()
 
 
 class _FileCache(threading.local):
@@ -94,7 +208,13 @@ class VideoDataset:
         self.T = int(spec["max_seq_len"])
         self.randomize_length, self.randomize_start = bool(randomize_length), bool(randomize_start)
         self.dataset_size = dataset_size
-        self.kind = dataset_class_name(spec)
+        self.topdown = None
+        if _spec_class(spec) in _TOPDOWN_CLASSES:                     # GlobalSplit file rules; frames drawn from the states
+            self.kind = _CLASSES[1]
+            self.topdown = load_topdown_assets(data_dir)
+            self.resize = True                                        # always: the crop is 2cw, the model reads img_sz
+        else:
+            self.kind = dataset_class_name(spec)
         self.filenames = self._get_filenames()
         self._cache = _FileCache()
         self.traj_per_file = int(self._cache.get(self.filenames[0])["traj_per_file"])
@@ -104,7 +224,9 @@ class VideoDataset:
             self.states_den = np.asarray(1e-6 + np.asarray(spec["states_std"])).astype(np.float32)
         # the size the frames are stored at: img_sz unless `resize`, then the size of item 0 (the loader's slots are sized once)
         self.src_size = (self.img_sz, self.img_sz)
-        if self.resize:
+        if self.topdown is not None:
+            self.src_size = (2 * self.topdown["cw"],) * 2
+        elif self.resize:
             im = self._cache.get(self.filenames[0])["traj0/images"]
             self.src_size = tuple(int(x) for x in im.shape[-3:-1])
 
@@ -113,7 +235,7 @@ class VideoDataset:
             names = sorted(glob.glob(os.path.join(self.data_dir, "hdf5", self.phase + "/*")))
         else:                                                         # :275-290 (.npz instead of .h5)
             names = [os.path.join(r, f) for r, fs in _sorted_walk(self.data_dir) for f in fs
-                     if f.endswith(".npz") and f != "dataset_info.npz"]
+                     if f.endswith(".npz") and f not in ("dataset_info.npz", TOPDOWN_ASSETS)]
         if not names:
             raise RuntimeError(f"No filenames found in {self.data_dir}")
         random.Random(2).shuffle(names)                               # _shuffle_with_seed, :251-255
@@ -136,15 +258,22 @@ class VideoDataset:
 
     def read(self, index):
         """the raw arrays of item `index` (images uint8 [T_raw, H, W, 3] of camera 0 at their stored size, states / actions /
-        pad_mask f32)"""
+        pad_mask f32).  A top-rendered dataset reads no images (files may omit them): states[..., :2], actions, pad_mask and the
+        trajectory's name for messages."""
         path = self.filenames[index // self.traj_per_file]
         F = self._cache.get(path)
         key = f"traj{index % self.traj_per_file}"
         raw = {}
-        for name in ("images", "states", "actions", "pad_mask"):
+        for name in ("images", "states", "actions", "pad_mask")[self.topdown is not None:]:
             k = f"{key}/{name}"
             if k in F.files:
                 raw[name] = F[k] if name == "images" else F[k].astype(np.float32)
+        if self.topdown is not None:
+            if "states" not in raw:
+                raise ValueError(f"{path}:{key}: a top-rendered dataset draws its frames from the states, which this trajectory lacks")
+            raw["states"] = raw["states"][..., :2]                    # only x, y reach the model (data_loader.py:292-296)
+            raw["name"] = f"{path}:{key}"
+            return raw
         im = raw["images"]
         if im.ndim == 5:
             im = im[:, 0]                                             # number of cameras, data_loader.py:214-216
@@ -266,12 +395,20 @@ def resize_frames_numpy(frames, img_sz):
     return np.ascontiguousarray(frames)
 
 
-def assemble_numpy(items, T, states_mean=None, states_den=None, img_sz=None):
+def assemble_numpy(items, T, states_mean=None, states_den=None, img_sz=None, topdown=None):
     """[(raw, plan)] -> the model's inputs as numpy arrays, by the reference's own steps (pad, chop, [resize to img_sz,] convert) —
-    what gcpx_assemble_batch (gcpx_resize_assemble_batch when the frames are resized) computes, bit for bit."""
+    what gcpx_assemble_batch (gcpx_resize_assemble_batch when the frames are resized) computes, bit for bit.  With `topdown` (the assets
+    of a top-rendered dataset) the frames up to end_ind are rendered from the states and resized to img_sz, the rest is zero:
+    gcpx_topdown_assemble_batch."""
     out = {k: [] for k in ("traj_seq", "pad_mask", "end_ind", "start_ind", "traj_seq_states", "actions")}
     for raw, p in items:
-        im = _time_map(_maybe_pad(raw["images"], p["offset"], T), p, T)
+        if topdown is not None:
+            pix, goal = topdown_item_pixels((raw, p), T, topdown)
+            n = p["end_ind"] + 1
+            im = np.zeros((T, 2 * topdown["cw"], 2 * topdown["cw"], 3), dtype=np.uint8)
+            im[:n] = render_topdown_numpy(topdown, pix[np.minimum(np.arange(n) + p["chop"], T - 1)], goal)
+        else:
+            im = _time_map(_maybe_pad(raw["images"], p["offset"], T), p, T)
         if img_sz is not None and im.shape[1:3] != (img_sz, img_sz):          # data_loader.py:213-220: after the time map
             im = resize_frames_numpy(im, img_sz)
         im = np.transpose(im, (0, 3, 1, 2)).astype(np.float32) / 255 * 2 - 1
@@ -321,16 +458,23 @@ def epoch_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank=0, 
 def numpy_batch(ds, batch, seed):
     """one scheduled batch assembled on the host by assemble_numpy"""
     return assemble_numpy([ds.item(i, item_rng(seed, c, p)) for i, p, c in batch], ds.T, ds.states_mean, ds.states_den,
-                          img_sz=ds.img_sz if ds.resize else None)
+                          img_sz=ds.img_sz if ds.resize else None, topdown=ds.topdown)
 
 
-def pack_item(item, j, frames, aux, info, B, T, S, A):
+def pack_item(item, j, frames, aux, info, B, T, S, A, topdown=None):
     """sequence j of a staging slot (numpy views): the uint8 window raw[offset : offset + T], pad mask / state / action windows in
-    aux = [pad_mask B*T | states B*T*S | actions B*(T-1)*A], and the per-sequence integers of gcpx_assemble_batch"""
+    aux = [pad_mask B*T | states B*T*S | actions B*(T-1)*A], and the per-sequence integers of gcpx_assemble_batch.  With `topdown`
+    (the assets of a top-rendered dataset) `frames` is the int32 coordinate slot [B*T*2 agent pixels | B*2 goal pixels] instead (the
+    kernel renders frames up to end_ind only; states and actions keep the time map of every dataset)."""
     raw, p = item
     o = p["offset"]
-    fr = raw["images"][o:o + T]
-    frames[j, :fr.shape[0]] = fr
+    if topdown is not None:
+        fr, goal = topdown_item_pixels(item, T, topdown)
+        frames[:B * T * 2].reshape(B, T, 2)[j, :fr.shape[0]] = fr
+        frames[B * T * 2:].reshape(B, 2)[j] = goal
+    else:
+        fr = raw["images"][o:o + T]
+        frames[j, :fr.shape[0]] = fr
     aux[j * T:(j + 1) * T] = p["pad_mask"]
     n_s = n_a = 0
     if S:
@@ -379,6 +523,37 @@ def resize_assemble_into(lib, frames, aux, info, lut, tables, mean, den, out, S,
                                             ptr("start_ind"), ptr("traj_seq_states"), ptr("actions"), stream), "resize_assemble_batch")
 
 
+def topdown_device_assets(assets, img_sz, device):
+    """what gcpx_topdown_assemble_batch keeps on the device for a dataset: the padded picture, both stamps (uint8) and the resize tables
+    for (2cw, 2cw) -> img_sz; plus the host-side integers of the call"""
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    rgb = lambda c: int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16
+    D = 2 * assets["cw"]
+    return dict(background=t(assets["background"]), agent_stamp=t(assets["agent_stamp"].astype(np.uint8)),
+                goal_stamp=t(assets["goal_stamp"].astype(np.uint8)), tables=tuple(t(x) for x in resize_tables(D, D, img_sz)),
+                cw=assets["cw"], k=int(assets["agent_stamp"].shape[0]), agent_rgb=rgb(assets["agent_color"]),
+                goal_rgb=rgb(assets["goal_color"]))
+
+
+def topdown_assemble_into(lib, dev_assets, coords, aux, info, lut, mean, den, out, S, A, stream):
+    """gcpx_topdown_assemble_batch from the device-resident assets (topdown_device_assets) and the staging tensors (coords int32
+    [B*T*2 + B*2], aux, info) into the device tensors of `out` (the model's input names)"""
+    B, T = out["traj_seq"].shape[:2]
+    H, W = out["traj_seq"].shape[-2:]
+    d = dev_assets
+    kx, bx, ky, by = d["tables"]
+    a, c = aux.data_ptr(), coords.data_ptr()
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    rt.check(lib.gcpx_topdown_assemble_batch(d["background"].data_ptr(), d["background"].shape[0], d["cw"], d["agent_stamp"].data_ptr(),
+                                             d["goal_stamp"].data_ptr(), d["k"], d["agent_rgb"], d["goal_rgb"], c, c + 4 * B * T * 2,
+                                             info.data_ptr(), lut.data_ptr(), kx.data_ptr(), bx.data_ptr(), ky.data_ptr(), by.data_ptr(),
+                                             a, a + 4 * B * T if S else None, a + 4 * B * T * (1 + S) if A else None,
+                                             mean.data_ptr() if mean is not None else None, den.data_ptr() if den is not None else None,
+                                             B, T, H, W, kx.shape[1], ky.shape[1], S, A, ptr("traj_seq"), ptr("I_0"), ptr("I_g"),
+                                             ptr("pad_mask"), ptr("end_ind"), ptr("start_ind"), ptr("traj_seq_states"), ptr("actions"),
+                                             stream), "topdown_assemble_batch")
+
+
 class _Streams:
     """the H2D copy stream and the ring's events.  copy_done[s]: slot s's last upload finished (its pinned slot may be refilled);
     assembled[s]: the assembly kernel that read device slot s has run (the slot may be overwritten)."""
@@ -395,7 +570,8 @@ class HostFedLoader:
     stream when the next one is asked for, i.e. behind the previous training step.  RepeatedDataLoader semantics (n_repeat passes
     per epoch, data_loader.py:83-88), drop_last, shuffle in the train phase only.  A dataset read with resize=True whose frames are
     stored at another size than the model's is uploaded at that size (the slots hold H_s x W_s frames) and resized in the assembly,
-    over tables uploaded once."""
+    over tables uploaded once.  A top-rendered dataset (dataset.topdown) has no frame slots at all: a slot holds int32 pixel coordinates
+    [B][T][2] + [B][2], and the padded picture, the stamps and the tables for (2cw, 2cw, img_sz) stay on the device."""
 
     def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None):
         if rank is None or world is None:
@@ -440,19 +616,23 @@ class HostFedLoader:
         H, W = self.ds.src_size                        # the slots hold the frames as stored; the resize is part of the assembly
         S, A = self.S, self.A
         naux = B * T + B * T * S + B * (T - 1) * A
-        pin = dict(frames=[torch.empty(B, T, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(n)],
-                   aux=[torch.empty(naux, dtype=torch.float32, pin_memory=True) for _ in range(n)],
+        top = self.ds.topdown is not None
+        fkey, fshape, ftype = ("coords", (B * T * 2 + B * 2,), torch.int32) if top else ("frames", (B, T, H, W, 3), torch.uint8)
+        pin = {fkey: [torch.empty(fshape, dtype=ftype, pin_memory=True) for _ in range(n)]}
+        pin.update(aux=[torch.empty(naux, dtype=torch.float32, pin_memory=True) for _ in range(n)],
                    info=[torch.zeros(B, N_INFO, dtype=torch.int32, pin_memory=True) for _ in range(n)])
-        devs = dict(frames=[torch.empty(B, T, H, W, 3, dtype=torch.uint8, device=dev) for _ in range(n)],
-                    aux=[torch.empty(naux, dtype=torch.float32, device=dev) for _ in range(n)],
+        devs = {fkey: [torch.empty(fshape, dtype=ftype, device=dev) for _ in range(n)]}
+        devs.update(aux=[torch.empty(naux, dtype=torch.float32, device=dev) for _ in range(n)],
                     info=[torch.empty(B, N_INFO, dtype=torch.int32, device=dev) for _ in range(n)])
         lut = torch.from_numpy(LUT).to(dev)
         mean = den = None
         if self.ds.states_mean is not None and S:
             mean = torch.from_numpy(self.ds.states_mean).to(dev)
             den = torch.from_numpy(self.ds.states_den).to(dev)
-        self._tables = None
-        if (H, W) != (self.ds.img_sz, self.ds.img_sz):
+        self._tables = self._topdown = None
+        if top:
+            self._topdown = topdown_device_assets(self.ds.topdown, self.ds.img_sz, dev)
+        elif (H, W) != (self.ds.img_sz, self.ds.img_sz):
             self._tables = tuple(torch.from_numpy(t).to(dev) for t in resize_tables(H, W, self.ds.img_sz))
         self._bufs = (pin, devs, lut, mean, den, _Streams(dev, n))
 
@@ -460,8 +640,9 @@ class HostFedLoader:
         pin, _, _, _, _, st = self._bufs
         st.copy_done[slot].synchronize()              # rule 1: the slot's previous upload has completed (a worker thread waits)
         item = self.ds.item(index, item_rng(self.seed, cycle, pos))
-        pack_item(item, j, pin["frames"][slot].numpy(), pin["aux"][slot].numpy(), pin["info"][slot].numpy(), self.B, self.ds.T,
-                  self.S, self.A)
+        fkey = "coords" if self.ds.topdown is not None else "frames"
+        pack_item(item, j, pin[fkey][slot].numpy(), pin["aux"][slot].numpy(), pin["info"][slot].numpy(), self.B, self.ds.T,
+                  self.S, self.A, topdown=self.ds.topdown)
 
     def _submit(self, slot, batch):
         return [self.pool.submit(self._fill_item, slot, j, i, p, c) for j, (i, p, c) in enumerate(batch)]
@@ -470,7 +651,7 @@ class HostFedLoader:
         pin, devs, _, _, _, st = self._bufs
         with torch.cuda.stream(st.copy):
             st.copy.wait_event(st.assembled[slot])    # rule 2: the assembly that read this device slot has run
-            for k in ("frames", "aux", "info"):
+            for k in pin:
                 devs[k][slot].copy_(pin[k][slot], non_blocking=True)
             st.copy_done[slot].record(st.copy)
 
@@ -487,7 +668,10 @@ class HostFedLoader:
             out["traj_seq_states"] = ib("traj_seq_states", (B, T, S))
         if A:
             out["actions"] = ib("actions", (B, T - 1, A))
-        if self._tables is None:
+        if self._topdown is not None:
+            topdown_assemble_into(m.lib, self._topdown, devs["coords"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out,
+                                  S, A, caller.cuda_stream)
+        elif self._tables is None:
             assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out, S, A, caller.cuda_stream)
         else:
             resize_assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, self._tables, mean, den, out,
