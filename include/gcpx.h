@@ -783,6 +783,11 @@ int gcpx_split_pack_group2(const gcpx_split_pack_desc* tab, int32_t nprob, uint3
    and -W2 (on the clamped row below).  w: dev [Cout][Cin][3][3]; out: dev f32 [24][Cout][Cin], set t = py 9 + dyl 3 + tx for
    t < 18, 18 + tx = -W0[tx], 21 + tx = -W2[tx]; sums formed in float64 in tap-row order (bit-identical to packing.fold_up_weights). */
 int gcpx_fold_upsample_weights(const float* w, int32_t Cout, int32_t Cin, float* out, void* stream);
+/* The optimizer state is four floats: state[0] = step counter, state[1] = this step's gradient-clipping coefficient (0 = unset = 1),
+   state[2] = the norm gcpx_grad_clip_coef measured, state[3] = the GATE.  With state[3] != 0 every step entry point below
+   (gcpx_radam_step, gcpx_optim_step, gcpx_optim_range, whatever kind and tick) returns at kernel entry: theta, m, v and state[0] keep
+   their bits.  gcpx_grad_health writes the gate (1 = this step's gradient or loss is not finite, 0 = clean) on every call; a caller
+   without a guard leaves it 0, and every result is then what it was before the slot had a meaning. */
 /* RAdam (Liu et al. 2019; blox.torch.radam.RAdam as used by gcp_builder.py:178-179): state[0] = step counter (float),
    incremented by this call; rectified update when the variance is tractable (rho_t > 5), momentum SGD otherwise */
 int gcpx_radam_step(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, float* state, int64_t n, float lr,
@@ -1095,6 +1100,26 @@ int gcpx_grad_segment_norms(const float* grad, int64_t n, const gcpx_grad_chunk*
                             float* stats, void* stream);
 int gcpx_kl_layerwise(const float* qz, const float* pz, int32_t B, int32_t L, int32_t nz, int64_t batch_stride, int64_t node_stride,
                       float free_nats, float* node_v, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Training guard (video-gcp_amd/health.py; csrc/train_stats.hip).
+ *
+ * gcpx_grad_health: NanGradHook (base_trainer.py:20-66: every parameter's gradient is tested between backward() and optimizer.step(),
+ *   the bad ones are named and training stops before the weights are touched) and the NaN total loss of base_gcp.py:302-303, on the
+ *   device.  x: a flat f32 vector of n < 2^31 elements, walked through the tables of gcpx_grad_segment_norms (chunks, seg_chunk0: only
+ *   the elements the chunks name are read; a chunk outside [0, n) or longer than GCPX_GRAD_NORM_CHUNK is skipped).  extra: n_extra
+ *   device scalars tested beside it (the loss terms and their total), or NULL / 0.
+ *   An element is classified by its bits: exponent all ones and mantissa != 0 -> NaN (either sign, any payload), exponent all ones and
+ *   mantissa 0 -> +Inf or -Inf by the sign; everything else, denormals, -0 and +-FLT_MAX included, is finite.
+ *   seg_bad [n_seg][3] = NaN, +Inf, -Inf elements of every segment.  summary [8]: [0..2] their totals, [3] number of segments with a
+ *   count > 0, [4] the first such segment or -1, [5] number of extra scalars that are NaN or +-Inf, [6] the verdict: 1 when [3] or [5]
+ *   is > 0, else 0, [7] a running count: incremented by the verdict on every call (the caller zeroes it once).
+ *   gate: NULL, or a float that receives verdict ? 1 : 0 on EVERY call (a clean call re-opens it): slot 3 of the optimizer state.
+ *   partial: caller's scratch of n_partial >= 3 * n_chunks int32.  Two launches on `stream`, no atomic, nothing allocated, nothing
+ *   synchronises; integer sums, so the result does not depend on the schedule. */
+int gcpx_grad_health(const float* x, int64_t n, const gcpx_grad_chunk* chunks, int32_t n_chunks, const int32_t* seg_chunk0, int32_t n_seg,
+                     const float* extra, int32_t n_extra, int32_t* partial, int64_t n_partial, int32_t* seg_bad, int32_t* summary,
+                     float* gate, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,8 @@ def checkpoint_name(epoch):
     return f"weights_ep{epoch}.pth"
 
 
-def save_checkpoint(model, folder, epoch, global_step=0, optimizer_state=None):
+def save_checkpoint(model, folder, epoch, global_step=0, optimizer_state=None, name=None):
+    """name: the file's name in `folder` instead of weights_ep{epoch}.pth (the guard's nan_debug_ckpt.pth, base_trainer.py:62-66)"""
     os.makedirs(folder, exist_ok=True)
     state = {"epoch": epoch, "global_step": global_step,
              "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
@@ -26,7 +27,7 @@ def save_checkpoint(model, folder, epoch, global_step=0, optimizer_state=None):
     rng = model.rng_state() if hasattr(model, "rng_state") else None
     if rng is not None:
         state["rng_state"] = rng
-    path = os.path.join(folder, checkpoint_name(epoch))
+    path = os.path.join(folder, checkpoint_name(epoch) if name is None else name)
     torch.save(state, path)
     return path
 

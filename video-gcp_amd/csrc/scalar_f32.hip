@@ -317,6 +317,7 @@ __global__ void __launch_bounds__(256) radam_kernel(float* __restrict__ theta, c
                                                     float* __restrict__ m, float* __restrict__ v, const float* __restrict__ state,
                                                     const long long n, const float lr, const float beta1, const float beta2,
                                                     const float eps, const float grad_scale) {
+    if (state[3] != 0.f) return;                    // the gate (gcpx_grad_health): this step's gradient is not to be applied
     const RadamCoef c = radam_coef(state, beta1, beta2, grad_scale);
     const long long stride = (long long)gridDim.x * 256, first = (long long)blockIdx.x * 256 + threadIdx.x;
     long long done = 0;
@@ -350,10 +351,16 @@ __global__ void __launch_bounds__(256) radam_kernel(float* __restrict__ theta, c
     for (long long i = done + first; i < n; i += stride) radam_one(theta[i], grad[i], m[i], v[i], c, lr, beta1, beta2, eps);
 }
 
-__global__ void radam_tick_kernel(float* state) { state[0] += 1.f; }
+// state[3] is the gate: written by gcpx_grad_health (1 = the step's gradient or loss is not finite), 0 otherwise.  Closed, every step
+// kernel and the tick return at entry -- the branch is uniform over the launch -- and theta, the moments and the counter keep their bits.
+__global__ void radam_tick_kernel(float* state) {
+    if (state[3] != 0.f) return;
+    state[0] += 1.f;
+}
 
 // The trainer's other optimizers (gcp_builder.py:174-186: 'adam', 'rmsprop', 'sgd' as torch.optim defines them) and the optional
-// gradient clipping by global norm.  state[0] = step counter, state[1] = clip coefficient of this step (1 when clipping is off).
+// gradient clipping by global norm.  state[0] = step counter, state[1] = clip coefficient of this step (1 when clipping is off),
+// state[2] = the clipped norm, state[3] = the gate.
 //   adam:    m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  theta -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //   rmsprop: v = alpha v + (1 - alpha) g^2;  d = g / (sqrt(v) + eps);  momentum > 0: m = momentum m + d, theta -= lr m;  else theta -= lr d
 //   sgd:     momentum > 0: m = momentum m + g (m = g at the first step), theta -= lr m;  else theta -= lr g
@@ -361,6 +368,7 @@ __global__ void __launch_bounds__(256) optim_kernel(float* __restrict__ theta, c
                                                     float* __restrict__ v, const float* __restrict__ state, const long long n,
                                                     const int kind, const float lr, const float p1, const float p2, const float eps,
                                                     const float grad_scale) {
+    if (state[3] != 0.f) return;                    // the gate, as in radam_kernel
     const float t = state[0] + 1.f;
     const float gs = grad_scale * (state[1] > 0.f ? state[1] : 1.f);
     const float bc1 = 1.f - powf(p1, t), bc2s = sqrtf(1.f - powf(p2, t));

@@ -3,8 +3,10 @@
 //   gcpx_grad_segment_norms   log_gradients (base_model.py:139-146): torch.norm(p.grad) of every parameter, their mean and maximum, over
 //                             the trainer's flat gradient vector
 //   gcpx_kl_layerwise         TreeModule._log_outputs (tree_module.py:159-169): the KL error matrix averaged per tree level
+// and the training guard's scan over the same tables (further down):
+//   gcpx_grad_health          NanGradHook (base_trainer.py:20-66): NaN / +Inf / -Inf counts per parameter, the verdict, the optimizer's gate
 //
-// Both are deterministic and bit-repeatable: every sum has a fixed shape, there is no atomic.
+// All are deterministic and bit-repeatable: every sum has a fixed shape, there is no atomic.
 //
 // Gradient norms.  The host cuts every counted segment into chunks of at most kChunk elements (scalar_log.grad_tables); stage 1 runs one
 // workgroup per chunk.  A thread adds the squares of at most kSerial elements into one f32 accumulator (fmaf: one rounding per element),
@@ -209,6 +211,140 @@ __global__ void __launch_bounds__(1024) kl_level_mean_kernel(const float* __rest
     if (lane == 0) out[l] = acc / (float)cnt;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Training guard (NanGradHook, base_trainer.py:20-66; the NaN total loss of base_gcp.py:302-303): gcpx_grad_health counts the NaN, +Inf
+// and -Inf elements of every segment of a flat f32 vector, through the tables of the norms kernel above and in its shape.  An element
+// is classified by its bit pattern alone (integer compares on the 32 bits: exponent all ones, mantissa zero or not, the sign), so
+// denormals, -0 and +-FLT_MAX are finite whatever the float mode of the wavefront.  Stage 1, one workgroup per chunk: three integer
+// counters per thread, the wavefront butterfly, the four wavefronts in LDS.  Stage 2, one workgroup: a thread sums the chunks of its
+// segments, the workgroup reduces the totals, the number of bad segments and the first of them, thread 0 writes the summary and the
+// gate.  Integer sums: the result does not depend on the schedule, there is no atomic.
+// ---------------------------------------------------------------------------------------------------
+struct BadCount { int nan, pinf, ninf; };
+
+__device__ __forceinline__ void classify(const uint32_t u, BadCount& c) {
+    c.nan += (u & 0x7fffffffu) > 0x7f800000u;
+    c.pinf += u == 0x7f800000u;
+    c.ninf += u == 0xff800000u;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+__global__ void __launch_bounds__(kThreads) chunk_health_kernel(const uint32_t* __restrict__ x, const long long n,
+                                                                const gcpx_grad_chunk* __restrict__ chunks,
+                                                                int32_t* __restrict__ partial) {
+    __shared__ int red[kThreads / 64][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const gcpx_grad_chunk c = chunks[blockIdx.x];
+    BadCount bc = {0, 0, 0};
+    if (c.first >= 0 && c.length > 0 && c.length <= kChunk && c.first + c.length <= n) {      // (uniform over the workgroup)
+        const uint32_t* g = x + c.first;
+        const int len = c.length;
+        if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+            const int nvec = len >> 2;
+            const uint4* g4 = reinterpret_cast<const uint4*>(g);
+            if (nvec == kChunk / 4) {                 // a full chunk: a fixed trip count, every load of the thread in flight at once
+                uint4 v[kChunk / 4 / kThreads];
+#pragma unroll
+                for (int i = 0; i < kChunk / 4 / kThreads; ++i) v[i] = g4[tid + i * kThreads];
+#pragma unroll
+                for (int i = 0; i < kChunk / 4 / kThreads; ++i) {
+                    classify(v[i].x, bc);
+                    classify(v[i].y, bc);
+                    classify(v[i].z, bc);
+                    classify(v[i].w, bc);
+                }
+            } else {
+                for (int i = tid; i < nvec; i += kThreads) {
+                    const uint4 v = g4[i];
+                    classify(v.x, bc);
+                    classify(v.y, bc);
+                    classify(v.z, bc);
+                    classify(v.w, bc);
+                }
+                const int e = 4 * nvec + tid;         // the segment's tail: len % 4 single elements
+                if (e < len) classify(g[e], bc);
+            }
+        } else {
+            for (int e = tid; e < len; e += kThreads) classify(g[e], bc);
+        }
+    }
+    bc.nan = wave_sum_int(bc.nan);
+    bc.pinf = wave_sum_int(bc.pinf);
+    bc.ninf = wave_sum_int(bc.ninf);
+    if (lane == 0) {
+        red[wave][0] = bc.nan;
+        red[wave][1] = bc.pinf;
+        red[wave][2] = bc.ninf;
+    }
+    __syncthreads();
+    if (tid < 3) partial[3 * (size_t)blockIdx.x + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+__global__ void __launch_bounds__(kThreads2) segment_health_kernel(const int32_t* __restrict__ partial, const int n_chunks,
+                                                                   const int32_t* __restrict__ seg_chunk0, const int n_seg,
+                                                                   const uint32_t* __restrict__ extra, const int n_extra,
+                                                                   int32_t* __restrict__ seg_bad, int32_t* __restrict__ summary,
+                                                                   float* __restrict__ gate) {
+    __shared__ int red[kThreads2 / 64][6];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // this thread's share: [0..2] element counts, [3] bad segments, [4] bad extra scalars; the first bad segment apart (a minimum)
+    int acc[5] = {0, 0, 0, 0, 0};
+    int first = 0x7fffffff;
+    for (int s = tid; s < n_seg; s += kThreads2) {
+        const int c0 = max(seg_chunk0[s], 0), c1 = min(seg_chunk0[s + 1], n_chunks);
+        int q[3] = {0, 0, 0};
+        for (int c = c0; c < c1; ++c) {
+            q[0] += partial[3 * (size_t)c];
+            q[1] += partial[3 * (size_t)c + 1];
+            q[2] += partial[3 * (size_t)c + 2];
+        }
+        seg_bad[3 * (size_t)s] = q[0];
+        seg_bad[3 * (size_t)s + 1] = q[1];
+        seg_bad[3 * (size_t)s + 2] = q[2];
+        acc[0] += q[0];
+        acc[1] += q[1];
+        acc[2] += q[2];
+        if (q[0] | q[1] | q[2]) {                     // (counts are >= 0)
+            acc[3] += 1;
+            first = min(first, s);
+        }
+    }
+    for (int e = tid; e < n_extra; e += kThreads2) acc[4] += (extra[e] & 0x7f800000u) == 0x7f800000u;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) acc[k] = wave_sum_int(acc[k]);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) first = min(first, __shfl_xor(first, m));
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) red[wave][k] = acc[k];
+        red[wave][5] = first;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int tot[5] = {0, 0, 0, 0, 0};
+        int f = 0x7fffffff;
+        for (int w = 0; w < kThreads2 / 64; ++w) {
+            for (int k = 0; k < 5; ++k) tot[k] += red[w][k];
+            f = min(f, red[w][5]);
+        }
+        const int verdict = (tot[3] > 0 || tot[4] > 0) ? 1 : 0;
+        summary[0] = tot[0];
+        summary[1] = tot[1];
+        summary[2] = tot[2];
+        summary[3] = tot[3];
+        summary[4] = tot[3] > 0 ? f : -1;
+        summary[5] = tot[4];
+        summary[6] = verdict;
+        summary[7] += verdict;
+        if (gate) gate[0] = verdict ? 1.f : 0.f;
+    }
+}
+
 }  // namespace
 
 extern "C" int gcpx_grad_segment_norms(const float* grad, int64_t n, const gcpx_grad_chunk* chunks, int32_t n_chunks,
@@ -223,6 +359,25 @@ extern "C" int gcpx_grad_segment_norms(const float* grad, int64_t n, const gcpx_
                        n_chunks);
     hipLaunchKernelGGL(segment_norm_kernel, dim3(1), dim3(kThreads2), 0, stream, partial, n_chunks, seg_chunk0, n_seg, grad_scale,
                        clip_coef, seg_norm, stats);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_grad_health(const float* x, int64_t n, const gcpx_grad_chunk* chunks, int32_t n_chunks, const int32_t* seg_chunk0,
+                                int32_t n_seg, const float* extra, int32_t n_extra, int32_t* partial, int64_t n_partial, int32_t* seg_bad,
+                                int32_t* summary, float* gate, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(x && chunks && seg_chunk0 && partial && seg_bad && summary, "null pointer");
+    GCPX_CHECK_ARG(n > 0 && n_chunks > 0 && n_seg > 0 && n_seg <= n_chunks, "sizes must be positive, and every segment has a chunk");
+    GCPX_CHECK_ARG(n < (1ll << 31), "more than 2^31 - 1 elements: the counts are 32-bit");
+    GCPX_CHECK_ARG(n_extra >= 0 && (n_extra == 0 || extra), "n_extra scalars need a pointer");
+    GCPX_CHECK_ARG(n_partial >= 3 * (int64_t)n_chunks, "partial must hold 3 * n_chunks integers");
+    GCPX_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(chunks) & 7) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(extra) | reinterpret_cast<uintptr_t>(gate)) & 3) == 0, "misaligned pointer");
+    hipLaunchKernelGGL(chunk_health_kernel, dim3((unsigned)n_chunks), dim3(kThreads), 0, stream, reinterpret_cast<const uint32_t*>(x),
+                       (long long)n, chunks, partial);
+    hipLaunchKernelGGL(segment_health_kernel, dim3(1), dim3(kThreads2), 0, stream, partial, n_chunks, seg_chunk0, n_seg,
+                       reinterpret_cast<const uint32_t*>(extra), n_extra, seg_bad, summary, gate);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

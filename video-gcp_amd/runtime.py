@@ -265,6 +265,7 @@ SYMBOLS = [
     ("gcpx_panel_compose", C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp]),
     ("gcpx_grad_segment_norms", C.c_int, [vp, i64, vp, i32, vp, i32, C.c_float, vp, vp, i64, vp, vp, vp]),
     ("gcpx_kl_layerwise", C.c_int, [vp, vp, i32, i32, i32, i64, i64, C.c_float, vp, vp, vp]),
+    ("gcpx_grad_health", C.c_int, [vp, i64, vp, i32, vp, i32, vp, i32, vp, i64, vp, vp, vp, vp]),
 ]
 
 _lib = None

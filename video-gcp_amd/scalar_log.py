@@ -122,14 +122,15 @@ class ScalarLogger:
 
 
 # ---- gradient norms: the tables of gcpx_grad_segment_norms ----
-def grad_tables(poff, chunk=GRAD_NORM_CHUNK):
+def grad_tables(poff, chunk=GRAD_NORM_CHUNK, buffers=False):
     """(names, chunks, seg_chunk0) from a model's `_poff` {name: (offset, shape)}: the counted segments (parameters; buffers are left
     out by name, empty tensors have no norm) in layout order, each cut into pieces of at most `chunk` elements -- chunks: structured
-    array (first, seg, length) with the pieces of one segment adjacent; seg_chunk0 [n_seg + 1]: first chunk of every segment."""
+    array (first, seg, length) with the pieces of one segment adjacent; seg_chunk0 [n_seg + 1]: first chunk of every segment.
+    buffers=True keeps the buffers: the table of the weights themselves (health.py scans theta with it before a checkpoint)."""
     names, rows, seg_chunk0 = [], [], [0]
     for name, (off, shape) in poff.items():
         numel = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
-        if name.endswith(BUFFER_SUFFIXES) or numel == 0:
+        if (name.endswith(BUFFER_SUFFIXES) and not buffers) or numel == 0:
             continue
         s = len(names)
         names.append(name)

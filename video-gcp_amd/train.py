@@ -37,6 +37,14 @@ train.py:182-186).  After a validation: the averages of every term over its batc
 (train.py:229-230), the layer-wise KL of the last batch, and scalar_data.json is rewritten.  Under a process group the loss terms are
 rank 0's shard (the reference's DataParallel saw the whole batch); the gradient norms are of the all-reduced gradient, identical on
 every rank.  Deviation: the reference always logs; `--log_scalars` defaults to 0, and nothing then changes anywhere.
+Training guard: `--nan_guard raise|skip` tests every step's gradient and loss vector for NaN / +-Inf on the device, between the
+backward and the optimizer, and keeps a bad gradient out of the weights and moments (health.py; NanGradHook, base_trainer.py:20-66,
+gcp_builder.py:99-103; base_gcp.py:302-303).  `raise` stops as the reference does: rank 0 writes <path>/nan_debug_info.npz (the batch,
+the loss terms, end_ind, the bad and OK parameter names and counts, global_step, epoch) and <path>/nan_debug_ckpt.pth (the untouched
+weights and optimizer state, in the checkpoint format), prints the two lists and the run ends with NonFiniteGradients.  `skip` drops
+the step on the device without a sync and goes on; with --log_scalars 1 `gradients/skipped_steps_train` counts them, and the total is
+printed at the end.  Under either, a checkpoint is written only from finite parameters and running statistics.
+Deviation: the reference always installs its hook; `--nan_guard` defaults to off, and a plain run is what it was.
 """
 import argparse
 import json
@@ -74,6 +82,9 @@ def get_cmd_args(argv=None):
                    "default is 1)")
     p.add_argument("--log_scalars", default=0, type=int, help="if 1, writes loss terms, gradient norms and the layer-wise KL to "
                    "<path>/events (event file + scalar_data.json; the reference always does)")
+    p.add_argument("--nan_guard", default="off", choices=("off", "raise", "skip"), help="tests every gradient for NaN / Inf on the device "
+                   "before the optimizer applies it: 'raise' dumps the batch and a checkpoint and stops (the reference always does), "
+                   "'skip' drops the step and goes on")
     return p.parse_args(argv)
 
 
@@ -192,9 +203,13 @@ class ModelTrainer:
         self.model.reseed()                   # (a second trainer of the process seeded with the same value starts the same stream again)
         pg = torch.distributed.group.WORLD if self.world > 1 else None
         lr = conf.get("lr") if conf.get("lr") is not None else 1e-3
+        guard = getattr(args, "nan_guard", "off")
+        self.nan_guard = None if guard in (None, "off") else guard
+        guard_kw = {"nan_guard": self.nan_guard} if self.nan_guard else {}
         self.trainer = step_cls(self.model, lr=lr, betas=(conf.get("adam_beta", 0.9), 0.999), process_group=pg,
                                 optimizer=conf.get("optimizer", "radam"), momentum=conf.get("momentum", 0),
-                                gradient_clip=conf.get("gradient_clip"))                   # gcp_builder.py:174-186,255-263
+                                gradient_clip=conf.get("gradient_clip"), **guard_kw)       # gcp_builder.py:174-186,255-263
+        self._weight_health = None
         if self.data_dir and (train_loader is None or val_loader is None):
             # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val / test unshuffled
             reps = int(conf.get("epoch_cycles_train", 1))
@@ -240,6 +255,8 @@ class ModelTrainer:
             if self.scalar_log is not None:
                 self.scalar_log.dump_scalars()
                 self.scalar_log.close()
+            if self.nan_guard == "skip" and self.rank == 0 and self.trainer._health is not None:
+                print("[train] steps skipped for non-finite gradients: {}".format(int(self.trainer.health().summary[7])), flush=True)
 
     # ---- train.py:56-70, checkpoint_handler.py:31-74 ----
     def resume(self, ckpt, path=None):
@@ -271,8 +288,48 @@ class ModelTrainer:
     # ---- train.py:106-115 ----
     def save_checkpoint(self, epoch):
         from . import checkpoint as CK
+        if self.nan_guard:
+            self.check_weights()                       # never overwrite a good checkpoint with non-finite weights
         return CK.save_checkpoint(self.model, os.path.join(self.exp_path, "weights"), epoch, self.global_step,
                                   self.trainer.optimizer_state())
+
+    def check_weights(self):
+        """one gcpx_grad_health over theta -- parameters and BatchNorm running statistics -- and a sync: raises NonFiniteWeights when
+        anything in it is NaN or +-Inf (once per epoch, in front of save_checkpoint)"""
+        from .health import GradHealth, NonFiniteWeights
+        if self._weight_health is None:
+            self._weight_health = GradHealth(self.model, buffers=True)
+        h, stream = self._weight_health, torch.cuda.current_stream(self.device)
+        h.launch(self.model.lib, self.model.theta, None, None, stream.cuda_stream)
+        if h.read_summary(stream)[6]:
+            raise NonFiniteWeights(h.bad()[0])
+
+    def dump_nan_debug(self, err, inputs, epoch):
+        """NanGradHook's report (base_trainer.py:24-66): the two name lists, nan_debug_info.npz and nan_debug_ckpt.pth.  The reference
+        pickles every output tensor; here the outputs are the plan's device buffers (gigabytes at c2), so only end_ind goes along."""
+        import numpy as np
+        from . import checkpoint as CK
+        print("Detected NaN gradients, dumping data for diagnosis, ...", flush=True)
+        if not self.cmd_args.dont_save:
+            info = {"inputs/" + k: v.detach().cpu().numpy() for k, v in inputs.items() if torch.is_tensor(v)}
+            if err.outputs is not None:
+                for k, v in self.model.loss(inputs, err.outputs).items():
+                    v = v.value if isinstance(v, dict) else v
+                    info["losses/" + ("total" if k == "_total" else k)] = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v)
+                end_ind = err.outputs.get("end_ind")
+                if torch.is_tensor(end_ind):
+                    info["outputs/end_ind"] = end_ind.detach().cpu().numpy()
+            info["bad_parameters"] = np.array([b[0] for b in err.bad], dtype=str)
+            info["ok_parameters"] = np.array(list(err.ok), dtype=str)
+            info["bad_counts"] = np.array([b[1:] for b in err.bad], dtype=np.int64).reshape(len(err.bad), 3)
+            info["loss_nonfinite"] = np.int64(err.loss_nonfinite)
+            info["global_step"], info["epoch"] = np.int64(self.global_step), np.int64(epoch)
+            os.makedirs(self.exp_path, exist_ok=True)
+            np.savez(os.path.join(self.exp_path, "nan_debug_info.npz"), **info)
+            CK.save_checkpoint(self.model, self.exp_path, epoch, self.global_step, self.trainer.optimizer_state(),
+                               name="nan_debug_ckpt.pth")
+        print("nan gradients here: ", [b[0] for b in err.bad])                  # base_trainer.py:31-32
+        print("there parameters are OK: ", list(err.ok), flush=True)
 
     # ---- train.py:132-193 ----
     def train_epoch(self, epoch):
@@ -287,7 +344,13 @@ class ModelTrainer:
         for batch_idx, inputs in enumerate(self.train_loader):
             if slog is not None:
                 data_time, n_timed = data_time + time.time() - tick, n_timed + 1
-            out = self.trainer.step(inputs)            # zero_grad, forward, loss, backward, (all-reduce), optimizer.step
+            try:
+                out = self.trainer.step(inputs)        # zero_grad, forward, loss, backward, (all-reduce), optimizer.step
+            except ValueError as err:                  # --nan_guard raise: the reference's hook (gcp_builder.py:99-103)
+                from .health import NonFiniteGradients
+                if isinstance(err, NonFiniteGradients) and self.rank == 0:
+                    self.dump_nan_debug(err, inputs, epoch)
+                raise
             self.model.step()                          # train.py:163
             if self.log_images and self.global_step % images_interval == 0:          # train.py:125-126,170-172
                 self.image_files += self.model.log_outputs(out, inputs, None, self.global_step, True, "train")
@@ -310,12 +373,14 @@ class ModelTrainer:
         """the scalars of one logging step (base_model.py:86-108,139-146, train.py:170-186): loss terms, layer-wise KL, gradient norms
         (one launch behind the step, read back in one copy) and the two host clocks"""
         stats = self.trainer.gradient_stats().stats
+        if self.nan_guard == "skip":                   # the count of skipped steps rides in the same copy
+            stats = torch.cat([stats, self.trainer.health().summary[7:8].to(torch.float32)])
         losses = self.model.loss(inputs, out)
         losses["_total"] = total
         self.model.log_outputs(out, inputs, losses, self.global_step, False, "train")
-        mean, mx, _, nonfinite = stats.tolist()
+        mean, mx, _, nonfinite, *skipped = stats.tolist()
         for name, v in (("gradients/mean_norm", mean), ("gradients/max_norm", mx), ("gradients/nonfinite", nonfinite),
-                        ("time/batch", batch_time), ("time/data_load", data_time)):
+                        ("time/batch", batch_time), ("time/data_load", data_time)) + tuple(("gradients/skipped_steps", v) for v in skipped):
             self.scalar_log.log_scalar(v, name, self.global_step, "train")
         self.scalar_log.flush()
 

@@ -38,13 +38,22 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
     OPTIMIZERS = {"radam": 0, "adam": 1, "rmsprop": 2, "sgd": 3}
     _early_on, _caller, _slice_stream, last_bplan_caller_lane = False, None, None, False          # (see __init__: early_optimizer)
     _pending_slices = ()
+    NAN_GUARDS = (None, "raise", "skip")
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, optimizer="radam", momentum=0.0,
-                 gradient_clip=None):
+                 gradient_clip=None, nan_guard=None):
         """optimizer / momentum / gradient_clip: the trainer's `optimizer` ('radam' default, 'adam', 'rmsprop', 'sgd'), `momentum`
-        (RMSprop / SGD) and `gradient_clip` settings (gcp_builder.py:174-186,255-263)."""
+        (RMSprop / SGD) and `gradient_clip` settings (gcp_builder.py:174-186,255-263).
+        nan_guard: None (nothing is tested: the step as it always was), "raise" or "skip" -- the reference's NanGradHook
+        (base_trainer.py:20-66) as a device kernel between the backward and the optimizer (health.py): one gcpx_grad_health over the
+        whole (all-reduced) gradient and the loss vector writes the gate of the optimizer state, and the step kernels and the tick
+        return at entry when it is closed.  "raise": step() then reads the 32-byte summary and raises NonFiniteGradients; "skip": no
+        sync, training goes on, health() holds the counts.  Either way a non-finite gradient never reaches theta or the moments."""
         if optimizer not in self.OPTIMIZERS:
             raise ValueError("Optimizer '{}' not supported!".format(optimizer))          # gcp_builder.py:185
+        if nan_guard not in self.NAN_GUARDS:
+            raise ValueError("nan_guard must be None, 'raise' or 'skip', not {!r}".format(nan_guard))
+        self.nan_guard, self._health, self._health_extra = nan_guard, None, None
         self.optimizer, self.momentum, self.gradient_clip = optimizer, float(momentum), gradient_clip
         self._clip_state_dirty, self._clip_part = True, None      # the clip coefficient slot of the optimizer state / its scratch
         hp = model._hp
@@ -158,6 +167,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         out = m.forward(inputs, "train", noise)
         if "losses" not in out.raw:
             raise ValueError("the training step needs traj_seq and pad_mask")
+        if self.nan_guard:
+            self._health_extra = out.raw["losses"]        # the device loss vector: tested beside the gradient (base_gcp.py:302-303)
         key = [k for k, v in m._plans.items() if v[1].outs is out.raw][0]
         if key not in self._bplans:
             self._bplans[key] = self._build_backward(m._plans[key][1])
@@ -280,15 +291,25 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
                 self._lanes.append(sp)
         return self._lanes
 
-    def optimizer_step(self):
+    def optimizer_step(self, outputs=None):
         """The configured optimizer (RAdam / Adam / RMSprop / SGD, optional clip_grad_norm_) on the flat vectors + one re-pack gather
-        (gcp_builder.py:88-89,178-179)."""
+        (gcp_builder.py:88-89,178-179).  Under a nan_guard the gradient's health check goes first and gates all of it; with
+        nan_guard="raise" the call ends by reading the verdict (`outputs`: what the exception carries as .outputs)."""
+        self._optimizer_step()
+        if self.nan_guard == "raise":
+            self._raise_if_bad(outputs)
+
+    def _optimizer_step(self):
         m = self.m
         st = torch.cuda.current_stream(m.device).cuda_stream
         scale = 1.0
         if self.buckets is not None:
             # the tree-level buckets were started during the backward; the last one (conv stacks, heads, level 0) goes now
             scale = self.buckets.finish()
+        if self.nan_guard:
+            # the whole gradient is final here (data-parallel: the ranks' sum, the same bits on every rank, so every rank reaches the
+            # same verdict without a further collective); the verdict lands in opt_state[3] before anything below reads it
+            self._grad_health().launch(m.lib, self.grad, self._health_extra, self.opt_state.data_ptr() + 12, st)
         applied, self._applied = self._applied, set()
         if applied:
             # step(): those slices were updated during the backward; the others (at least "rest") follow here, the last one ticks
@@ -326,7 +347,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         m.repack(st)
 
     def step(self, inputs, noise=None):
-        self._early_on = (self.early_optimizer and not self.gradient_clip and len(self._ranges) > 1 and
+        # (no early slices under a nan_guard either: the verdict needs the whole gradient, as the clipping norm does)
+        self._early_on = (self.early_optimizer and not self.gradient_clip and not self.nan_guard and len(self._ranges) > 1 and
                           not (self.m.use_graph and self.backward_graph))
         if self._early_on and self._clip_state_dirty:
             self.opt_state[1:2].zero_()          # the early slices read the clip coefficient: it must be 0 (unset) before they run
@@ -335,19 +357,50 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             out = self.backward(inputs, noise)
         finally:
             self._early_on = False
-        self.optimizer_step()
+        self.optimizer_step(out)
         return out
+
+    # ---- the training guard (health.py) ----
+    def _grad_health(self):
+        if self._health is None:
+            from .health import GradHealth
+            self._health = GradHealth(self.m)
+        return self._health
+
+    def _raise_if_bad(self, outputs):
+        """nan_guard="raise": health check, gated step and re-pack are enqueued; copy the summary behind them and wait -- the device
+        works while the host does.  A verdict of 1 raises; the device has already skipped the update."""
+        from .health import NonFiniteGradients
+        h = self._grad_health()
+        summary = h.read_summary(torch.cuda.current_stream(self.m.device))
+        if summary[6]:
+            bad, ok = h.bad()
+            raise NonFiniteGradients(bad, ok, int(summary[5]), outputs)
+
+    def health(self):
+        """the guard's counts of the last step, as device tensors and without a sync (like gradient_stats()):
+        Outputs(names, seg_bad [len(names), 3] = NaN, +Inf, -Inf elements per parameter, summary [8] int32: totals, number of bad
+        parameters, the first of them or -1, non-finite loss entries, this step's verdict, [7] the number of skipped steps so far)"""
+        from .plan_ops import Outputs
+        if not self.nan_guard:
+            raise ValueError("this trainer runs without a nan_guard")
+        h = self._grad_health()
+        return Outputs(names=h.names, seg_bad=h.seg_bad, summary=h.summary)
 
     def optimizer_state(self):
         """optimizer.state_dict() counterpart (train.py:111): flat first / second moments + step counter"""
+        state = self.opt_state.detach().cpu()
+        state[3] = 0.0                        # the gate belongs to the step that set it: a resumed trainer must step
         return {"exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu(),
-                "state": self.opt_state.detach().cpu(), "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
+                "state": state, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
                 "optimizer": self.optimizer, "momentum": self.momentum, "gradient_clip": self.gradient_clip}
 
     def load_optimizer_state(self, st):
         self.exp_avg.copy_(st["exp_avg"])
         self.exp_avg_sq.copy_(st["exp_avg_sq"])
-        self.opt_state.copy_(st["state"])
+        state = torch.as_tensor(st["state"]).detach().to("cpu", torch.float32, copy=True)
+        state[3] = 0.0                        # a stored gate must not outlive its run (as the clip coefficient below)
+        self.opt_state.copy_(state)
         self.lr, self.betas, self.eps = st["lr"], tuple(st["betas"]), st["eps"]
         if st.get("optimizer", self.optimizer) != self.optimizer:
             raise ValueError(f"checkpoint holds the state of optimizer '{st['optimizer']}', this trainer runs '{self.optimizer}'")
