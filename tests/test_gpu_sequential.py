@@ -131,33 +131,13 @@ def test_sequential_gradients_match_autograd_free_nats_burn_in():
     assert not bad, bad[:10]
 
 
-def test_sequential_cell_backward_in_the_gemm_epilogue_gives_the_same_gradient():
-    """fuse_lstm_bwd (off by default: it does not pay, NOTEBOOK round 4): every LSTM cell backward of the 79-step chains rides in the
-    epilogue of the data-gradient GEMM that feeds it (gcpx_gemm_args.lstm_bwd) — the same device function on the same values: the
-    gradient of the plain plan, bit for bit."""
-    hp, sd, model, tr = _train_setup(False)
-    _, _, model2, tr2 = _train_setup(False)
-    tr2.fuse_lstm_bwd = True
-    inputs, noise, _ = make_inputs(hp, seed=7, variant="B")
-    noise = noise[:, :hp.max_seq_len - 1].contiguous()
-    dev_in = {k: v.cuda() for k, v in inputs.items()}
-    tr.backward(dev_in, noise.cuda())
-    tr2.backward(dev_in, noise.cuda())
-    torch.cuda.synchronize()
-    n1 = sum(1 for op in tr.last_bplan.ops if not op[0].startswith("@"))
-    n2 = sum(1 for op in tr2.last_bplan.ops if not op[0].startswith("@"))
-    assert n1 - n2 >= 3 * (hp.max_seq_len - 1), (n1, n2)
-    assert torch.equal(tr.grad, tr2.grad)
-
-
-@pytest.mark.parametrize("env", [{"GCPX_SEQ_CHAINS": "serial"}, {"GCPX_SEQ_CHAINS": "overlap"}, {"GCPX_SEQ_CHAINS": "lockstep3"}, {"GCPX_SEQ_LIVE_FOLDS": "0"},
-                                 {"GCPX_BWD_SEGMENTS": "3"}, {"GCPX_BWD_SEGMENTS": "-1"}])
+@pytest.mark.parametrize("env", [{"GCPX_SEQ_LIVE_FOLDS": "0"}, {"GCPX_BWD_SEGMENTS": "3"}, {"GCPX_BWD_SEGMENTS": "-1"}],
+                         ids=["live_folds_off", "segments_3", "segments_none"])
 def test_sequential_backward_schedules_agree(env, monkeypatch):
-    """The default schedule of the flat model's training step (prior chain ahead on its lane as small graphs, generator step t and
-    inference step t + 1 in the same grouped launches, folded 3-launch forward steps) against the other ones the switches select: the
-    round-5 serial order, three lanes with step-by-step events, the unfolded training forward, every run of launches as a graph / none.
-    Same mathematics, different summation order inside the `out` data-gradient GEMM (the tripled weights) and a float64-folded
-    forward: 2e-4 of each gradient's max-abs; the graph switches replay the very same launches: bit for bit."""
+    """The flat model's training step (prior chain ahead on its lane as small graphs, generator step t and inference step t + 1 in the
+    same grouped launches, folded 3-launch forward steps) against what the remaining switches select: the unfolded training forward,
+    every run of launches as a graph / none.  Same mathematics behind a float64-folded forward: 2e-4 of each gradient's max-abs; the
+    graph switches replay the very same launches: bit for bit."""
     hp, sd, model, tr = _train_setup(False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)

@@ -1,4 +1,4 @@
-"""gcp_sequential training step at the c2 shapes: `GCPX_SEQ_CHAINS=serial|overlap python tools/r06/time_seq_train.py [width]`."""
+"""gcp_sequential training step at the c2 shapes: `python tools/r06/time_seq_train.py [width]`."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -21,4 +21,4 @@ for rep in range(3):
     for _ in range(10):
         h0 = time.perf_counter(); tr.step(dev); th += time.perf_counter() - h0
     torch.cuda.synchronize()
-    print(f"GCPX_SEQ_CHAINS={os.environ.get('GCPX_SEQ_CHAINS', 'lockstep')} width {hp.nz_mid_lstm}: {(time.perf_counter() - t0) * 100:.2f} ms / step (host {th * 100:.2f})", flush=True)
+    print(f"width {hp.nz_mid_lstm}: {(time.perf_counter() - t0) * 100:.2f} ms / step (host {th * 100:.2f})", flush=True)

@@ -15,8 +15,6 @@ hp = V.config(os.environ.get("CONFIG", "c2"))
 model = GCPTreeModel(hp, device="cuda")
 tr = GCPTrainStep(model)
 model.use_graph = os.environ.get('NOGRAPH') is None
-tr.backward_graph = os.environ.get('BGRAPH') is not None
-tr.side_priority = int(os.environ.get('SIDEPRIO', '0'))
 if os.environ.get('NOSIDE'):
     tr.side_lanes = False
 inputs, noise, _ = make_inputs(hp, seed=0, variant="A")

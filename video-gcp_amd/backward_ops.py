@@ -241,7 +241,7 @@ class BackwardOpsMixin:
     def _dense(self, ptr, ld, width, M):
         return self.m._rowsrc(ptr, M * ld, ld, width)
 
-    def _bn_bwd(self, plan, tag, bn, da, ldc, c_off, up, r, F, Hh, Ww, add=None, fused=None, defer_affine=False, skip=None):
+    def _bn_bwd(self, plan, tag, bn, da, ldc, c_off, up, r, F, Hh, Ww, add=None, fused=None, skip=None):
         """activation + BatchNorm backward of one conv block: returns the buffer holding d(raw conv output).
         fused = (dy, partial sums [nb][2][C], nb): the data-gradient conv that produced `da` already applied the activation's derivative
         and left the statistics (gcpx_conv_args.bwd_r): only the BatchNorm half remains, in place.
@@ -268,18 +268,9 @@ class BackwardOpsMixin:
                 plan.add(f"bw.act:{tag}", lib.gcpx_act_bwd, C.byref(a))
         coef = m._buf(f"bw.coef:{tag}", (3, Cc))
         pre = bn["prefix"]
-        if defer_affine:
-            # this chain runs beside other chains that accumulate into the same d gamma / d beta (the three encoder passes): the sums go
-            # to a scratch pair and are added with the pass's weight gradients, in order on one lane
-            dgb = m._buf(f"bw.dgb:{tag}", (2, Cc))
-            plan.add(f"bw.bnfin:{tag}", lib.gcpx_bn_bwd_finalize, st.data_ptr(), nb, Cc, C.c_double(float(F * Hh * Ww)),
-                     m.sd[f"{pre}.weight"].data_ptr(), bn["rstd"].data_ptr(), coef.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(), 0)
-            self._side(plan, f"bw.bnacc:{tag}.g", lib.gcpx_reduce_partials, dgb[0].data_ptr(), 1, Cc, Cc, self.g(f"{pre}.weight"), 1)
-            self._side(plan, f"bw.bnacc:{tag}.b", lib.gcpx_reduce_partials, dgb[1].data_ptr(), 1, Cc, Cc, self.g(f"{pre}.bias"), 1)
-        else:
-            plan.add(f"bw.bnfin:{tag}", lib.gcpx_bn_bwd_finalize, st.data_ptr(), nb, Cc, C.c_double(float(F * Hh * Ww)),
-                     m.sd[f"{pre}.weight"].data_ptr(), bn["rstd"].data_ptr(), coef.data_ptr(), self.g(f"{pre}.weight"),
-                     self.g(f"{pre}.bias"), 1)
+        plan.add(f"bw.bnfin:{tag}", lib.gcpx_bn_bwd_finalize, st.data_ptr(), nb, Cc, C.c_double(float(F * Hh * Ww)),
+                 m.sd[f"{pre}.weight"].data_ptr(), bn["rstd"].data_ptr(), coef.data_ptr(), self.g(f"{pre}.weight"),
+                 self.g(f"{pre}.bias"), 1)
         plan.add(f"bw.bnapply:{tag}", lib.gcpx_bn_bwd_apply, dy.data_ptr(), r.data_ptr(), bn["mean"].data_ptr(),
                  bn["rstd"].data_ptr(), coef.data_ptr(), F * Hh * Ww * Cc, Cc)
         return dy

@@ -168,8 +168,7 @@ class BackwardPlanMixin:
 
         # ---- tree levels, leaves first (tree_utils.py:21-44 backward) ----
         MERGE_LANE = 1 + self.n_side                    # the caller's stream (backward(): the last entry of the stream list)
-        merge_lane = (self.merge_on_caller_lane and self.side_lanes and bool(hp.tree_lstm) and not self.parallel_level_chains and
-                      not (m.use_graph and self.backward_graph))
+        merge_lane = self.merge_on_caller_lane and self.side_lanes and bool(hp.tree_lstm)
         plan.rec["caller_lane"] = merge_lane
         merge_pending = False
         pid = hp.pred_inp_dim
@@ -212,25 +211,16 @@ class BackwardPlanMixin:
                     a.M, a.H, a.rpb = M, H, n
                     plan.keep.append(a)
                     cells.append(a)
-                # each layer's cell backward rides in the epilogue of the GEMM that produces its d h (fuse_lstm_bwd): 3 launches per level
-                # less on the chain
-                fuse_cell = self.fuse_lstm_bwd
+                # The cell backward is a launch of its own: in the epilogue of the GEMM that produces its d h (gcpx_gemm_args.lstm_bwd) its
+                # dependent loads sit behind the K loop of a launch with 32 .. 64 workgroups (c2 step 13.07 ms against 12.91)
+                self._dgemm(plan, f"out{l}", [m._rowsrc(dEn, PS * nz, 2 * s * nz, nz)], M, H, n, Wt["out.wT"], dxt.data_ptr(), n * H, H)
                 if merge_pending:
                     # the level above wrote this level's d state (dHid) on the merge lane: the first cell backward reads it
-                    if not fuse_cell:
-                        self._dgemm(plan, f"out{l}", [m._rowsrc(dEn, PS * nz, 2 * s * nz, nz)], M, H, n, Wt["out.wT"], dxt.data_ptr(), n * H, H)
                     plan.wait(0, MERGE_LANE)
                     merge_pending = False
-                    if fuse_cell:
-                        self._dgemm(plan, f"out{l}", [m._rowsrc(dEn, PS * nz, 2 * s * nz, nz)], M, H, n, Wt["out.wT"], dxt.data_ptr(), n * H, H,
-                                    lstm_bwd=cells[nl - 1])
-                else:
-                    self._dgemm(plan, f"out{l}", [m._rowsrc(dEn, PS * nz, 2 * s * nz, nz)], M, H, n, Wt["out.wT"], dxt.data_ptr(), n * H, H,
-                                lstm_bwd=(cells[nl - 1] if fuse_cell else None))
                 for i in reversed(range(nl)):
                     dg = dgs[i]
-                    if not fuse_cell:
-                        plan.add(f"bw.lstm{l}.{i}", lib.gcpx_lstm_bwd, C.byref(cells[i]))
+                    plan.add(f"bw.lstm{l}.{i}", lib.gcpx_lstm_bwd, C.byref(cells[i]))
                     x_i = buf(f"x{l}.{i}", (M, H))
                     self._wgrad(plan, f"lstm{l}.{i}.ih", dg.data_ptr(), 4 * H, M, 4 * H, x_i.data_ptr(), H,
                                 self.g(f"{sp}.lstm.{i}.weight_ih"), ldw=H, sr=H, sb=M * H, rpb=M,
@@ -239,8 +229,7 @@ class BackwardPlanMixin:
                                 self.g(f"{sp}.lstm.{i}.weight_hh"), ldw=H, sr=2 * nl * H, sb=M * 2 * nl * H, rpb=M)
                     dxi = dxis[i]
                     src = [self._dense(dg.data_ptr(), 4 * H, 4 * H, M)]
-                    self._dgemm(plan, f"lstm{l}.{i}.x", src, M, H, M, Wt[f"lstm{i}.wxT"], dxi.data_ptr(), 0, H,
-                                lstm_bwd=(cells[i - 1] if (fuse_cell and i > 0) else None))
+                    self._dgemm(plan, f"lstm{l}.{i}.x", src, M, H, M, Wt[f"lstm{i}.wxT"], dxi.data_ptr(), 0, H)
                     if not self.batch_dh:
                         self._dgemm(plan, f"lstm{l}.{i}.h", src, M, H, M, Wt["lstm.whT"][i], _addr(dmerged, 2 * i * H), 0, 2 * nl * H)
                     dh_src = dxi
@@ -300,22 +289,20 @@ class BackwardPlanMixin:
                 self._tree_accum(plan, f"hid{l}", dHid, PS * SD, 2 * s * SD, B, n, H,
                                  [(dpar.data_ptr() + 4 * j * M * 2 * H, 2 * H, 0, H, -1, -1, j * H) for j in range(2 * nl)])
 
-            # Below the root the three remaining chains of a level are independent: posterior MLP (+ attention), prior MLP,
-            # parent-state merge.  They run on three lanes (each ~10 dependent launches) and meet again at the accumulation.
-            split = self.parallel_level_chains and self.side_lanes and l > 0
+            # The parent-state merge chain.  (Posterior, prior and merge chains of a level on three lanes of their own measured 30.0
+            # against 28.2 ms / step: the side lanes are busy with the previous level's weight gradients.)
             dXi = None
-            if not split:
-                if hp.tree_lstm:
-                    if merge_lane:
-                        plan.lane = MERGE_LANE
-                    dh_batched()
-                merge_backward()
-                if hp.tree_lstm and merge_lane:
-                    plan.lane = 0
-                    merge_pending = True
-                    if l == 0:
-                        plan.wait(0, MERGE_LANE)        # (the LSTM initialiser below reads the root states' gradient)
-                        merge_pending = False
+            if hp.tree_lstm:
+                if merge_lane:
+                    plan.lane = MERGE_LANE
+                dh_batched()
+            merge_backward()
+            if hp.tree_lstm and merge_lane:
+                plan.lane = 0
+                merge_pending = True
+                if l == 0:
+                    plan.wait(0, MERGE_LANE)        # (the LSTM initialiser below reads the root states' gradient)
+                    merge_pending = False
             if l == 0 and hp.tree_lstm and hp.lstm_init == "mlp":
                 # MLP LSTM initialiser (tree_module.py:104-105): outputs live in Hid slots 0 and 2^L
                 dinit = buf("bw.dinit", (B, 2 * SD))
@@ -332,12 +319,9 @@ class BackwardPlanMixin:
             dXq, dXp = buf(f"bw.dXq{l}", (M, 2 * nz)), buf(f"bw.dXp{l}", (M, 2 * nz))
             dEt_l = buf(f"bw.dEt{l}", (M, nz)) if attentive else None
             et_out = (dEt_l.data_ptr(), n * nz, nz) if attentive else (_addr(dET, s * nz), PS * nz, 2 * s * nz)
-            if split:
-                plan.fork([1, 2])
-                plan.lane = 1
             # posterior and prior chains are independent: one grouped launch of both (not with attention, whose backward sits between
-            # them and reads the posterior's result; not on three lanes)
-            grp = [] if (self.group_mlp_bwd and not attentive and not split) else None
+            # them and reads the posterior's result)
+            grp = [] if (self.group_mlp_bwd and not attentive) else None
             self._mlp_bwd(plan, f"posterior{l}", f"{p}.inference.q", rec[f"mlp:posterior{l}"], Wt["q"], dq.data_ptr(), 2 * nv,
                           [(dXq.data_ptr(), n * 2 * nz, 2 * nz), et_out], group=grp)
             dXa = None
@@ -351,17 +335,9 @@ class BackwardPlanMixin:
                             self.g(f"{a_}.k_proj.weight"), ldw=dk, sr=dk, sb=B * T * dk, rpb=B * T, dbias=self.g(f"{a_}.k_proj.bias"))
                 self._wgrad(plan, f"attn.v_proj{l}", _addr(dVp, li * nz), n_mod * nz, B * T, nz, o["inf_enc_seq"].data_ptr(), nz,
                             self.g(f"{a_}.v_proj.weight"), ldw=nz, sr=nz, sb=B * T * nz, rpb=B * T, dbias=self.g(f"{a_}.v_proj.bias"))
-            if split:
-                plan.lane = 2
             self._mlp_bwd(plan, f"prior{l}", f"{p}.prior", rec[f"mlp:prior{l}"], Wt["prior"], dp.data_ptr(), 2 * nv,
                           [(dXp.data_ptr(), n * 2 * nz, 2 * nz)], group=grp)
             self._mlp_bwd_group(plan, f"level{l}", grp)
-            if split:
-                plan.lane = 0
-                if hp.tree_lstm:
-                    dh_batched()
-                merge_backward()
-                plan.join([1, 2])
             ctx = (2 * nz + nv, 3 * nz + nv) if hp.context_every_step else (-1, -1)
             srcs = [(dpi.data_ptr(), pid, 0, nz, ctx[0], ctx[1], 0), (dXq.data_ptr(), 2 * nz, 0, nz, -1, -1, 0),
                     (dXp.data_ptr(), 2 * nz, 0, nz, -1, -1, 0)]
@@ -415,26 +391,12 @@ class BackwardPlanMixin:
         return plan
 
     def _three_encoder_passes(self, plan, fplan, traj, i0, ig):
-        """The backward chains of the three encoder passes (trajectory frames, I_0, I_g: base_gcp.py:188,208,209) are independent — each a
-        chain of ~15 small launches, 0.7 / 0.3 / 0.3 ms at c2 — so the two image passes run on the side lanes beside the trajectory pass
-        instead of behind it.  Their weight gradients ACCUMULATE into the same parameters: the trajectory pass's go out first (over the
-        lanes, one layer per tag), the image passes' behind them on one lane."""
-        if not (self.side_lanes and self.n_side >= 2 and self.parallel_encoder_passes):
-            traj()
-            self._flush(plan)
-            i0()
-            ig()
-            self._flush(plan, one_lane=True)      # same parameters as the trajectory pass: one lane, behind it
-            return
-        assert not plan.deferred
-        plan.fork([1, 2])
-        plan.lane = 1
-        i0()
-        plan.lane = 2
-        ig()
-        plan.lane = 0
-        late, plan.deferred = plan.deferred, []
+        """The backward chains of the three encoder passes (trajectory frames, I_0, I_g: base_gcp.py:188,208,209), one behind the other:
+        with the two image passes on the side lanes beside the trajectory pass the backward's tail got 0.15 ms shorter and the step did
+        not (c2: 14.94 ms against 14.64).  Their weight gradients ACCUMULATE into the same parameters: the trajectory pass's go out
+        first (over the lanes, one layer per tag), the image passes' behind them on one lane."""
         traj()
         self._flush(plan)
-        plan.deferred = late
-        self._flush(plan, one_lane=True)
+        i0()
+        ig()
+        self._flush(plan, one_lane=True)      # same parameters as the trajectory pass: one lane, behind it

@@ -83,8 +83,7 @@ class BackwardStagesMixin:
             # bias: per-frame column sums come out of the loss-gradient kernel
             self._colsum(plan, "dec.head", buf("bw.dMD.colsum", (R, pitch)).data_ptr(), pitch, R, pitch,
                          self.g("decoder.gen_head.conv.bias"), n_map=perm32)
-        if self.early_fork:
-            self._flush(plan)
+        # (the weight gradients queued above go out behind the data gradients: forked in front of them they cost 0.25 ms on the critical lane)
         dA = buf("bw.dA.head", (F, S, S, ngf))
         a = m._conv_args([(dMD.data_ptr(), pitch, 1, None, None, rt.ACT_NONE)], F, S, S, S, S, ngf, ngf, self.bk["dec.head.wT"],
                          self._zeros, dA)
@@ -145,8 +144,6 @@ class BackwardStagesMixin:
                 self._side(plan, f"bw.stage:dec.{name}", lib.gcpx_conv_stage, C.byref(a))
                 self._wgrad_conv3(plan, f"dec.{name}", dy.data_ptr(), cout, U.data_ptr(), F, res, res, cin, cout,
                                   self.g(f"decoder.net.{name}.conv.weight"))
-            if self.early_fork:
-                self._flush(plan)
             dU = buf(f"bw.dU.{name}", (F, res, res, cin))
             quarters = (self.split_dgrad_wide and m.split_f16 and res % 16 == 0 and res >= 16 and cin % 32 == 0 and cout % 16 == 0 and
                         f"bw.dec.{name}.q0" in m.pk_split and f"dec.{name}.wTq0" in self.bk)
@@ -301,8 +298,7 @@ class BackwardStagesMixin:
             name, cin, cout, _ = layers[li]
             r = er["r"][li]
             bn = rec[f"bn:{tag}.bn{li}"]
-            dy = self._bn_bwd(plan, f"{tag}.{name}", bn, dA.data_ptr(), cout, 0, 0, r, F, res, res, add=dskip.get(li),
-                              defer_affine=(self.side_lanes and self.n_side >= 2 and self.parallel_encoder_passes))
+            dy = self._bn_bwd(plan, f"{tag}.{name}", bn, dA.data_ptr(), cout, 0, 0, r, F, res, res, add=dskip.get(li))
             if li == 1:
                 x, sc, sh, act = er["a0"], None, None, rt.ACT_NONE
             else:

@@ -8,6 +8,7 @@ chain runs on a side lane next to the posterior chain.  Weight streaming dominat
 step), so this path is HBM/L2 bound, not MFMA bound.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -77,7 +78,7 @@ class GCPSequentialModel(GCPTreeModel):
     # generator steps as the plain forward instead of 5 (embed and out Linear off the dependent chain): 7.4 -> ~6 ms at c2.
     def repack(self, stream=None, bucket=None, max_blocks=0):
         super().repack(stream, bucket, max_blocks)
-        live = self.__dict__.setdefault("_live_folds", __import__("os").environ.get("GCPX_SEQ_LIVE_FOLDS", "1") == "1")   # (read once per model)
+        live = self.__dict__.setdefault("_live_folds", os.environ.get("GCPX_SEQ_LIVE_FOLDS", "1") == "1")   # (read once per model)
         xp = getattr(self, "_extra_packs", None) or {}
         live = live and all(n in xp and "embed.wT" in xp[n] and "out.wT" in xp[n] for n in self._nets)   # (the trainer's transposed packs)
         if self._arena is not None and live and self._hp.tree_lstm and (bucket is None or bucket == self._arena_ranges[-1][0]):

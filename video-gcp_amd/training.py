@@ -6,7 +6,7 @@ Mirrors the reference's inner loop (/root/reference/gcp/prediction/train.py:155-
 with optimizer = RAdam(lr, betas=(adam_beta, 0.999)) (gcp_builder.py:88-89,178-179; gradient_clip defaults to None).
 
 The reference leans on torch autograd; here the backward pass is a second recorded launch plan, generated from the
-records the forward plan leaves behind (`plan.rec`), and replayed as a hipGraph:
+records the forward plan leaves behind (`plan.rec`), and replayed over the model's streams:
   * data gradients of Linear / Conv1d / ConvTranspose / strided-conv layers: gcpx_gemm with transposed weight packs;
     of the decoder's 3x3 convs: gcpx_conv3x3 with flipped + transposed packs;
   * weight gradients: gcpx_wgrad (f32 MFMA "TN" GEMM; convs as implicit im2col);
@@ -36,7 +36,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
     after the gradients (tests)."""
 
     OPTIMIZERS = {"radam": 0, "adam": 1, "rmsprop": 2, "sgd": 3}
-    _early_on, _caller, _slice_stream, last_bplan_caller_lane = False, None, None, False          # (see __init__: early_optimizer)
+    _early_on, _caller, last_bplan_caller_lane = False, None, False          # (see __init__: early_optimizer)
     _pending_slices = ()
     NAN_GUARDS = (None, "raise", "skip")
 
@@ -78,7 +78,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         # while the backward plan runs on the model's lanes — as soon as the backward reports the slice final (and, data-parallel, its
         # all-reduce is done): the 7 levels' 10.3 M parameters each (c2) are updated under the remaining levels and the encoder
         # backward, instead of 2.9 GB of optimizer + re-pack traffic behind the last gradient.  Not with gradient_clip (the global norm
-        # needs every slice) and not with a graph-captured backward (no host callbacks).  backward() alone never touches parameters.
+        # needs every slice).  backward() alone never touches parameters.
         # Issued at a level's mark, a full grid of the optimizer kernel stretched the tree chain's GEMMs beside it from 41 to 101 us
         # (profiles/r04n_train_timeline.txt) and took back 0.4 of the 0.58 ms; with the levels' merge chains on the caller's stream
         # (merge_on_caller_lane) the slices are held until the last chain is out and run under the encoder backward (_on_mark): -0.24 ms
@@ -86,7 +86,6 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         # (one workgroup per CU, 256, is the default since round 6: -0.1 ms against full grids; 128: +0.3 ms, 64: +1.6).
         self.early_optimizer = os.environ.get("GCPX_NO_EARLY_OPTIMIZER") is None
         self.early_blocks = int(os.environ.get("GCPX_EARLY_BLOCKS", "256"))     # (round 6 sweep: 0 = full grids 12.00 ms, 64: 13.6, 128: 12.3, 256: 11.90, 512: 11.96)
-        self.early_on_caller = os.environ.get("GCPX_EARLY_STREAM", "caller") == "caller"     # else: communication stream / last side lane
         self._early_on, self._applied, self._caller = False, set(), None
         self.split_dgrad_wide = os.environ.get("GCPX_NO_SPLIT_DGRAD_WIDE") is None     # data gradients of the 32- / 64-channel decoder blocks on the split-f16 kernel
         self.bk = model.build_arena(self._pack_backward)
@@ -98,9 +97,6 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self.wgroup_min_blocks = int(os.environ.get("GCPX_WGROUP_MIN", "256"))
         self.fused_image_wgrad = os.environ.get("GCPX_IMAGE_WGRAD_UNFUSED") is None
         self.split_wgrad = os.environ.get("GCPX_WGRAD_NOSPLIT") is None     # decoder conv weight gradients on the split-f16 kernel
-        # the I_0 / I_g encoder backward chains on the side lanes beside the trajectory pass's: the backward's tail gets 0.15 ms shorter in
-        # tools/train_phase_times.py, the step does not (8 same-box pairs, c2: 14.94 ms with, 14.64 without) — off
-        self.parallel_encoder_passes = os.environ.get("GCPX_PARALLEL_ENCODER_BWD") is not None
         self.wgrad_per_cu = int(os.environ.get("GCPX_WGRAD_PER_CU", "1"))         # conv weight gradients: workgroups per CU (0: the kernel's own occupancy)
         self.lean_mean_grad = os.environ.get("GCPX_NO_LEAN_MEAN_GRAD") is None   # adaptive: head backward over the 80 slots of the mixture mean
         self.fuse_stage = os.environ.get("GCPX_NO_STAGE_FUSION") is None     # 16-channel upsampling blocks: weight gradient without gcpx_conv_stage
@@ -112,16 +108,11 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         # during the backward, with a hardware queue of its own (a fifth stream would share one of the four) — beside the level's
         # embedding / latent / Predictor chain on lane 0
         self.merge_on_caller_lane = os.environ.get("GCPX_NO_MERGE_LANE") is None
-        # LSTM cell backward in the epilogue of the GEMM that feeds it (gcpx_gemm_args.lstm_bwd): 3 launches per level off the chain, but
-        # the cell's dependent loads then sit behind the K loop of a launch with 32 .. 64 workgroups: c2 step 13.07 ms with, 12.91 without
-        # (tools/ab_train_attr.py fuse_lstm_bwd 1 0); gcp_sequential 24.3 either way (host issue time 10 -> 7.6 ms).  Off.
-        self.fuse_lstm_bwd = os.environ.get("GCPX_LSTM_BWD_FUSION") is not None
         self.zero_on_side_lane = os.environ.get("GCPX_ZERO_ON_LANE0") is None
         self.heads_on_side_lane = os.environ.get("GCPX_NO_HEADS_ASIDE") is None
 
         self.batch_dh = os.environ.get("GCPX_NO_BATCH_DH") is None                 # a level's d h_prev GEMMs as one batched launch
         self.group_mlp_bwd = os.environ.get("GCPX_NO_MLP_BWD_GROUP") is None       # a level's posterior + prior backward as one launch
-        self.early_fork = os.environ.get("GCPX_EARLY_FORK") is not None   # measured: forking the head's weight gradient before its data gradient costs 0.25 ms (contention on the critical lane)
         self.fused_mlp_bwd = os.environ.get("GCPX_NO_FUSED_MLP_BWD") is None
         self._pad_fixups = []                 # (see _mlp_in_dst)
         # the decoder's weight gradients (5 ms of throughput-bound kernels) are forked after the decoder's data-gradient chain: they then
@@ -140,18 +131,13 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self.group_wgrads = os.environ.get("GCPX_NO_WGROUP") is None   # one grouped launch per level and kernel variant
         self.side_lanes = bool(hp.untied_layers)   # tied levels accumulate into the same weights: keep them on one lane
         self.wgrad_waves = 8192               # wavefronts a split weight-gradient launch aims for (latency hiding)
-        # The backward plan is replayed EAGERLY over real streams by default: as parallel branches of one hipGraph the runtime
-        # maps nodes of the critical chain onto the same hardware queue as multi-millisecond weight-gradient kernels and
-        # serialises them (measured: 32.0 ms / step as a graph, 28.0 ms eager, c2).
-        self.backward_graph = False
+        # The backward plan is replayed EAGERLY over real streams: as parallel branches of one hipGraph the runtime maps nodes of the
+        # critical chain onto the same hardware queue as multi-millisecond weight-gradient kernels and serialises them (measured:
+        # 32.0 ms / step as a graph, 28.0 ms eager, c2).
         # GCPX_BWD_SEGMENTS=n > 0: EVERY run of >= n consecutive launches on one lane is replayed as a small linear hipGraph
         # (plan_ops.compact); 0: only where the plan asks for it (rec["segment_ranges"]); -1: nowhere
         self.segment_graphs = int(os.environ.get("GCPX_BWD_SEGMENTS", "0"))
-        # posterior / prior / merge chains of a level on three lanes: measured SLOWER (30.0 vs 28.2 ms / step) — the side lanes are
-        # busy with the previous level's weight gradients, so the forked chains queue behind them.  Kept for experiments.
-        self.parallel_level_chains = False
-        self.n_side = int(__import__("os").environ.get("GCPX_NSIDE", N_LANES - 1))   # side lanes of the backward plan
-        self.side_priority = 0                # middle priority; lowest (> 0) starves the side lanes: 40.9 ms / step
+        self.n_side = int(os.environ.get("GCPX_NSIDE", N_LANES - 1))   # side lanes of the backward plan
         self._lanes = None
         self._lane_streams = None
         self._zeros = torch.zeros(256, device=model.device)
@@ -179,29 +165,22 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self._pending_slices = []
         self.last_bplan_caller_lane = bool(bplan.rec.get("caller_lane"))
         m._stream.wait_stream(caller)
-        stream = m._stream.cuda_stream
-        if m.use_graph and self.backward_graph:
-            if bplan.graph is None:
-                bplan.run(m._streams)
-                bplan.graph = m._capture(bplan, bplan.ops, stream)
-            rt.check(m.lib.gcpx_graph_launch(bplan.graph, stream), "graph_launch")
-        else:
-            # (the caller's stream is the plan's last lane: the levels' merge chains, and step()'s early optimizer slices behind them)
-            lanes = self._backward_streams() + [caller.cuda_stream]
-            ops = None
-            seg_ranges = None if self.segment_graphs > 0 else bplan.rec.get("segment_ranges")
-            if (self.segment_graphs > 0 or (seg_ranges and self.segment_graphs == 0)) and not bplan.rec.get("caller_lane"):
-                # runs of launches on one lane as small linear graphs (fewer host calls; lanes, events and marks unchanged): everywhere
-                # (GCPX_BWD_SEGMENTS=n) or where the plan asks for it (`segment_ranges`: chains with slack, GCPX_BWD_SEGMENTS=-1: nowhere)
-                if bplan.rec.get("_segments") is None:
-                    bplan.run(lanes, on_mark=self._on_mark)
-                    torch.cuda.synchronize(m.device)
-                    bplan.rec["_segments"] = bplan.compact(self._backward_streams(), max(self.segment_graphs, 3), seg_ranges)
-                    self.last_bplan = bplan
-                    caller.wait_stream(m._stream)
-                    return out
-                ops = bplan.rec["_segments"]
-            bplan.run(lanes, ops=ops, on_mark=self._on_mark)
+        # (the caller's stream is the plan's last lane: the levels' merge chains, and step()'s early optimizer slices behind them)
+        lanes = self._backward_streams() + [caller.cuda_stream]
+        ops = None
+        seg_ranges = None if self.segment_graphs > 0 else bplan.rec.get("segment_ranges")
+        if (self.segment_graphs > 0 or (seg_ranges and self.segment_graphs == 0)) and not bplan.rec.get("caller_lane"):
+            # runs of launches on one lane as small linear graphs (fewer host calls; lanes, events and marks unchanged): everywhere
+            # (GCPX_BWD_SEGMENTS=n) or where the plan asks for it (`segment_ranges`: chains with slack, GCPX_BWD_SEGMENTS=-1: nowhere)
+            if bplan.rec.get("_segments") is None:
+                bplan.run(lanes, on_mark=self._on_mark)
+                torch.cuda.synchronize(m.device)
+                bplan.rec["_segments"] = bplan.compact(self._backward_streams(), max(self.segment_graphs, 3), seg_ranges)
+                self.last_bplan = bplan
+                caller.wait_stream(m._stream)
+                return out
+            ops = bplan.rec["_segments"]
+        bplan.run(lanes, ops=ops, on_mark=self._on_mark)
         caller.wait_stream(m._stream)
         self.last_bplan = bplan
         return out
@@ -218,7 +197,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         if self.buckets is not None:
             self.buckets.reduce_async(payload, after_streams=self._lane_streams)
         if self._early_on:
-            if self.early_on_caller and self.last_bplan_caller_lane:
+            if self.last_bplan_caller_lane:
                 # The caller's stream also carries the levels' merge chains (merge_on_caller_lane): a slice issued here would wait for
                 # the level's weight gradients on the side lanes and hold up the next level's merge chain behind it (measured: 15.0
                 # instead of 13.2 ms / step).  Remember where the lanes stand (events) and issue the slices behind the last merge chain
@@ -230,22 +209,12 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
                     evs.append(e)
                 self._pending_slices.append((payload, evs))
                 return
-            # elsewhere: at once, on the caller's stream or — early_on_caller = False — on the communication stream (data-parallel: the
-            # slice follows its all-reduce there) / the last side lane
-            if self.early_on_caller:
-                on = self._caller
-            elif self.buckets is not None and self.buckets.comm_stream is not None:
-                on = self.buckets.comm_stream
-            else:
-                on = self._lane_streams[-1]
-            self._slice_stream = on
-            self._apply_slice(payload, tick=False, on=on, after=[s_ for s_ in self._lane_streams if s_ is not on],
-                              max_blocks=self.early_blocks)
+            # elsewhere: at once, on the caller's stream
+            self._apply_slice(payload, tick=False, on=self._caller, after=self._lane_streams, max_blocks=self.early_blocks)
             self._applied.add(payload)
 
     def _issue_pending_slices(self):
         for i, evs in self._pending_slices:
-            self._slice_stream = self._caller
             self._apply_slice(i, tick=False, on=self._caller, after=evs, max_blocks=self.early_blocks)
             self._applied.add(i)
         self._pending_slices = []
@@ -287,7 +256,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             for _ in range(1 + self.n_side - len(self._lanes)):
                 sp = C.c_void_p()
                 with torch.cuda.device(m.device):
-                    rt.check(m.lib.gcpx_stream_create_priority(C.byref(sp), int(self.side_priority)), "stream_create")
+                    rt.check(m.lib.gcpx_stream_create_priority(C.byref(sp), 0), "stream_create")      # middle priority; lowest (> 0) starves the side lanes: 40.9 ms / step
                 self._lanes.append(sp)
         return self._lanes
 
@@ -317,8 +286,6 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             if self._clip_state_dirty:
                 self.opt_state[1:2].zero_()      # (ordered behind the early slices: they already read it — see step())
                 self._clip_state_dirty = False
-            if self._slice_stream is not None and self._slice_stream is not self._caller:
-                self._caller.wait_stream(self._slice_stream)
             todo = [i for i in range(len(self._ranges)) if i not in applied]
             for j, i in enumerate(todo):
                 self._apply_slice(i, tick=(j == len(todo) - 1), on=self._caller)
@@ -348,8 +315,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
 
     def step(self, inputs, noise=None):
         # (no early slices under a nan_guard either: the verdict needs the whole gradient, as the clipping norm does)
-        self._early_on = (self.early_optimizer and not self.gradient_clip and not self.nan_guard and len(self._ranges) > 1 and
-                          not (self.m.use_graph and self.backward_graph))
+        self._early_on = self.early_optimizer and not self.gradient_clip and not self.nan_guard and len(self._ranges) > 1
         if self._early_on and self._clip_state_dirty:
             self.opt_state[1:2].zero_()          # the early slices read the clip coefficient: it must be 0 (unset) before they run
             self._clip_state_dirty = False

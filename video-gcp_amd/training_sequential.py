@@ -23,6 +23,7 @@ has only the generator chain (no KL, no latent backward, no prior / inference ch
 columns of every net are the encoded action, whose gradient — summed over the nets — goes through the action encoder's Predictor backward.
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -40,14 +41,7 @@ class SequentialTrainStep(GCPTrainStep):
         assert model._hp.context_every_step, "the recurrent nets are built with the (e_0, e_g) context at every step (hyperparameters.py default)"
         super().__init__(model, lr=lr, betas=betas, eps=eps, process_group=process_group, **optim)
         self.side_lanes = True
-        self.wgrad_per_cu = int(__import__("os").environ.get("GCPX_WGRAD_PER_CU", "0"))   # (full occupancy here: backward_ops._wgrad_conv3)
-        # GCPX_SEQ_CHAINS: "lockstep" (default): prior chain ahead on its own lane, generator step t and inference step t + 1 in the SAME
-        # five launches (gcpx_gemm_group) on the main lane; "overlap": three lanes, step-by-step events; "serial": round-5 order
-        # "lockstep3": the prior net's step t rides in the same launches too (three problems each; no side chain, no events at all)
-        mode = __import__("os").environ.get("GCPX_SEQ_CHAINS", "lockstep")
-        self.chains_overlap = mode in ("overlap", "lockstep", "lockstep3")
-        self.chains_lockstep = mode in ("lockstep", "lockstep3")
-        self.chains_lockstep3 = mode == "lockstep3"
+        self.wgrad_per_cu = int(os.environ.get("GCPX_WGRAD_PER_CU", "0"))   # (full occupancy here: backward_ops._wgrad_conv3)
 
     # ------------------------------------------------------------------------------------------------
     def _pack_backward(self, sd):
@@ -120,7 +114,7 @@ class SequentialTrainStep(GCPTrainStep):
         DX0 = buf(f"bw.{net}.dxh0", (T - 1, B, 2 * H))                                 # layer 0: kept per step (embedding weight gradient)
         dtop = buf(f"bw.{net}.dtop", (B, H))
         dcrec = [buf(f"bw.{net}.dc{i}", (B, 2 * H)) for i in range(nl)]                 # (pitch 2H: addressed with the strides of [h | c])
-        fuse_cell = self.fuse_lstm_bwd or slots is not None   # a layer's cell backward in the epilogue of the GEMM that produces its d h (training.py)
+        fuse_cell = slots is not None    # grouped: a layer's cell backward runs in the epilogue of the GEMM that produces its d h
         slot = (lambda k: slots[k]) if slots is not None else (lambda k: None)
         for t in reversed(range(T - 1)):
             last = t == T - 2
@@ -266,34 +260,19 @@ class SequentialTrainStep(GCPTrainStep):
                             dbias=(self.g(f"{p}.embed.bias") if k == 0 else None))
                 koff += sc["w"]
 
-        # ---- prior chain on a side lane (needs the KL gradient only), decoder backward on the main lane ----
-        # chains_overlap: the generator's step t needs the prior's input gradient of step t + 1 only, so it follows the prior chain
-        # step by step (one event per prior step) instead of waiting for its last one: the prior chain starts beside the decoder
-        # backward as before, the generator starts when the decoder backward ends, wherever the prior chain is by then
-        overlap = self.chains_overlap and not det
-        lockstep = overlap and self.chains_lockstep
-        lock3 = lockstep and self.chains_lockstep3
-        prior_done = {} if (overlap and not lock3) else None
-        PE = 4 if lockstep else 1                             # the prior chain hands over every PE steps (it is far ahead anyway)
-
-        def prior_chain():
-            plan.lane = 1
-            i0 = len(plan.ops)
-            if not det:
-                for _ in self._chain(plan, "prior_lstm", lambda t: m._rowsrc(_addr(dPZ, t * 2 * nv), (T - 1) * 2 * nv, 0, 2 * nv), B, T, dIn["prior_lstm"],
-                                     nrec, events=prior_done, event_every=PE):
-                    pass
-            plan.lane = 0
-            return i0
-        if lock3:
-            pass                                              # (the prior's steps are issued with the generator's, below)
-        elif overlap:
+        # ---- the schedule (18.6-18.76 ms / step at c2; the chains one behind the other 24.5, three lanes with an
+        # event per step 20.3-20.9, the prior's steps in the grouped launches too 18.75-19.2) ----
+        #   * the prior chain needs the KL gradient only: it runs ahead on lane 1, beside the decoder backward, and hands over every PE steps;
+        #   * the generator's step t needs the prior's input gradient of step t + 1 only, so it follows the prior chain instead of waiting
+        #     for its last step, and shares its launches with the inference net's step t + 1 on the main lane.
+        # A deterministic predictor has the generator chain alone.
+        if det:
+            plan.fork([1])
+        else:
+            PE = 4                                            # the prior chain hands over every PE steps (it is far ahead anyway)
             # the HOST issues the plan in order: the decoder backward's launches go out first (the main lane starts at once), the prior
             # chain's ~870 host calls follow while the device is busy with them; lane 1 starts from where the main lane stood HERE
             prior_start = plan.record(0)
-        else:
-            plan.fork([1])
-            prior_chain()
         F = B * (T - 1)
         row2frame = buf("bw.seq.row2frame", (B * T,), torch.int32)       # row (b, t) of the matched arrays <- decoded frame (b, t - 1); (b, 0): none
         r2f = torch.arange(B * T, dtype=torch.int64).view(B, T)
@@ -304,105 +283,76 @@ class SequentialTrainStep(GCPTrainStep):
         row2frame_inv.copy_(inv.reshape(-1).to(torch.int32))
         dE_dec, dskip = self._decoder_backward(plan, fplan, dMD, B, maps=dict(R=B * T, row2src=row2frame, frame2row=rec["seq_row_map"],
                                                                                row2frame=row2frame_inv))
-        pd = in_dim["prior_lstm"]
-        prior_dx = lambda: self._rows(plan, "bw.prior.dx", DX.data_ptr(), T * nz, nz, dIn["prior_lstm"].data_ptr(), (T - 1) * pd, pd, B, T - 1, nz, 1)
-        if lock3:
-            self._flush(plan, only_lane=1)                    # decoder weight gradients on lane 1, beside the one chain
-            inf_lane = 2
-        elif overlap:
+        gd = in_dim["gen_lstm"]
+        if det:
+            plan.join([1])
+            self._flush(plan, only_lane=2)                    # decoder weight gradients: on lane 2, beside the generator chain
+        else:
+            pd = in_dim["prior_lstm"]
+            prior_done = {}
             plan.await_event(1, prior_start)
-            i0 = prior_chain()
+            plan.lane = 1
+            i0 = len(plan.ops)
+            for _ in self._chain(plan, "prior_lstm", lambda t: m._rowsrc(_addr(dPZ, t * 2 * nv), (T - 1) * 2 * nv, 0, 2 * nv), B, T, dIn["prior_lstm"],
+                                 nrec, events=prior_done, event_every=PE):
+                pass
+            plan.lane = 0
             # the prior chain has hours of slack (it runs beside the decoder backward and only has to stay ahead of the generator): its
             # steps are replayed as small linear graphs, one host call per step instead of eight (training.py: segment_ranges)
             plan.rec.setdefault("segment_ranges", []).append((i0, len(plan.ops)))
             net_wgrads("prior_lstm")                          # due at the end of the step: behind the chain on its lane, with the decoder's
                                                               # (measured: no gain, no loss — the tail is the trajectory encoder's backward)
-            # decoder weight gradients behind the prior chain on lane 1 (they are due at the end of the step only); lane 2 is the
-            # inference chain's
             self._flush(plan, only_lane=1)                    # (in the tail instead, beside the encoder backward: +0.5 ms)
-            inf_lane = 2
-            plan.fork([inf_lane])
-        else:
-            plan.join([1])
-            self._flush(plan, only_lane=2)                    # decoder weight gradients: on lane 2, beside the generator / inference chains
-            inf_lane = 1
-        # gradient of x_{t+1}, t = 0 .. T-2: decoder + the prior's input at step t + 1
+            plan.fork([2])                                    # (lane 2 enters here and is joined behind the chains)
+        # gradient of x_{t+1}, t = 0 .. T-2: decoder (+ below, inside the generator's out GEMM, the prior's and generator's input at step t + 1)
         plan.add("bw.addrows.dec", lib.gcpx_add_rows, _addr(DX, nz), T * nz, nz, dE_dec.data_ptr(), None, B, T - 1, nz)
-        if not det and not overlap:
-            prior_dx()
+        own = lambda t: m._rowsrc(_addr(DX, (t + 1) * nz), T * nz, 0, nz)
+        if det:
+            # The deterministic predictor's loop: no inference chain to share launches with and no prior term, so the generator's steps
+            # go out one by one, each adding its input gradient to x_t's before the next step reads it
+            for t in self._chain(plan, "gen_lstm", own, B, T, dIn["gen_lstm"], nrec):
+                self._rows(plan, f"bw.gen.dx{t}", _addr(DX, t * nz), T * nz, 0, _addr(dIn["gen_lstm"], t * gd), (T - 1) * gd, 0, B, 1, nz, 1)
+            plan.join([1])
+        else:
+            def gen_dout(t):
+                if t + 1 > T - 2:                             # (the last frame is no input of the prior)
+                    return own(t)
+                return [own(t), m._rowsrc(_addr(dIn["prior_lstm"], (t + 1) * pd), (T - 1) * pd, 0, nz),
+                        m._rowsrc(_addr(dIn["gen_lstm"], (t + 1) * gd), (T - 1) * gd, 0, nz)]
 
-        # ---- generator chain on the main lane, inference chain one step behind it on lane 1 ----
-        # gen(t): the gradient of x_t is complete once step t has added its input gradient.  z_t = mu_q + exp(log_sigma_q) eps
-        # (sequential.py:51-54): step t's d z_t turns into d q_t right away (one tiny launch), lane 1 waits for exactly that and runs the
-        # inference net's step t while the generator goes on to step t - 1 — the two 79-step chains overlap instead of queueing.
-        gd = in_dim["gen_lstm"]
-        inf_chain = iter(()) if det else \
-            self._chain(plan, "inf_lstm", lambda t: m._rowsrc(DQ[t].data_ptr(), 2 * nv, 0, 2 * nv), B, T, dIn["inf_lstm"], nrec)
+            awaited = set()
 
-        def gen_dout(t):
-            own = m._rowsrc(_addr(DX, (t + 1) * nz), T * nz, 0, nz)
-            if not overlap or t + 1 > T - 2:                  # (the last frame is no input of the prior)
-                return own
-            return [own, m._rowsrc(_addr(dIn["prior_lstm"], (t + 1) * pd), (T - 1) * pd, 0, nz),
-                    m._rowsrc(_addr(dIn["gen_lstm"], (t + 1) * gd), (T - 1) * gd, 0, nz)]
+            def gen_before(t):
+                if t + 1 <= T - 2:
+                    tp = (t + 1) // PE * PE                    # the hand-over that covers the prior's step t + 1 (it counts t downwards)
+                    if tp not in awaited:
+                        awaited.add(tp)
+                        plan.await_event(0, prior_done[tp])
 
-        awaited = set()
-
-        def gen_before(t):
-            if overlap and not lock3 and t + 1 <= T - 2:
-                tp = (t + 1) // PE * PE                        # the hand-over that covers the prior's step t + 1 (it counts t downwards)
-                if tp not in awaited:
-                    awaited.add(tp)
-                    plan.await_event(0, prior_done[tp])
-
-        def latent(t):
-            plan.add(f"bw.latent{t}", lib.gcpx_latent_bwd, _addr(dQZ, t * 2 * nv), _addr(dPZ, t * 2 * nv), _addr(QZ, t * 2 * nv), (T - 1) * 2 * nv, 0,
-                     _addr(tin["eps"], t * nv), tin["eps"].shape[1] * nv, 0, _addr(dIn["gen_lstm"], t * gd + nz), (T - 1) * gd, None, 0,
-                     DQ[t].data_ptr(), DPd.data_ptr(), B, 1, nv)
-        if lockstep:
             # super-step k: generator step T-2-k and inference step T-1-k (one behind: it needs that step's d z) share five launches on
-            # the main lane — no lane of its own, no events between the two chains
+            # the main lane — no lane of its own, no events between the two chains.  z_t = mu_q + exp(log_sigma_q) eps
+            # (sequential.py:51-54): step t's d z_t turns into d q_t in one tiny launch in front of the inference net's step
             slots = [[] for _ in range(nl + 2)]
             gen_chain = self._chain(plan, "gen_lstm", gen_dout, B, T, dIn["gen_lstm"], nrec, before_step=gen_before, slots=slots)
             inf_chain = self._chain(plan, "inf_lstm", lambda t: m._rowsrc(DQ[t].data_ptr(), 2 * nv, 0, 2 * nv), B, T, dIn["inf_lstm"], nrec, slots=slots)
-            # lockstep3: the prior's step t in the same launches as the generator's step t (which reads the prior's step t + 1: issued one
-            # super-step earlier)
-            pri_chain = self._chain(plan, "prior_lstm", lambda t: m._rowsrc(_addr(dPZ, t * 2 * nv), (T - 1) * 2 * nv, 0, 2 * nv), B, T,
-                                    dIn["prior_lstm"], nrec, slots=slots) if lock3 else iter(())
             for k in range(T):
                 if k < T - 1:
                     next(gen_chain)
-                    if lock3:
-                        next(pri_chain)
                 if k >= 1:
-                    latent(T - 1 - k)
+                    t = T - 1 - k
+                    plan.add(f"bw.latent{t}", lib.gcpx_latent_bwd, _addr(dQZ, t * 2 * nv), _addr(dPZ, t * 2 * nv), _addr(QZ, t * 2 * nv),
+                             (T - 1) * 2 * nv, 0, _addr(tin["eps"], t * nv), tin["eps"].shape[1] * nv, 0, _addr(dIn["gen_lstm"], t * gd + nz),
+                             (T - 1) * gd, None, 0, DQ[t].data_ptr(), DPd.data_ptr(), B, 1, nv)
                     next(inf_chain)
                 for j, g in enumerate(slots):
                     m._gemm_group(plan, f"bw.dgrad:gen{T - 2 - k}+inf{T - 1 - k}.{j}", list(g))
                     g.clear()
-            for ch in (gen_chain, inf_chain, pri_chain):
+            for ch in (gen_chain, inf_chain):
                 for _ in ch:                                  # (exhausts the generators: they record their stacked buffers on the way out)
                     pass
-        for t in (() if lockstep else self._chain(plan, "gen_lstm", gen_dout, B, T, dIn["gen_lstm"], nrec, before_step=gen_before)):
-            if not overlap:
-                self._rows(plan, f"bw.gen.dx{t}", _addr(DX, t * nz), T * nz, 0, _addr(dIn["gen_lstm"], t * gd), (T - 1) * gd, 0, B, 1, nz, 1)
-            if det:
-                continue
-            if overlap:                                       # the sample's backward feeds the inference chain only: on its lane
-                plan.wait(inf_lane, 0)
-                plan.lane = inf_lane
-            latent(t)
-            if not overlap:
-                plan.wait(inf_lane, 0)
-            plan.lane = inf_lane
-            next(inf_chain)
-            plan.lane = 0
-        for _ in inf_chain:                                   # (exhausts the generator: it records its stacked buffers on the way out)
-            pass
-        plan.join([1, 2] if overlap else [1])
-        if overlap:
+            plan.join([1, 2])
             # x_t's prior and generator terms join DX for the weight gradients and the I_0 encoder
-            prior_dx()
+            self._rows(plan, "bw.prior.dx", DX.data_ptr(), T * nz, nz, dIn["prior_lstm"].data_ptr(), (T - 1) * pd, pd, B, T - 1, nz, 1)
             self._rows(plan, "bw.gen.dx", DX.data_ptr(), T * nz, nz, dIn["gen_lstm"].data_ptr(), (T - 1) * gd, gd, B, T - 1, nz, 1)
 
         # ---- weight gradients of the generator's and the inference net's chains (the prior's went out behind its chain) ----

@@ -111,15 +111,6 @@ class WeightsMixin:
             d.update(idx=idx, out=torch.zeros(2 * idx.numel(), dtype=torch.int16, device=self.device),
                      log2=torch.zeros(1, dtype=torch.int32, device=self.device))
             self.pk_split[name] = d
-            if perm == "rowfold" and shp[1] == 32:
-                # the same folded weights as two 16-channel packs (two horizontal taps per k-step, GCPX_SPLIT_ROWFOLD16): the node half
-                # and the skip half of a block whose skip channels are convolved once per sequence (forward_plan: gcpx_conv_args.addend).
-                # They gather from the block's fold scratch (folded once, above)
-                for tag, cbase in (("f16a", 0), ("f16b", 16)):
-                    i16 = pk.conv3x3_fold16_index(shp[1], cbase).to(self.device)
-                    self.pk_split[f"{name}.{tag}"] = dict(fold=d["fold"], fold16=True, idx=i16,
-                                                          out=torch.zeros(2 * i16.numel(), dtype=torch.int16, device=self.device),
-                                                          log2=torch.zeros(1, dtype=torch.int32, device=self.device))
         self.repack_split()
 
     def repack_split(self, stream=None):
@@ -183,7 +174,7 @@ class WeightsMixin:
         if self.split_f16 and d is not None:
             a.wpk_split, a.w_split_log2_dev = d["out"].data_ptr(), d["log2"].data_ptr()
             if layout is None:
-                layout = rt.SPLIT_ROWFOLD16 if d.get("fold16") else (rt.SPLIT_ROWFOLD if "fold" in d else rt.SPLIT_PLAIN)
+                layout = rt.SPLIT_ROWFOLD if "fold" in d else rt.SPLIT_PLAIN
             a.split_layout = layout
 
     def _pack_fused_embed(self):
