@@ -1057,6 +1057,61 @@ int gcpx_panel_compose(const gcpx_panel_tile* tiles, int32_t n_tiles, const void
                        uint8_t* canvas_u8, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * State trajectories on the top-down map (video-gcp_amd/image_log.py, visualization.render_trajectories_numpy; csrc/topdown_traj.hip):
+ * Multiroom3dEnv.render_top_down (multiroom3d_env.py:151-183) for n canvases at once.
+ *
+ * gcpx_topdown_trajectories: out uint8 [n][S][S][3].  background: the padded picture uint8 [S + 2 cw][S + 2 cw][3] of
+ *   topdown_assets.npz; the drawing surface is its unpadded middle [cw : cw + S]^2 (the reference renders these pictures from an
+ *   environment without crop_window).  agent_stamp / goal_stamp: [k][k] bytes (non-zero = painted), k odd and at most 31;
+ *   agent_rgb / goal_rgb: r | g << 8 | b << 16.  layers [n_layers]: a host array, read before the call returns.  Layer l of canvas i:
+ *     points     m = min(len[i], P) (len = end_ind + 1, int32 or int64 as len_i64 says); m < 1 paints nothing.  Point p is
+ *                states[i * s_n + p * s_p + {0, s_d}] (element strides).
+ *     pixels     in float32, nothing contracted: y *= -1; if the maximum of the 2 m values is > 1 or their minimum < -1 (a NaN among
+ *                them: neither, as numpy's max / min return it) every value is divided by 27 (correctly rounded); then
+ *                + (float)(0.5 * table_size), table_size = (1 / 3) * int(sqrt(n_rooms)); fx = x * render_scale, fy = y * render_scale;
+ *                px = int(fx), py = S - int(fy), truncated toward zero.  A point whose fx or fy is not finite is skipped: no segment
+ *                ends in it, no stamp is centred on it.  px and py are clamped to [-GCPX_TRAJ_COORD_LIMIT, GCPX_TRAJ_COORD_LIMIT],
+ *                which with S <= GCPX_TRAJ_MAX_SIDE keeps the test below inside int64 (the reference raises on such a point).
+ *     segments   j = 0 .. m - 2, from point j to point j + 1, covers pixel q when q lies within GCPX_TRAJ_THICKNESS / 2 of it, decided
+ *                in int64 on integer coordinates: d = b - a, w = q - a, t = w . d; t <= 0: 4 |w|^2 <= thickness^2; t >= |d|^2:
+ *                4 |q - b|^2 <= thickness^2; else 4 (d x w)^2 <= thickness^2 |d|^2.
+ *     colour     trunc(c * f * 255) per channel of color[3], clamped to [0, 255]; f = 0.5^hits, hits = [j in D] + [j + 1 in D], D = the
+ *                set {min(dim_t[i][q], len[i] - 1), q < K} (nav_9rooms.py:46-49: `color_seq[t] *= 0.5`, `color_seq[t - 1] *= 0.5`, each
+ *                once per distinct t; t = 0 dims the unused last entry through the index -1).  dim_t NULL: f = 1.  Negative values of
+ *                dim_t are ignored.
+ *     order      the background; then per layer the segments in order, the agent stamp centred on point 0, the goal stamp centred on
+ *                point m - 1 (clipped at the picture's border).  A later write wins.  Every pixel belongs to one thread for the whole
+ *                launch; GCPX_TRAJ_LAYERS_PER_LAUNCH layers go into one launch, more layers into further launches on the same stream.
+ *   Limits (GCPX_ERR_INVALID_ARG): S <= GCPX_TRAJ_MAX_SIDE, 1 <= P <= GCPX_TRAJ_MAX_POINTS, n_layers <= GCPX_TRAJ_MAX_LAYERS,
+ *   K <= GCPX_TRAJ_MAX_DIM, k odd and <= 31, state_dim == 2.  Nothing is allocated, nothing synchronises.
+ *
+ * gcpx_topdown_bottlenecks: out int32 [n][K], out[i][j] = the first maximum over t of match_dist_df[i][df(j)][:] for the breadth-first
+ *   nodes j < K of the depth-first tensor [B][N = 2^levels - 1][T] (`tree.bf.match_dist.argmax(2)[:, :7]`, nav_9rooms.py:42); a NaN
+ *   counts as the maximum, as in numpy.argmax.  One launch. */
+#define GCPX_TRAJ_MAX_SIDE 2048
+#define GCPX_TRAJ_MAX_POINTS 1024
+#define GCPX_TRAJ_MAX_LAYERS 64
+#define GCPX_TRAJ_LAYERS_PER_LAUNCH 8
+#define GCPX_TRAJ_MAX_DIM 16
+#define GCPX_TRAJ_THICKNESS 4
+#define GCPX_TRAJ_COORD_LIMIT 16384
+typedef struct gcpx_traj_layer {
+    const float* states;
+    int64_t s_n, s_p, s_d;             /* element strides of [n][P][2] */
+    const void* len;                   /* [n] */
+    const int32_t* dim_t;              /* [n][K] or NULL */
+    float color[3];
+    int32_t len_i64;                   /* len is int64 (else int32) */
+    int32_t K;
+    int32_t P;                         /* points per trajectory of `states` */
+} gcpx_traj_layer;
+int gcpx_topdown_trajectories(const uint8_t* background, int32_t S, int32_t cw, const uint8_t* agent_stamp, const uint8_t* goal_stamp,
+                              int32_t k, int32_t agent_rgb, int32_t goal_rgb, const gcpx_traj_layer* layers, int32_t n_layers, int32_t n,
+                              int32_t state_dim, int32_t n_rooms, int32_t render_scale, uint8_t* out, void* stream);
+int gcpx_topdown_bottlenecks(const float* match_dist_df, int32_t B, int32_t N, int32_t T, int32_t levels, int32_t n, int32_t K,
+                             int32_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Scalar logs (video-gcp_amd/scalar_log.py; csrc/train_stats.hip).
  *
  * gcpx_grad_segment_norms: log_gradients (base_model.py:139-146): `torch.norm(p.grad)` of every parameter with a gradient, their mean

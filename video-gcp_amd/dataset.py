@@ -95,10 +95,10 @@ def dataset_class_name(spec):
 
 
 def load_topdown_assets(data_dir):
-    """`<data_dir>/topdown_assets.npz` -> dict: background uint8 [S + 2cw, S + 2cw, 3], cw, n_rooms, scale, S, agent_stamp / goal_stamp
+    """`<data_dir>/topdown_assets.npz` (`data_dir` may also be the path of the `.npz` file itself: plan.py --topdown_assets) -> dict: background uint8 [S + 2cw, S + 2cw, 3], cw, n_rooms, scale, S, agent_stamp / goal_stamp
     bool [k, k], agent_color / goal_color uint8 [3].  S = int(table_size * scale) with table_size = (1 / 3) * int(sqrt(n_rooms)) as the
     reference computes it (multiroom3d layout; 256 for 9 rooms, 426 for 25 at the reference's scale of 256)."""
-    path = os.path.join(data_dir, TOPDOWN_ASSETS)
+    path = data_dir if str(data_dir).endswith(".npz") else os.path.join(data_dir, TOPDOWN_ASSETS)
     if not os.path.exists(path):
         raise ValueError(f"{path} not found: a MazeTopRendered... dataset (Nav9Rooms, Nav25Rooms) trains on top-down pictures drawn from "
                          "the states; the static picture and the dot stamps come from the reference's OpenCV renderer and are dumped "

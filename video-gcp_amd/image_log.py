@@ -11,6 +11,11 @@ Files (standard library only: zlib, struct): stills `<log_dir>/<name>_<phase>_<s
 (acTL / fcTL / fdAT chunks) at the reference logger's 4 frames per second, whose first frame is a plain IDAT, so any PNG reader shows
 frame 0 and every browser plays the rest.  All rows use filter type 0.
 
+A model that was handed a nav dataset's top-down assets (model.topdown_assets) also logs `regressed_state_topdown` and
+`action_traj_topdown`: the maze with the state trajectories drawn on it by gcpx_topdown_trajectories (csrc/topdown_traj.hip; the spec
+and its numpy mirror are visualization.render_trajectories_numpy), from the states, the regressed states and the matching distribution
+where they already are, on the device.
+
 Not built: pruned_pred (this build's tree has no dense-rec module, and its action row needs cv2), pixel_copy_masks, pruned_tree,
 draw_frame's colour borders, log_prior_images (hard-wired off in the reference), scalars.
 """
@@ -207,6 +212,142 @@ def sequential_panels(model, outputs, inputs, phase):
     return [(("dense_rec", res, B, F, phase), lambda: V.rows_gif("dense_rec", res, rows, min(V.N_LOGGED_SEQS, B), F), src, None)]
 
 
+# ---- state trajectories on the nav datasets' top-down map (base_gcp.py:311-327, nav_9rooms.py:11-54) --------------------------------
+class TrajectoryRenderer:
+    """the picture and the stamps of a nav dataset's `topdown_assets.npz` on the device, and the uint8 canvases [n, S, S, 3] that
+    gcpx_topdown_trajectories (csrc/topdown_traj.hip) draws into, one per key, allocated once"""
+
+    def __init__(self, assets, device):
+        import torch
+        self.assets, self.device = assets, torch.device(device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        rgb = lambda c: int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16
+        self.background, self.agent_stamp, self.goal_stamp = (t(assets["background"]), t(assets["agent_stamp"].astype(np.uint8)),
+                                                              t(assets["goal_stamp"].astype(np.uint8)))
+        self.S, self.cw, self.k = int(assets["S"]), int(assets["cw"]), int(assets["agent_stamp"].shape[0])
+        self.agent_rgb, self.goal_rgb = rgb(assets["agent_color"]), rgb(assets["goal_color"])
+        self.canvases = {}
+
+    def render(self, lib, layers, n, stream, key=None):
+        """layers: [dict(states f32 device tensor [>= n, P, 2] (any strides), length int32 / int64 device tensor [>= n] (end_ind + 1),
+        color (three floats), dim_t int32 device tensor [n, K] or None)] -> the uint8 device canvas [n, S, S, 3] of `key`.  One call of
+        the export on `stream`; nothing is copied to the host."""
+        import torch
+        canvas = self.canvases.get((key, n))
+        if canvas is None:
+            canvas = self.canvases[(key, n)] = torch.empty((n, self.S, self.S, 3), dtype=torch.uint8, device=self.device)
+        tab = (rt.TrajLayer * max(len(layers), 1))()
+        dims = {2}
+        for d, L in zip(tab, layers):
+            st, ln, dt = L["states"], L["length"], L.get("dim_t")
+            assert st.dtype == torch.float32 and st.dim() == 3 and st.shape[0] >= n and ln.shape[0] >= n, (st.shape, ln.shape)
+            assert ln.dtype in (torch.int32, torch.int64) and ln.is_contiguous(), ln.dtype
+            dims.add(int(st.shape[2]))
+            d.states, (d.s_n, d.s_p, d.s_d), d.P = st.data_ptr(), st.stride(), st.shape[1]
+            d.len, d.len_i64 = ln.data_ptr(), int(ln.dtype == torch.int64)
+            d.color = (C.c_float * 3)(*[float(c) for c in L["color"]])
+            if dt is not None:
+                assert dt.dtype == torch.int32 and dt.is_contiguous() and dt.dim() == 2 and dt.shape[0] >= n, (dt.dtype, dt.shape)
+                d.dim_t, d.K = dt.data_ptr(), dt.shape[1]
+        a = self.assets
+        rt.check(lib.gcpx_topdown_trajectories(self.background.data_ptr(), self.S, self.cw, self.agent_stamp.data_ptr(),
+                                               self.goal_stamp.data_ptr(), self.k, self.agent_rgb, self.goal_rgb, tab, len(layers), n,
+                                               max(dims), int(a["n_rooms"]), int(a["scale"]), canvas.data_ptr(), stream),
+                 "topdown_trajectories")
+        return canvas
+
+
+def trajectory_renderer(model):
+    """the model's TrajectoryRenderer, or None when the model was given no top-down assets (model.topdown_assets: the trainer sets it
+    for a top-rendered dataset class)"""
+    assets = getattr(model, "topdown_assets", None)
+    if assets is None:
+        return None
+    cache = model.__dict__.setdefault("_image_log_panels", {})
+    r = cache.get("topdown_renderer")
+    if r is None or r.assets is not assets:
+        r = cache["topdown_renderer"] = TrajectoryRenderer(assets, model.device)
+    return r
+
+
+def bottleneck_frames(model, match_dist_df, n, stream, K=7):
+    """int32 device tensor [n, min(K, N)]: `tree.bf.match_dist.argmax(2)[:, :7]` (nav_9rooms.py:42) of the depth-first matching
+    distribution [B, N, T], one small launch, cached output"""
+    import torch
+    B, N, T = match_dist_df.shape
+    K = min(K, N)
+    cache = model.__dict__.setdefault("_image_log_panels", {})
+    out = cache.get(("bottlenecks", n, K))
+    if out is None:
+        out = cache[("bottlenecks", n, K)] = torch.empty((n, K), dtype=torch.int32, device=match_dist_df.device)
+    assert match_dist_df.is_contiguous() and match_dist_df.dtype == torch.float32
+    rt.check(model.lib.gcpx_topdown_bottlenecks(match_dist_df.data_ptr(), B, N, T, (N + 1).bit_length() - 1, n, K, out.data_ptr(), stream),
+             "topdown_bottlenecks")
+    return out
+
+
+def trajectory_layers(model, outputs, inputs, stream, n=V.N_LOGGED_SAMPLES):
+    """{panel name: layers} of log_dataset_specific_trajectory for a model's outputs: `regressed_state_topdown` (ground truth green,
+    regressed states red, the segments around the matched frames of the top three tree levels darkened when the tree has a matching)
+    and `action_traj_topdown` (the cumulated full-sequence actions from the first regressed state; only where the forward produced
+    them: the reference re-runs the inverse model on a training step, this build does not).  The first min(n, B) samples are drawn.
+    Empty without regressed states or ground-truth states, and when the regressed states are not (x, y) pairs (state_dim != 2: the
+    reference's renderer takes two columns)."""
+    import torch
+    o = outputs.raw
+    rs = o.get("regressed_state_padded")
+    if rs is None or "traj_seq_states" not in inputs:
+        return {}
+    n = min(n, rs.shape[0])
+    gt = torch.as_tensor(inputs["traj_seq_states"]).to(device=model.device, dtype=torch.float32)
+    if gt.shape[-1] < 2 or rs.shape[-1] != 2:
+        return {}
+    length = outputs.end_ind + 1                             # int64 [B], on the device
+    dim_t = bottleneck_frames(model, o["match_dist_df"], n, stream) if "match_dist_df" in o else None
+    truth = dict(states=gt[..., :2], length=length, color=V.GREEN)
+    res = {"regressed_state_topdown": [truth, dict(states=rs, length=length, color=V.RED, dim_t=dim_t)]}
+    act = o.get("actions_padded")
+    if act is not None and act.dim() == 3 and act.shape[-1] == 2:
+        cum = torch.cat((rs[:, :1], act), dim=1).cumsum(1)
+        res["action_traj_topdown"] = [truth, dict(states=cum, length=length, color=V.RED, dim_t=dim_t)]
+    return res
+
+
+def numpy_layers(layers):
+    """the same layers on the host, for visualization.render_trajectories_numpy"""
+    h = lambda t: None if t is None else t.detach().cpu().numpy()
+    return [dict(states=h(L["states"]), length=h(L["length"]), color=L["color"], dim_t=h(L.get("dim_t"))) for L in layers]
+
+
+def write_trajectory_png(path, assets, states, device, lib=None, color=V.RED):
+    """one red polyline of `states` [m, >= 2] on the map, drawn on the device and written as a PNG (the `metrics/trajectories` pictures
+    and the planner's `inferStateTraj`)"""
+    import torch
+    st = torch.as_tensor(np.asarray(states, dtype=np.float32)[None, :, :2]).to(device).contiguous()
+    r = TrajectoryRenderer(assets, device) if not isinstance(assets, TrajectoryRenderer) else assets
+    ln = torch.full((1,), st.shape[1], dtype=torch.int64, device=st.device)
+    canvas = r.render(lib or rt.lib(), [dict(states=st, length=ln, color=color)], 1, torch.cuda.current_stream(st.device).cuda_stream,
+                      key="single")
+    return write_png(path, canvas.cpu().numpy()[0])
+
+
+def write_metric_trajectories(model, inputs, exp_path, step, n=V.N_PLOTTED_ELEMENTS):
+    """dump_traj_overview (compute_metrics.py:253-261): `<exp>/metrics/trajectories/it_<step>/trajectories_<b>.png` for the first n
+    sequences of a batch, one red polyline of traj_seq_states[b, :end_ind + 1] each.  One launch, one copy.  Returns the files."""
+    import torch
+    renderer = trajectory_renderer(model)
+    if renderer is None or "traj_seq_states" not in inputs:
+        return []
+    st = torch.as_tensor(inputs["traj_seq_states"]).to(device=model.device, dtype=torch.float32)
+    end = torch.as_tensor(inputs["end_ind"]).to(device=model.device)
+    n = min(n, st.shape[0])
+    stream = torch.cuda.current_stream(model.device).cuda_stream
+    canvas = renderer.render(model.lib, [dict(states=st[..., :2], length=(end + 1).to(torch.int64), color=V.RED)], n, stream,
+                             key="metric").cpu().numpy()
+    folder = os.path.join(exp_path, "metrics", "trajectories", f"it_{step}")
+    return [write_png(os.path.join(folder, f"trajectories_{b}.png"), canvas[b]) for b in range(n)]
+
+
 def log_outputs(model, panels_fn, outputs, inputs, losses, step, log_images, phase):
     """the body of `model.log_outputs`: composes every panel of `outputs` on the device, copies the uint8 canvases to the host and
     writes them under model.log_dir (stills: the logged samples one below the other).  Returns the files written; model.last_panels
@@ -225,7 +366,17 @@ def log_outputs(model, panels_fn, outputs, inputs, losses, step, log_images, pha
             dp = cache[key] = DevicePanel(build(), model.device)
         dp.compose(model.lib, tensors, stream)
         done.append((dp, trim))
+    renderer = trajectory_renderer(model)
+    drawn = []
+    if renderer is not None:                                 # a nav dataset: the maze with the state trajectories, one launch each
+        n = min(V.N_LOGGED_SAMPLES, int(outputs.end_ind.shape[0]))
+        for name, layers in trajectory_layers(model, outputs, inputs, stream, n).items():
+            drawn.append((name, renderer.render(model.lib, layers, n, stream, key=name)))
     files, model.last_panels = [], {}
+    for name, canvas in drawn:
+        canvas = canvas.cpu().numpy()
+        model.last_panels[name] = canvas
+        files.append(write_png(os.path.join(model.log_dir, f"{name}_{phase}_{step}.png"), canvas.reshape(-1, *canvas.shape[2:])))
     for dp, trim in done:
         canvas = dp.canvas.cpu().numpy()                     # the one device-to-host copy of the panel (it waits for the launch)
         if trim is not None:

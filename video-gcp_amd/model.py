@@ -371,6 +371,7 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
     # (image_log.py); scalars through self.scalar_log, a scalar_log.ScalarLogger (the trainer's --log_scalars) ----
     log_dir = None
     scalar_log = None
+    topdown_assets = None     # dataset.load_topdown_assets' dict of a top-rendered (nav) dataset: the trajectory panels of image_log.py
 
     def log_outputs(self, outputs, inputs, losses, step, log_images, phase):
         """TreeModel.log_outputs: the scalars and the pictures of one logging step; returns the picture files written.

@@ -29,6 +29,9 @@ def get_args(argv=None):
     p.add_argument("--elite_frac", type=float, default=0.1)
     p.add_argument("--split", default="candidates", choices=["candidates", "pairs"])
     p.add_argument("--out", default="", help="directory for plan_{i}.npz")
+    p.add_argument("--topdown_assets", default="", help="a nav dataset's topdown_assets.npz: when the plan carries regressed states, "
+                   "plan_{i}_inferStateTraj.png (the state trajectory on the maze) is written next to plan_{i}.npz, which then "
+                   "also holds `states`")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reference_rng", action="store_true",
                    help="hierarchical planner: replay the reference's np.random call sequence draw for draw (6x the host time per "
@@ -76,14 +79,25 @@ def main(argv=None):
         planner = P.HierarchicalCEMPlanner(sim, cost, hp.hierarchy_levels, [10, 10], action_dim=hp.nz_vae,       # rates of the
                                            max_seq_len=hp.max_seq_len,                                       # 25-room control config
                                            fast_draws=not args.reference_rng, seed=args.seed + 1)
+    renderer = None
+    if args.topdown_assets and args.out:                             # log_single_topdown_traj (logger.py:255-261, cem_planner.py:244-250)
+        from .dataset import load_topdown_assets
+        from .image_log import TrajectoryRenderer
+        renderer = TrajectoryRenderer(load_topdown_assets(args.topdown_assets), dev)
     results = []
     for i in idx:
-        plan, actions, latents, c = planner(starts[i:i + 1], goals[i:i + 1])
+        r = planner.plan(starts[i:i + 1], goals[i:i + 1])
+        plan, actions, latents, c, states = r.predictions, r.actions, r.latents, r.cost, r.states
         results.append({"pair": int(i), "cost": float(c), "plan_len": int(plan.shape[0])})
         if args.out and (rank == 0 or args.split == "pairs"):
             os.makedirs(args.out, exist_ok=True)
+            drawn = renderer is not None and states is not None and len(states) and np.asarray(states).shape[-1] == 2
+            extra = {"states": np.asarray(states)} if drawn else {}                   # the drawn states travel with the picture
             np.savez_compressed(os.path.join(args.out, f"plan_{i}.npz"), image_plan=plan, latents=latents,
-                                actions=(actions if actions is not None else np.zeros(0)), cost=c)
+                                actions=(actions if actions is not None else np.zeros(0)), cost=c, **extra)
+            if drawn:
+                from .image_log import write_trajectory_png
+                write_trajectory_png(os.path.join(args.out, f"plan_{i}_inferStateTraj.png"), renderer, states, dev, lib=model.lib)
     if rank == 0 or args.split == "pairs":
         print(json.dumps({"rank": rank, "plans": results}), flush=True)
     return results

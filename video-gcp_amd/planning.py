@@ -484,6 +484,13 @@ class CEMPlanner:
         return best, best_scores, scores
 
     def __call__(self, state, goal_state):
+        """the reference's contract (cem_planner.py:96): (image_plan, actions, latents, cost)"""
+        r = self.plan(state, goal_state)
+        return r.predictions, r.actions, r.latents, r.cost
+
+    def plan(self, state, goal_state):
+        """the plan as Outputs(predictions, actions, latents, cost, states): `states` are the final rollout's regressed states
+        [len, state_dim], None when the simulator's model has no state regressor"""
         self._sampler.init()
         n_elite = max(int(self.batch_size * self.elite_frac), 1)
         best_samples = best_scores = None
@@ -497,7 +504,9 @@ class CEMPlanner:
             kw["len_u"] = self._sampler.sample_uniform(1)             # the plan's own length draw, from the rank-shared stream
         final = self._sim.rollout(state, goal_state, best_samples[:1].cpu().numpy(), self.max_seq_len, **kw)
         actions = final.actions[0] if final.actions is not None else None
-        return final.predictions[0], actions, final.latents[0], float(best_scores[0])
+        states = final.get("states")
+        return Outputs(predictions=final.predictions[0], actions=actions, latents=final.latents[0], cost=float(best_scores[0]),
+                       states=states[0] if states is not None else None)
 
 
 class ImageHierarchicalTreeCEMSampler:
@@ -586,6 +595,12 @@ class HierarchicalCEMPlanner:
         return np.random.default_rng(seed)
 
     def __call__(self, state, goal_state):
+        """the reference's contract (cem_planner.py:218): (image_plan, actions, latents, cost)"""
+        r = self.plan(state, goal_state)
+        return r.predictions, r.actions, r.latents, r.cost
+
+    def plan(self, state, goal_state):
+        """the plan as Outputs(predictions, actions, latents, cost, states), as CEMPlanner.plan"""
         self._sampler.init()
         self.logs = []
         goal = np.asarray(goal_state)
@@ -606,7 +621,9 @@ class HierarchicalCEMPlanner:
             self.logs.append(Outputs(elite_rollouts=best_rollouts, elite_scores=best_scores))
         final = self._sim.rollout(state, goal, best_samples, self.max_seq_len)
         actions = final.actions[0] if final.actions is not None else None
-        return final.predictions[0], actions, final.latents[0], float(np.asarray(best_scores[0]).reshape(-1)[0])
+        states = final.get("states")
+        return Outputs(predictions=final.predictions[0], actions=actions, latents=final.latents[0],
+                       cost=float(np.asarray(best_scores[0]).reshape(-1)[0]), states=states[0] if states is not None else None)
 
     @property
     def fully_optimized(self):

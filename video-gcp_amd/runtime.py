@@ -120,6 +120,12 @@ class PanelTile(C.Structure):
                 ("s_y", i64)]
 
 
+class TrajLayer(C.Structure):
+    """gcpx_traj_layer: one polyline layer of gcpx_topdown_trajectories (include/gcpx.h, csrc/topdown_traj.hip)"""
+    _fields_ = [("states", vp), ("s_n", i64), ("s_p", i64), ("s_d", i64), ("len", vp), ("dim_t", vp), ("color", C.c_float * 3),
+                ("len_i64", i32), ("K", i32), ("P", i32)]
+
+
 PANEL_MAX_SRCS = 16
 PANEL_IMAGE, PANEL_GREY, PANEL_GREY_ADD, PANEL_FILL = 0, 1, 2, 3
 PANEL_RESCALE, PANEL_LENGTH_STRICT, PANEL_INDEX_FRAME, PANEL_INDEX_I64, PANEL_LENGTH_I64 = 1, 2, 4, 8, 16
@@ -263,6 +269,8 @@ SYMBOLS = [
     ("gcpx_topdown_assemble_batch", C.c_int, [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                               i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("gcpx_panel_compose", C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp]),
+    ("gcpx_topdown_trajectories", C.c_int, [vp, i32, i32, vp, vp, i32, i32, i32, C.POINTER(TrajLayer), i32, i32, i32, i32, i32, vp, vp]),
+    ("gcpx_topdown_bottlenecks", C.c_int, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     ("gcpx_grad_segment_norms", C.c_int, [vp, i64, vp, i32, vp, i32, C.c_float, vp, vp, i64, vp, vp, vp]),
     ("gcpx_kl_layerwise", C.c_int, [vp, vp, i32, i32, i32, i64, i64, C.c_float, vp, vp, vp]),
     ("gcpx_grad_health", C.c_int, [vp, i64, vp, i32, vp, i32, vp, i32, vp, i64, vp, vp, vp, vp]),

@@ -23,6 +23,9 @@ Frame size: `--resize_frames 1` resizes recorded frames stored at another size t
 assembly, as Pillow's bilinear Image.resize does (dataset.py), for the train, validation and `--metric` test loaders alike.
 Deviation: the reference resizes every item (data_loader.py:213-220); here it defaults to 0, so that a dataset of the wrong size
 stops the run as it did before the option existed.
+On a nav dataset (Nav9Rooms, Nav25Rooms) the picture logs also hold `regressed_state_topdown` / `action_traj_topdown`, and `--metric 1`
+writes `<path>/metrics/trajectories/it_<step>/trajectories_<b>.png`: the maze with the state trajectories drawn on it (image_log.py).
+
 Picture logs: `--log_images 1` writes the reference's prediction panels (model.log_outputs, image_log.py) as PNG / animated PNG to
 <path>/images/<name>_<phase>_<step>.png|.apng, on rank 0, unless --dont_save: in training every int(epoch_len / --imepoch) steps
 (train.py:125-130,147,170-172), in validation for the last batch's prior-sampled prediction (train.py:229-230).
@@ -228,6 +231,10 @@ class ModelTrainer:
         if self.log_images:
             self.model.log_dir = os.path.join(self.exp_path, "images")
         self.image_files = []
+        # a top-rendered (nav) dataset: its picture and stamps also serve the trajectory panels of the picture logs and of --metric
+        top = getattr(getattr(self.train_loader, "ds", None), "topdown", None) or getattr(getattr(self.val_loader, "ds", None), "topdown", None)
+        if top is not None and self.rank == 0 and (self.log_images or getattr(args, "metric", False)):
+            self.model.topdown_assets = top
         self.scalar_log = None
         if bool(getattr(args, "log_scalars", 0)) and not args.dont_save and self.rank == 0:
             from .scalar_log import ScalarLogger
@@ -397,6 +404,10 @@ class ModelTrainer:
                 # reuses the buffers `output` views
                 if self.log_images and i_val == n_val - 1 and not getattr(self.cmd_args, "metric", False):
                     self.image_files += self.model.log_outputs(output, inputs, None, self.global_step, True, "val")
+                if i_val == 0 and getattr(self.cmd_args, "metric", False) and self.model.topdown_assets is not None \
+                        and not self.cmd_args.dont_save:
+                    from .image_log import write_metric_trajectories   # compute_metrics.py:225-226: the first sequences on the map
+                    self.image_files += write_metric_trajectories(self.model, inputs, self.exp_path, self.global_step)
                 if self.evaluator is not None:         # train.py:208-209: every batch, prior samples of the model's own noise stream
                     self.evaluator.eval(inputs, output, self.model)
             out = self.model(inputs)

@@ -11,7 +11,15 @@ Deviations from the reference as executed:
     `'done_mask' in segment` (logger.py:144) iterates the tree's layers and is never true, so its tree rows stay empty.
   * the balanced trees of match_overview / attention_masks / output_tree are plain tiles, without draw_frame's matplotlib colour border.
   * uint8 = trunc(clip(x, 0, 1) * 255): this build's own conversion (the reference leaves it to tensorboardX).
+
+State trajectories on the nav datasets' top-down map (Multiroom3dEnv.render_top_down, multiroom3d_env.py:151-183) are not tiles:
+`render_trajectories_numpy` below is the definition of gcpx_topdown_trajectories (csrc/topdown_traj.hip, spec in include/gcpx.h).
+  * a segment is the set of pixels within thickness / 2 of it, by an exact integer test: the shape of OpenCV's non-antialiased thick
+    line (a rectangle with round ends), not pinned to OpenCV pixel for pixel.
+  * a point whose pixel is not finite is skipped and pixels are clamped to +-TRAJ_COORD_LIMIT, where the reference raises.
 """
+import math
+
 import numpy as np
 
 IMAGE, GREY, GREY_ADD, FILL = 0, 1, 2, 3
@@ -199,3 +207,92 @@ def compose(panel, sources):
 def to_uint8(canvas):
     """this build's conversion of a [0, 1] f32 canvas to bytes: trunc(clip(x, 0, 1) * 255)"""
     return (np.clip(canvas, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8)
+
+
+# ---- state trajectories on the top-down map ----------------------------------------------------------------------------------------
+TRAJ_THICKNESS = 4            # render_top_down(line_thickness=4); GCPX_TRAJ_THICKNESS (tests/test_topdown_traj_cpu.py compares both
+TRAJ_COORD_LIMIT = 16384      # GCPX_TRAJ_COORD_LIMIT                                    with include/gcpx.h)
+N_PLOTTED_ELEMENTS = 5        # compute_metrics.py: the sequences whose trajectories --metric plots
+GREEN, RED = (0.0, 1.0, 0.0), (1.0, 0.0, 0.0)
+
+
+def trajectory_pixels(states, n_rooms, scale, S):
+    """float32 states [m, 2] -> (int64 pixels [m, 2] of the unpadded S x S picture, bool [m]: the pixel is finite).  The reference's
+    float32 expressions (multiroom3d_env.py:163-170): y *= -1; everything / 27 when max > 1 or min < -1 (numpy's max / min return a NaN
+    that is there, and then neither holds); + 0.5 * table_size; int(x * scale), S - int(y * scale)."""
+    t = np.array(states, dtype=np.float32).reshape(-1, 2)
+    t[:, 1] *= np.float32(-1)
+    with np.errstate(all="ignore"):
+        if t.size and (t.max() > 1.0 or t.min() < -1.0):
+            t = t / np.float32(27.0)
+        t = t + np.float32(0.5 * ((1 / 3) * int(math.sqrt(n_rooms))))
+        f = t * np.float32(scale)
+        ok = np.isfinite(f).all(axis=1)
+        v = np.clip(np.trunc(np.where(np.isfinite(f), f, np.float32(0))), -2.0 ** 30, 2.0 ** 30).astype(np.int64)
+    pix = np.stack([v[:, 0], S - v[:, 1]], axis=1)
+    return np.clip(pix, -TRAJ_COORD_LIMIT, TRAJ_COORD_LIMIT), ok
+
+
+def segment_colors(color, m, length, dim_t=None):
+    """uint8 [max(m - 1, 0), 3]: trunc(c * 255) of the base colour, halved once per hit of `color_seq[t] *= 0.5` and
+    `color_seq[t - 1] *= 0.5` (nav_9rooms.py:46-49) over the distinct t = min(dim_t, length - 1); negative dim_t are ignored"""
+    f = np.ones(max(m - 1, 0), dtype=np.float32)
+    if dim_t is not None:
+        D = {min(int(t), int(length) - 1) for t in np.asarray(dim_t).reshape(-1) if int(t) >= 0}
+        for j in range(f.shape[0]):
+            f[j] = np.float32(0.5) ** ((j in D) + (j + 1 in D))
+    with np.errstate(all="ignore"):
+        c = np.trunc((np.asarray(color, dtype=np.float32)[None] * f[:, None]) * np.float32(255))
+    return np.clip(np.nan_to_num(c, nan=0.0), 0, 255).astype(np.uint8)
+
+
+def _paint_segment(img, a, b, color, thickness=TRAJ_THICKNESS):
+    """the pixels of img [S, S, 3] within thickness / 2 of the segment a -> b (integer pixels), in Python integers"""
+    S, g = img.shape[0], (thickness + 1) // 2
+    ax, ay, bx, by = int(a[0]), int(a[1]), int(b[0]), int(b[1])
+    xs, xe, ys, ye = max(min(ax, bx) - g, 0), min(max(ax, bx) + g + 1, S), max(min(ay, by) - g, 0), min(max(ay, by) + g + 1, S)
+    if xs >= xe or ys >= ye:
+        return
+    qx, qy = np.arange(xs, xe, dtype=np.int64)[None, :], np.arange(ys, ye, dtype=np.int64)[:, None]
+    dx, dy, wx, wy = bx - ax, by - ay, qx - ax, qy - ay
+    dd, t, th2 = dx * dx + dy * dy, wx * dx + wy * dy, thickness * thickness
+    near_a = 4 * (wx * wx + wy * wy) <= th2
+    near_b = 4 * ((qx - bx) ** 2 + (qy - by) ** 2) <= th2
+    cross = dx * wy - dy * wx
+    cover = np.where(t <= 0, near_a, np.where(t >= dd, near_b, 4 * cross * cross <= th2 * dd))
+    img[ys:ye, xs:xe][cover] = color
+
+
+def _paint_stamp(img, stamp, color, px, py):
+    k, S = stamp.shape[0], img.shape[0]
+    x0, y0 = int(px) - k // 2, int(py) - k // 2
+    xs, xe, ys, ye = max(x0, 0), min(x0 + k, S), max(y0, 0), min(y0 + k, S)
+    if xs < xe and ys < ye:
+        img[ys:ye, xs:xe][stamp[ys - y0:ye - y0, xs - x0:xe - x0]] = color
+
+
+def render_trajectories_numpy(assets, layers):
+    """uint8 [n, S, S, 3]: the definition of gcpx_topdown_trajectories.  assets: dataset.load_topdown_assets' dict.  layers: a list of
+    dicts(states [n, P, 2], length [n] (= end_ind + 1), color (three floats), dim_t [n, K] or None).  Per canvas: the unpadded
+    picture; then per layer the segments 0 .. m - 2 in order, the agent stamp on point 0, the goal stamp on point m - 1."""
+    S, cw = assets["S"], assets["cw"]
+    n = len(layers[0]["length"])
+    out = np.repeat(assets["background"][None, cw:cw + S, cw:cw + S], n, axis=0).copy()
+    for L in layers:
+        states = np.asarray(L["states"], dtype=np.float32)
+        for i in range(n):
+            length = int(np.asarray(L["length"]).reshape(-1)[i])
+            m = min(length, states.shape[1])
+            if m < 1:
+                continue
+            pix, ok = trajectory_pixels(states[i, :m, :2], assets["n_rooms"], assets["scale"], S)
+            dim_t = None if L.get("dim_t") is None else np.asarray(L["dim_t"])[i]
+            col = segment_colors(L["color"], m, length, dim_t)
+            for j in range(m - 1):
+                if ok[j] and ok[j + 1]:
+                    _paint_segment(out[i], pix[j], pix[j + 1], col[j])
+            if ok[0]:
+                _paint_stamp(out[i], assets["agent_stamp"], assets["agent_color"], *pix[0])
+            if ok[m - 1]:
+                _paint_stamp(out[i], assets["goal_stamp"], assets["goal_color"], *pix[m - 1])
+    return out
