@@ -337,8 +337,8 @@ int gcpx_gather_rows_rest(const float* src, const int32_t* idx, float* out, int3
                           int64_t row_floats, const int32_t* written, void* stream);
 /* Learned pairwise cost over a rollout (LearnedCostEstimate, gcp/planning/cem/cost_fcn.py:88-95):
    gcpx_seq_pairs builds the "next" operand nxt[i][t] = lat[i][t+1] (t+1 < len_i) else goal[i] (goal == NULL: the
-   sequence's own last latent); the cost MLP runs on (lat, nxt) rows; gcpx_masked_row_sum adds the first len_i
-   per-step costs of every candidate. */
+   sequence's own last latent, row 0 when len_i <= 0); the cost MLP runs on (lat, nxt) rows; gcpx_masked_row_sum adds the first len_i
+   per-step costs of every candidate.  Both clamp len_i to T (lat and vals have T rows per candidate); a non-positive length sums to 0. */
 int gcpx_seq_pairs(const float* lat, const int32_t* lengths, const float* goal, float* nxt, int32_t n, int32_t T,
                    int32_t nz, void* stream);
 int gcpx_masked_row_sum(const float* vals, const int32_t* lengths, float* out, int32_t n, int32_t T, void* stream);
@@ -460,7 +460,9 @@ int gcpx_sample_length(const float* logits, const float* u, int32_t B, int32_t T
  * Evaluator.compute_metrics (gcp/evaluation/compute_metrics.py:123-130; blox.torch.evaluation is absent, spec in
  * video-gcp_amd/evaluation.py).  tgt [B][T][C][H][W] in [-1,1]; est: a pool of frames [R][C][H][W]; frame_map [B*T] = pool
  * frame compared with target frame (b, t) (negative: skipped; NULL: identity); per sequence the frames t in [first[b], last[b])
- * are averaged (the harness crops the two conditioning frames).  scratch: 2*B*T*C doubles.  out [B][3] = mse, psnr, ssim.
+ * are averaged (the harness crops the two conditioning frames).  Skipped means left out of the average: such a frame adds to no sum
+ * and is not counted, so the three values are those of the remaining frames of the range; a sequence with no frame left (an empty
+ * range, or every frame of it skipped) reports NaN three times.  scratch: 2*B*T*C doubles.  out [B][3] = mse, psnr, ssim.
  * ------------------------------------------------------------------------------------------------- */
 int gcpx_image_metrics(const float* est, const float* tgt, const int32_t* frame_map, const int32_t* first, const int32_t* last,
                        int32_t B, int32_t T, int32_t C, int32_t H, int32_t W, double* scratch, float* out, void* stream);
@@ -749,7 +751,9 @@ int gcpx_loss_aux_heads_bwd(const gcpx_loss_args* a, float* daction, float* dcos
 
 /* ---- parameters ---- */
 /* dst[i] = theta[idx0[i]] (+ theta[idx1[i]]), negative index = 0: every fragment-packed weight arena is a gather of the
-   canonical flat parameter vector (video-gcp_amd/packing.py), refreshed once per optimizer step */
+   canonical flat parameter vector (video-gcp_amd/packing.py), refreshed once per optimizer step.  idx0 / idx1 / dst 16-byte aligned;
+   n is any positive count: four elements per thread, and the last n % 4 go through a scalar tail (every call site of
+   video-gcp_amd/weights.py passes a multiple of 4, its arena leaves being padded to one) */
 int gcpx_repack(const float* theta, const int32_t* idx0, const int32_t* idx1, float* dst, int64_t n, void* stream);
 /* the same, held to max_blocks 256-thread workgroups (0 = no limit): see gcpx_optim_range */
 int gcpx_repack_blocks(const float* theta, const int32_t* idx0, const int32_t* idx1, float* dst, int64_t n, int32_t max_blocks, void* stream);

@@ -2,12 +2,11 @@
 
 Every `int gcpx_*(` declaration must be either
   (a) called in some tests/test_gpu_*.py — `.gcpx_name(` on the library handle, or passed as `lib.gcpx_name`; or
-  (b) listed below with a reason: INFRASTRUCTURE (no arithmetic of its own to compare with a reference), or INDIRECT (its only cover
-      today is the model-level test named beside it, which compares whole-model outputs or parameter gradients at 1e-3 of a tensor's
-      max-abs — the visible to-do list of kernel-level tests).
-The test also fails when a test named in INDIRECT does not exist, and when a listed name has gained a direct call (a stale entry).
-INDIRECT holds forward / planner glue only: every kernel the backward pass launches for its arithmetic has a kernel-level test
-(tests/test_gpu_backward_kernels.py, tests/test_gpu_kernels.py)."""
+  (b) listed in INFRASTRUCTURE with a reason: it has no arithmetic of its own to compare with a reference.
+INDIRECT used to list the entry points whose only cover was a model-level test (whole-model outputs or parameter gradients at 1e-3 of a
+tensor's max-abs).  It is empty and asserted to stay empty: the backward kernels have their kernel-level tests in
+tests/test_gpu_backward_kernels.py and tests/test_gpu_kernels.py, the forward / planner glue in tests/test_gpu_glue_kernels.py.  A new
+entry point needs a direct test or an INFRASTRUCTURE reason."""
 import glob
 import os
 import re
@@ -25,26 +24,7 @@ INFRASTRUCTURE = {
     "gcpx_event_elapsed_ms": "event timing", "gcpx_event_destroy": "event handle",
 }
 
-INDIRECT = {
-    "gcpx_bn_fold": "tests/test_gpu_model.py::test_posterior_forward_c1",
-    "gcpx_gather_rows_rest": "tests/test_gpu_model.py::test_losses_c1",
-    "gcpx_seq_pairs": "tests/test_gpu_planning.py::test_learned_cost_matches_oracle",
-    "gcpx_masked_row_sum": "tests/test_gpu_planning.py::test_learned_cost_matches_oracle",
-    "gcpx_rollout_cost": "tests/test_gpu_planning.py::test_hand_written_costs_on_device_rollouts",
-    "gcpx_copy_rows": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
-    "gcpx_seq_index": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
-    "gcpx_fill_zero": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
-    "gcpx_gauss_nll": "tests/test_gpu_sequential.py::test_sequential_posterior_forward_and_losses",
-    "gcpx_aux_index_rows": "tests/test_gpu_training.py::test_gradients_match_autograd_c1",
-    "gcpx_path_cost": "tests/test_gpu_training.py::test_gradients_match_autograd_c1",
-    "gcpx_sample_length": "tests/test_gpu_model.py::test_sampled_sequence_length_c1",
-    # (called through video_gcp_amd.evaluation.image_metrics, which that test compares with the metrics oracle)
-    "gcpx_image_metrics": "tests/test_gpu_api.py::test_image_metrics_kernel_matches_oracle",
-    "gcpx_repack": "tests/test_gpu_training.py::test_two_training_steps_c1",
-    "gcpx_repack_blocks": "tests/test_gpu_training.py::test_step_with_slices_applied_during_the_backward_equals_the_late_step",
-    # (called through video_gcp_amd.dataset, which that test compares bit for bit with the reference loader's arithmetic)
-    "gcpx_assemble_batch": "tests/test_gpu_dataset.py::test_assembly_is_bit_exact_against_the_reference_loader",
-}
+INDIRECT = {}
 
 # entry points the backward pass launches for their arithmetic: never acceptable in INDIRECT
 BACKWARD = ("_bwd", "gcpx_wgrad", "gcpx_colsum", "gcpx_reduce_partials", "gcpx_tree_accum", "gcpx_timestep_scatter", "gcpx_add_rows",
@@ -76,8 +56,12 @@ def _called(name, text):
 def test_every_entry_point_is_called_by_a_gpu_test_or_listed():
     names, text = _declared(), _gpu_test_sources()
     missing = [n for n in names if not _called(n, text) and n not in INFRASTRUCTURE and n not in INDIRECT]
-    assert not missing, (f"no tests/test_gpu_*.py calls {missing}: add a kernel-level test (preferred), or list the name in INDIRECT with the "
-                         "model-level test that covers it")
+    assert not missing, (f"no tests/test_gpu_*.py calls {missing}: add a kernel-level test, or, for an entry point without arithmetic of its "
+                         "own, list the name in INFRASTRUCTURE with the reason")
+
+
+def test_no_entry_point_is_covered_only_indirectly():
+    assert not INDIRECT, f"{sorted(INDIRECT)}: a model-level test is no cover for an entry point: call it directly in a tests/test_gpu_*.py"
 
 
 def test_the_tables_are_current():

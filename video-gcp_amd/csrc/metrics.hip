@@ -69,15 +69,17 @@ __global__ void __launch_bounds__(256) image_metrics_kernel(const float* __restr
     }
 }
 
-// per sequence b: mean over its frames [first, last) of the per-frame metrics -> mse, psnr, ssim
+// per sequence b: mean over its frames [first, last) of the per-frame metrics -> mse, psnr, ssim.  A frame whose frame_map entry is
+// negative is skipped: it is in no sum and not in the count (a sequence with every frame skipped reports NaN, like an empty range)
 __global__ void sequence_metrics_kernel(const double* __restrict__ sq_part, const double* __restrict__ ssim_part,
-                                        const int* __restrict__ first, const int* __restrict__ last, const int T, const int C,
+                                        const int* __restrict__ frame_map, const int* __restrict__ first, const int* __restrict__ last, const int T, const int C,
                                         const long long elems_per_frame, float* __restrict__ out) {
     const int b = blockIdx.x;
     if (threadIdx.x != 0) return;
     double sq = 0.0, ps = 0.0, ss = 0.0;
     int n = 0;
     for (int t = first[b]; t < last[b]; ++t) {
+        if (frame_map && frame_map[(size_t)b * T + t] < 0) continue;
         double fsq = 0.0, fss = 0.0;
         for (int c = 0; c < C; ++c) {
             fsq += sq_part[((size_t)b * T + t) * C + c];
@@ -107,7 +109,8 @@ extern "C" int gcpx_image_metrics(const float* est, const float* tgt, const int3
     double* sq = scratch;
     double* ss = scratch + (size_t)B * T * C;
     hipLaunchKernelGGL(image_metrics_kernel, dim3(B * T, C), dim3(256), lds, stream, est, tgt, frame_map, C, H, W, sq, ss);
-    hipLaunchKernelGGL(sequence_metrics_kernel, dim3(B), dim3(64), 0, stream, sq, ss, first, last, T, C, (long long)C * H * W, out);
+    hipLaunchKernelGGL(sequence_metrics_kernel, dim3(B), dim3(64), 0, stream, sq, ss, frame_map, first, last, T, C,
+                       (long long)C * H * W, out);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

@@ -211,12 +211,13 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restric
 }
 
 // nxt[i][t] = lat[i][t+1] for t+1 < len_i, else the goal latent: second argument rows of the learned pairwise cost
-// (LearnedCostEstimate list branch, cost_fcn.py:88-95: pairs of torch.cat((seq, goal)))
+// (LearnedCostEstimate list branch, cost_fcn.py:88-95: pairs of torch.cat((seq, goal))).  len_i is clamped to T as in
+// masked_row_sum_kernel / rollout_cost_kernel: a longer length must not make row T-1 read lat[i][T], the next candidate's first row
 __global__ void seq_pairs_kernel(const float* __restrict__ lat, const int32_t* __restrict__ lengths,
                                  const float* __restrict__ goal, float* __restrict__ nxt, const int T, const int nz4) {
     const int it = blockIdx.x;
     const int i = it / T, t = it % T;
-    const int len = lengths[i];
+    const int len = min(lengths[i], T);
     const float4* src;
     if (t + 1 < len) src = reinterpret_cast<const float4*>(lat) + ((size_t)i * T + t + 1) * nz4;
     else if (goal) src = reinterpret_cast<const float4*>(goal) + (size_t)i * nz4;
