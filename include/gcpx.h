@@ -849,7 +849,11 @@ int gcpx_event_destroy(void* ev);
  *   row r = (b, j), b = r / rpb:  score[h][t] = q[r][h] . k[b][t][h] / sqrt(dk / heads) / temperature[0],
  *   frames outside [start_ind[b], end_ind[b]] masked out, softmax over t, out[r][h] = sum_t a[h][t] v[b][t][h].
  *   q [M][dk], k [B][T][dk], v [B][T][nz], out [M][nz] dense; att [M][T] = head-averaged weights or NULL;
- *   start_ind NULL = 0. */
+ *   start_ind NULL = 0.  Caller's contract: end_ind[b] in [0, inf) — an end_ind at or beyond T is clamped to T - 1; start_ind[b] >= 0.
+ *   Keys and values outside the window are never used (the value rows outside it are not read).
+ *   A row whose window is empty (start_ind[b] > end_ind[b], or start_ind[b] >= T) is a softmax over nothing: every element of
+ *   out[r] and att[r] is NaN, what the reference's masking (scores outside the window at -inf, then softmax) gives; the other
+ *   rows of the launch are not affected. */
 int gcpx_attention(const float* q, const float* k, const float* v, const int64_t* start_ind, const int64_t* end_ind,
                    const float* temperature, float* out, float* att, int32_t M, int32_t rpb, int32_t T, int32_t dk, int32_t nz,
                    int32_t heads, void* stream);
@@ -866,7 +870,11 @@ int gcpx_cdist(const float* x, const float* y, int32_t B, int32_t N, int32_t T, 
  *   cost[b][n][t] = (dsum[b][n][t] / D) / temp[0]  ('mean' reduction of the cdist, then the matching temperature);
  *   w[b][n][t] = P(node n is aligned with frame t) under the Gibbs distribution over monotone alignments without horizontal
  *   moves that start at (0, 0) and end at (N-1, end_ind[b]), divided by max(sum over nodes, 1e-7).  Depth-first node order.
- *   acc: caller-owned scratch, float64 [2*B][N][T] (forward and backward accumulators).  Needs N >= T, T <= 1024. */
+ *   acc: caller-owned scratch, float64 [2*B][N][T] (forward and backward accumulators, both in the orientation of dsum; -inf where
+ *   no alignment reaches).  Every cell of acc and w is written; columns beyond end_ind[b] of w are exact zeros.
+ *   Needs N >= T, T <= 1024 (GCPX_ERR_UNSUPPORTED beyond, nothing written).
+ *   Caller's contract: end_ind[b] in [0, T-1].  It is used as a column index without a check; a value outside is an out-of-bounds
+ *   read.  The same holds for gcpx_soft_dtw_dtemp. */
 int gcpx_soft_dtw(const float* dsum, float D, const float* temp, const int64_t* end_ind, int32_t B, int32_t N, int32_t T,
                   double* acc, float* w, void* stream);
 
@@ -908,7 +916,9 @@ int gcpx_soft_average(const float* w, const float* x, float* out, int32_t B, int
  *   cost [B][N][T] float32 (mean squared distance estimate n vs target t); sequence b uses rows < n_len[b] and columns < t_len[b]
  *   (NULL = N / T).  acc [B][N][T] float64 accumulated cost; inds [B][T] = for every target frame the estimate with the smallest
  *   accumulated cost among the path cells of its column (-1 beyond t_len); path [B][2][N+T] = (rows | columns) from the END of
- *   the path to its start, path_len [B]; dist [B] = acc[n-1][t-1] / (n + t). */
+ *   the path to its start, path_len [B]; dist [B] = acc[n-1][t-1] / (n + t).
+ *   Caller's contract: 1 <= n_len[b] <= N and 1 <= t_len[b] <= T (not checked).  Cells of acc outside n_len[b] x t_len[b] and
+ *   entries of path beyond path_len[b] are not written. */
 int gcpx_dtw_align(const float* cost, const int32_t* n_len, const int32_t* t_len, int32_t B, int32_t N, int32_t T, double* acc,
                    int32_t* inds, int32_t* path, int32_t* path_len, double* dist, void* stream);
 

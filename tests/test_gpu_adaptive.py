@@ -26,6 +26,24 @@ def _st():
     return torch.cuda.current_stream().cuda_stream
 
 
+ISENT = -77                                                 # fill of integer outputs; float outputs start as NaN
+
+
+def _nan(*shape, dtype=torch.float32):
+    return torch.full(shape, float("nan"), dtype=dtype, device="cuda")
+
+
+def _isent(*shape):
+    return torch.full(shape, ISENT, dtype=torch.int32, device="cuda")
+
+
+def _all_written(**outs):
+    """every element of an output that started as NaN (floats) or ISENT (integers) has been written"""
+    for name, t in outs.items():
+        left = torch.isnan(t) if t.is_floating_point() else (t == ISENT)
+        assert not bool(left.any()), f"{name}: {int(left.sum())} elements never written"
+
+
 @pytest.mark.parametrize("i", range(int(G["sd_n"])))
 def test_soft_dtw_kernel_matches_reference_goldens(i):
     """cost -> forward accumulator (float64) and normalised expected edge frequencies, against outputs of the reference's
@@ -34,12 +52,12 @@ def test_soft_dtw_kernel_matches_reference_goldens(i):
     rt, lib = _lib()
     cost, end = torch.tensor(G[f"sd{i}_cost"]), torch.tensor(G[f"sd{i}_end"])
     B, N, T = cost.shape
-    acc = torch.zeros(2 * B, N, T, dtype=torch.float64, device="cuda")
-    w = torch.zeros(B, N, T, device="cuda")
+    acc, w = _nan(2 * B, N, T, dtype=torch.float64), _nan(B, N, T)
     one, cd, ed = torch.ones(1, device="cuda"), cost.cuda(), end.cuda()
     rt.check(lib.gcpx_soft_dtw(cd.data_ptr(), 1.0, one.data_ptr(), ed.data_ptr(), B, N, T, acc.data_ptr(), w.data_ptr(), _st()),
              "soft_dtw")
     torch.cuda.synchronize()
+    _all_written(acc=acc, w=w)
     fwd, ref = acc[:B].cpu().numpy(), G[f"sd{i}_fwd"]
     assert np.array_equal(np.isinf(fwd), np.isinf(ref))
     fin = ~np.isinf(ref)
@@ -78,16 +96,15 @@ def test_soft_dtw_temperature_gradient_kernel(i):
     w = A.normalize(A.soft_dtw_autograd((dsum / D) / temp, end), 1)
     val = 0.5 * dsum * torch.exp(-ls) ** 2 + D * (ls + 0.5 * math.log(2 * math.pi))
     (want,) = torch.autograd.grad(coef * (val * w * pad[:, None]).sum(), temp)
-    acc = torch.zeros(2 * B, N, T, dtype=torch.float64, device="cuda")
-    tan = torch.full((2 * B, N, T), float("nan"), dtype=torch.float64, device="cuda")
-    part = torch.zeros(B, dtype=torch.float64, device="cuda")
-    wd = torch.zeros(B, N, T, device="cuda")
+    acc, tan = _nan(2 * B, N, T, dtype=torch.float64), _nan(2 * B, N, T, dtype=torch.float64)
+    part, wd = _nan(B, dtype=torch.float64), _nan(B, N, T)
     tp, dd, ed, pd_, lsd = temp.detach().cuda(), dsum.cuda(), end.cuda(), pad.cuda(), ls.cuda()
     got = torch.full((1,), 0.25, device="cuda")                       # the kernel ACCUMULATES into the gradient slot
     rt.check(lib.gcpx_soft_dtw(dd.data_ptr(), D, tp.data_ptr(), ed.data_ptr(), B, N, T, acc.data_ptr(), wd.data_ptr(), _st()), "soft_dtw")
     rt.check(lib.gcpx_soft_dtw_dtemp(dd.data_ptr(), D, tp.data_ptr(), ed.data_ptr(), acc.data_ptr(), pd_.data_ptr(), lsd.data_ptr(), coef,
                                      B, N, T, tan.data_ptr(), part.data_ptr(), got.data_ptr(), _st()), "soft_dtw_dtemp")
     torch.cuda.synchronize()
+    _all_written(acc=acc, tan=tan, part=part, w=wd)
     assert_close(wd, w.detach(), 2e-6, 0, "w")
     g = float(got) - 0.25
     assert abs(float(want)) > 1e-3
@@ -110,11 +127,11 @@ def test_soft_dtw_full_size_properties():
     end = torch.tensor([199, 57, 120])
     temp = torch.tensor([0.7])
     D = 12288.0
-    acc = torch.zeros(2 * B, N, T, dtype=torch.float64, device="cuda")
-    w = torch.zeros(B, N, T, device="cuda")
+    acc, w = _nan(2 * B, N, T, dtype=torch.float64), _nan(B, N, T)
     dd, td, ed = dsum.cuda(), temp.cuda(), end.cuda()
     rt.check(lib.gcpx_soft_dtw(dd.data_ptr(), D, td.data_ptr(), ed.data_ptr(), B, N, T, acc.data_ptr(), w.data_ptr(), _st()), "soft_dtw")
     torch.cuda.synchronize()
+    _all_written(acc=acc, w=w)
     want = A.normalize(torch.from_numpy(A.soft_dtw(((dsum / D) / temp).numpy(), end.numpy())), 1)
     assert_close(w, want, 2e-6, 1e-5, "w")
     for b in range(B):
@@ -134,12 +151,12 @@ def test_cdist_kernel(shape):
     x, y = torch.rand(B, N, K, generator=g) * 2 - 1, torch.rand(B, T, K, generator=g) * 2 - 1
     y[0, 0] = x[0, 0]                                          # an exact match: distance clamps at >= 0
     ns = lib.gcpx_cdist_splits(K)
-    part = torch.zeros(ns, B, N, T, device="cuda")
-    xn, yn, out = torch.zeros(B * N, device="cuda"), torch.zeros(B * T, device="cuda"), torch.zeros(B, N, T, device="cuda")
+    part, xn, yn, out = _nan(ns, B, N, T), _nan(B * N), _nan(B * T), _nan(B, N, T)
     xd, yd = x.cuda(), y.cuda()
     rt.check(lib.gcpx_cdist(xd.data_ptr(), yd.data_ptr(), B, N, T, K, part.data_ptr(), xn.data_ptr(), yn.data_ptr(),
                             out.data_ptr(), _st()), "cdist")
     torch.cuda.synchronize()
+    _all_written(partial=part, xnorm=xn, ynorm=yn, out=out)
     want = A.batch_cdist(x, y, "sum")
     scale = float((x ** 2).sum(-1).max())
     assert_close(out, want, 2e-6 * scale, 0, "cdist")
@@ -165,11 +182,12 @@ def test_attention_kernel(heads):
     sd["a.temperature"] = torch.tensor([0.8])
     rep = lambda t: t.repeat_interleave(n, 0)
     want_o, want_a = A.multihead_attention(sd, "a", hp, q, rep(k), rep(v), torch.zeros(M, dtype=torch.long), rep(end))
-    out, att = torch.zeros(M, nz, device="cuda"), torch.zeros(M, T, device="cuda")
+    out, att = _nan(M, nz), _nan(M, T)
     qd, kd, vd, ed, td = q.cuda(), k.cuda(), v.cuda(), end.cuda(), sd["a.temperature"].cuda()
     rt.check(lib.gcpx_attention(qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), None, ed.data_ptr(), td.data_ptr(), out.data_ptr(),
                                 att.data_ptr(), M, n, T, dk, nz, heads, _st()), "attention")
     torch.cuda.synchronize()
+    _all_written(out=out, att=att)
     assert_close(att, want_a, 1e-6, 1e-5, "attention weights")
     assert_close(out, want_o, 1e-5, 1e-5, "attention output")
 
@@ -186,12 +204,13 @@ def test_match_stats_prune_and_averaging_kernels():
     w[0, 3, 2] = w[0, 7, 2] = 2.0                        # a tie: the first maximum in BREADTH-first order (the root, df 7) wins
     w = w / w.sum(1, keepdim=True).clamp_min(1e-7)
     end = torch.tensor([8, 8, 5])
-    f2n, midx = torch.zeros(B, T, dtype=torch.int32, device="cuda"), torch.zeros(B, T, dtype=torch.int32, device="cuda")
-    best = torch.zeros(B, N, dtype=torch.int32, device="cuda")
-    ent, pn = torch.zeros(B, N, device="cuda"), torch.zeros(B, N, device="cuda")
+    f2n, midx, best = _isent(B, T), _isent(B, T), _isent(B, N)
+    ent, pn = _nan(B, N), _nan(B, N)
     wd, ed = w.cuda(), end.cuda()
     rt.check(lib.gcpx_match_stats(wd.data_ptr(), ed.data_ptr(), B, L, T, f2n.data_ptr(), midx.data_ptr(), best.data_ptr(),
                                   ent.data_ptr(), pn.data_ptr(), _st()), "match_stats")
+    torch.cuda.synchronize()
+    _all_written(frame2node=f2n, matched_idx=midx, best_t=best, entropy=ent, p_n=pn)
     w_bf = O._bf_of_df(w, L)
     from oracle import tree_index_oracle as TI
     want_f2n = TI.bf2df_perm(L)[w_bf.argmax(1).numpy()]
@@ -203,11 +222,12 @@ def test_match_stats_prune_and_averaging_kernels():
     assert_close(pn, w.sum(2).clamp(0, 1), 1e-6, 0, "p_n")
     # learned pruning + BCE targets
     dist = torch.randn(B, N - 1, generator=g)
-    leave, kept = torch.zeros(B, N, dtype=torch.int32, device="cuda"), torch.zeros(B, N, dtype=torch.int32, device="cuda")
-    cnt, tgt = torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros(B, N - 1, dtype=torch.int32, device="cuda")
+    leave, kept, cnt, tgt = _isent(B, N), _isent(B, N), _isent(B), _isent(B, N - 1)
     dd = dist.cuda()
     rt.check(lib.gcpx_distance_prune(dd.data_ptr(), 0.5, best.data_ptr(), B, N, leave.data_ptr(), kept.data_ptr(),
                                      cnt.data_ptr(), tgt.data_ptr(), _st()), "distance_prune")
+    torch.cuda.synchronize()
+    _all_written(leave=leave, kept_idx=kept, count=cnt, target=tgt)
     close = torch.cat([torch.zeros(B, 1, dtype=torch.bool), torch.sigmoid(dist) > 0.5], 1)
     assert torch.equal(leave.cpu().bool(), ~close)
     for b in range(B):
@@ -217,17 +237,20 @@ def test_match_stats_prune_and_averaging_kernels():
     assert torch.equal(tgt.cpu().bool(), bt[:, 1:] == bt[:, :-1])
     # averaging loss rows and the soft average
     dsum, ls = torch.rand(B, N, T, generator=g) * 50, torch.tensor([0.3])
-    nll = torch.zeros(B, T, device="cuda")
+    nll = _nan(B, T)
     dsd, lsd = dsum.cuda(), ls.cuda()
     rt.check(lib.gcpx_averaging_nll(dsd.data_ptr(), wd.data_ptr(), lsd.data_ptr(), float(D), B, N, T, nll.data_ptr(),
                                     _st()), "averaging_nll")
+    torch.cuda.synchronize()
+    _all_written(nll=nll)
     want = ((0.5 * dsum * torch.exp(-ls) ** 2 + D * (ls + 0.5 * math.log(2 * math.pi))) * w).sum(1)
     assert_close(nll, want, 1e-4, 1e-5, "averaging nll")
     x = torch.randn(B, N, D, generator=g)
-    avg = torch.zeros(B, T, D, device="cuda")
+    avg = _nan(B, T, D)
     xd = x.cuda()
     rt.check(lib.gcpx_soft_average(wd.data_ptr(), xd.data_ptr(), avg.data_ptr(), B, N, T, D, _st()), "soft_average")
     torch.cuda.synchronize()
+    _all_written(avg=avg)
     assert_close(avg, torch.einsum("bnt,bnd->btd", w, x), 1e-5, 1e-5, "soft average")
 
 
@@ -343,16 +366,16 @@ def test_dtw_align_kernel_matches_reference_goldens():
         C = torch.tensor(C64.astype(np.float32))
         n, t = C.shape
         cd = C[None].contiguous().cuda()
-        acc = torch.zeros(1, n, t, dtype=torch.float64, device="cuda")
-        inds = torch.zeros(1, t, dtype=torch.int32, device="cuda")
-        path = torch.zeros(1, 2, n + t, dtype=torch.int32, device="cuda")
-        plen, dist = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.float64, device="cuda")
+        acc, inds, path = _nan(1, n, t, dtype=torch.float64), _isent(1, t), _isent(1, 2, n + t)
+        plen, dist = _isent(1), _nan(1, dtype=torch.float64)
         rt.check(lib.gcpx_dtw_align(cd.data_ptr(), None, None, 1, n, t, acc.data_ptr(), inds.data_ptr(), path.data_ptr(),
                                     plen.data_ptr(), dist.data_ptr(), _st()), "dtw_align")
         torch.cuda.synchronize()
         d_ref, D_ref, path_ref, inds_ref = A.dtw_matches(C.numpy())       # float32 costs, float64 accumulation
         assert np.max(np.abs(acc[0].cpu().numpy() - D_ref)) < 1e-12
         L = int(plen[0])
+        _all_written(acc=acc, inds=inds, path=path[0, :, :L], path_len=plen, dist=dist)
+        assert bool((path[0, :, L:] == ISENT).all())               # nothing behind the path's end
         got_p = path[0, :, :L].cpu().numpy()[:, ::-1]
         assert np.array_equal(got_p[0], path_ref[0]) and np.array_equal(got_p[1], path_ref[1])
         assert np.array_equal(inds[0].cpu().numpy(), inds_ref) and abs(float(dist[0]) - d_ref) < 1e-12

@@ -104,6 +104,8 @@ __global__ void __launch_bounds__(256) attention_kernel(const float* __restrict_
                 const float4 x = reinterpret_cast<float4*>(part)[g * c4n + tid];
                 o.x += x.x; o.y += x.y; o.z += x.z; o.w += x.w;
             }
+            // an empty window (start > end) is a softmax over nothing: NaN like its weights, not the 0 of the empty value loop
+            if (!(sum > 0.f)) o = make_float4(NAN, NAN, NAN, NAN);
             *reinterpret_cast<float4*>(out + (size_t)r * nz + h * vh + tid * 4) = o;
         }
         __syncthreads();
