@@ -131,9 +131,137 @@ def _exec_with_placeholders(path, name):
     return ns
 
 
+# ---- the key table: every key of the reference's hyper-parameter tables is mapped, value-checked, inert or unbuilt ---------------------
+# Groups follow the reference's `_default_hparams` functions (tests/golden/ref_hparam_defaults.json holds their keys and defaults):
+#   model    hyperparameters.py:4-150 + base_model.py:34-64      (model_config, policy.params)
+#   inv_mdl  inverse_mdl.py:32-73   cost_mdl  cost_mdl.py:26-50   (model_config's inv_mdl_params / cost_mdl_params)
+#   trainer  gcp_builder.py:249-272                               (configuration)
+#   policy   planner_policy.py:69-86,136-145,194-202   cem  cem_planner.py:24-53,173-192   (a control conf's policy / cem_params)
+# Per group:  mapped   a GCPHParams field, or a key this loader translates;
+#             checked  {key: allowed values}: settled by what this build implements;
+#             inert    {key: reason}: cannot change what is computed; still reported in `ignored`;
+#             unbuilt  {key: the reference's default}: any other value raises -- the feature is not built, and training or planning with a
+#                      different model silently is worse than stopping.
+# A key in none of the four raises as unknown.  (The reference's own "an override equal to the default raises" rule,
+# base_model.py:27-32, is not copied: a conf may restate a default.)
+INF = float("inf")
+_LEARNED_COSTS = ("LearnedCostEstimate", "ImageLearnedCostEstimate", "ImageWrappedLearnedCostFcn")
+_HAND_COSTS = ("EuclideanDistance", "EuclideanPathLength", "StepPathLength", "L2ImageCost")
+_HIERARCHICAL_SAMPLERS = ("ImageHierarchicalTreeCEMSampler", "HierarchicalTreeCEMSampler")
+_FLAT_SAMPLERS = ("SimpleTreeCEMSampler", "FlatCEMSampler", "PDDMSampler")
+_PLANNER_CLASSES = (None, "HierarchicalImageCEMPlanner", "HierarchicalCEMPlanner", "ImageCEMPlanner", "CEMPlanner")
+_FIXED = {"one_step_planner": ("sh_pred", "continuous"), "binding": ("loss",),
+          "dense_rec_type": ("node_prob", "svg", "none", None)}
+_MODEL_CHECKED = dict(_FIXED, tree_lstm=("split_linear", "linear", "sum", "", None), add_weighted_pixel_copy=(False,))
+KEY_TABLE = {
+    "model": dict(
+        mapped=(set(GCPHParams.__dataclass_fields__) - set(_MODEL_CHECKED)) | {"inv_mdl_params", "cost_mdl_params"},
+        checked=_MODEL_CHECKED,
+        inert=dict(randomize_length="dataset", randomize_start="dataset", device="placement", dump_encodings="logging",
+                   dump_encodings_inv_model="logging", log_states_2d="logging", log_cartgripper="logging", data_dir="logging",
+                   log_d2b_3x3maze="logging", dataset_class="dataset", split="dataset", checkpt_path="resume"),
+        unbuilt=dict(nz_vae2=256, n_conv_layers=None, action_activation=None, dense_action_rec_weight=1.0, pixel_shift_decoder=False,
+                     skip_from_parents=False, regress_actions=False, learn_attn_temp=True, learn_beta=True, initial_sigma=1.0,
+                     separate_cnn_start_goal_encoder=False, use_conv_lstm=False, one_hot_attn_time_cond=False,
+                     matching_temp_tenthlife=-1, matching_temp_min=1e-3, n_top_bias_nodes=1, supervise_match_weight=0.0,
+                     regress_index=False, act_cond_inference=False, train_on_action_seqs=False, states_inference=False,
+                     mask_inf_attention=False, use_convs=True, use_batchnorm=True, normalization="batch",
+                     predictor_normalization="group", filter_repeated_tail=False, rep_tail=False, standardize=None, subsampler=None,
+                     subsample_args=None)),
+    # the inverse model runs on the predictor's latents (base_gcp.py builds it with build_encoder=False, use_convs=False)
+    "inv_mdl": dict(
+        mapped={"n_actions", "temp_dist"},
+        checked=dict(use_convs=(False,), build_encoder=(False,)),
+        inert=dict(device="placement", log_topdown_maze="logging", randomize_length="dataset", dataset_class="dataset", split="dataset",
+                   checkpt_path="resume", batch_size="parent", max_seq_len="parent", state_dim="parent", img_sz="parent",
+                   input_nc="parent"),
+        unbuilt=dict(ngf=4, nz_enc=128, nz_mid=128, n_processing_layers=3, enc_params_checkpoint=None, take_first_tstep=False,
+                     use_states=False, aggregate_actions=False, pred_states=False, finetune_enc=False, add_lstm_state_enc=False,
+                     train_full_seq=False, train_im0_enc=True, action_rec_weight=1.0, state_rec_weight=1.0, use_skips=False,
+                     dense_rec_type=None, n_conv_layers=None, use_batchnorm=True, normalization="batch",
+                     predictor_normalization="group", filter_repeated_tail=False, rep_tail=False, standardize=None, subsampler=None,
+                     subsample_args=None)),
+    "cost_mdl": dict(
+        mapped=set(),
+        checked=dict(use_path_dist_cost=(False,), cost_fcn=(None, "EuclideanPathLength"), use_convs=(False,)),
+        inert=dict(device="placement", randomize_length="dataset", dataset_class="dataset", split="dataset", checkpt_path="weights",
+                   load_epoch="weights", batch_size="parent", max_seq_len="parent", state_dim="parent", img_sz="parent",
+                   input_nc="parent", n_actions="parent"),
+        unbuilt=dict(nz_enc=128, nz_mid=128, n_processing_layers=3, use_skips=False, dense_rec_type=None, n_conv_layers=None,
+                     use_batchnorm=True, normalization="batch", predictor_normalization="group", filter_repeated_tail=False,
+                     rep_tail=False, standardize=None, subsampler=None, subsample_args=None)),
+    "trainer": dict(
+        mapped={"model", "batch_size", "lr", "num_epochs", "adam_beta", "epoch_cycles_train", "seed", "gradient_clip", "top_of_100_eval",
+                "metric_pruning_scheme", "optimizer", "momentum"},
+        checked={},
+        inert=dict(logger="logging", dataset_name="dataset", exp_path="path", n_rooms="logging", data_dir="dataset",
+                   randomize_length="dataset", randomize_start="dataset"),
+        unbuilt={}),
+    "policy": dict(
+        mapped={"type", "params", "model_cls", "checkpt_path", "load_epoch", "cem_params", "replan_interval", "num_max_replans",
+                "closed_loop_execution"},
+        checked=dict(cem_planner=_PLANNER_CLASSES),
+        inert=dict(logger="logging", verbose="logging", max_dump_rollouts="logging", ncam="cameras"),
+        unbuilt=dict(act_cond=False)),
+    "cem": dict(
+        mapped={"horizon", "action_dim", "n_iters", "batch_size", "elite_frac", "cost_fcn", "cost_config", "dense_cost",
+                "final_step_cost_weight", "sampler", "sampler_clip_val", "initial_std", "verbose", "max_seq_len", "n_level_hierarchy",
+                "sampling_rates_per_layer", "n_ll_samples"},
+        checked={},
+        # prune_final: set by every shipped control conf, read nowhere in the reference.  max_rollout_bs: how the reference chunks a
+        # population; this build evaluates every candidate (planning.py, deviation D2)
+        inert=dict(prune_final="unread", max_rollout_bs="chunking", dump_planning_data="logging"),
+        unbuilt=dict(LL_cost_fcn=None, use_delta_state_actions=False, use_inferred_actions=True)),
+}
 # trainer keys (gcp_builder.py:_default_hparams) that the device trainer reads
 _TRAINER_KEYS = ("batch_size", "lr", "num_epochs", "adam_beta", "epoch_cycles_train", "seed", "gradient_clip", "top_of_100_eval",
                  "metric_pruning_scheme", "optimizer", "momentum")
+
+
+def class_name(v):
+    """a class in a conf arrives as a named placeholder (or, from a JSON fixture, as its name): the bare class name; None stays None"""
+    if v is None or isinstance(v, (bool, int, float, dict, list, tuple)):
+        return v
+    name = v if isinstance(v, str) else getattr(v, "__name__", repr(v))
+    return name.rsplit(".", 1)[-1]
+
+
+def key_classes(group, key):
+    """the classes of the group's table that hold `key`: exactly one for every key of the reference"""
+    return [c for c in ("mapped", "checked", "inert", "unbuilt") if key in KEY_TABLE[group][c]]
+
+
+def _same(v, default):
+    """a conf's value equals the reference's default (classes by name; an empty dict / list equals any empty one; True is not 1)"""
+    v = class_name(v)
+    if isinstance(v, (dict, list, tuple)) or isinstance(default, (dict, list, tuple)):
+        return v == default or (not v and not default)
+    if isinstance(v, bool) != isinstance(default, bool):
+        return False
+    return v == default
+
+
+def screen_keys(group, d, where):
+    """Every key of dict `d` against the group's table.  Returns the keys that take no part (inert ones, unbuilt ones at the reference's
+    default); raises ValueError for an unknown key, a checked key with a value that is not built, and an unbuilt key off its default."""
+    t = KEY_TABLE[group]
+    passed = []
+    for k, v in d.items():
+        if k in t["mapped"]:
+            continue
+        if k in t["checked"]:
+            if class_name(v) not in t["checked"][k]:
+                raise ValueError(f"{where}[{k!r}] = {v!r}: only {t['checked'][k]} is built")
+        elif k in t["inert"]:
+            passed.append(k)
+        elif k in t["unbuilt"]:
+            if not _same(v, t["unbuilt"][k]):
+                raise ValueError(f"{where}[{k!r}] = {v!r}: not built (only the reference's default, {t['unbuilt'][k]!r}, is); "
+                                 "a different model would be run silently otherwise")
+            passed.append(k)
+        else:
+            raise ValueError(f"{where}[{k!r}]: unknown key (in none of the reference's hyper-parameter tables, and no field of this build)")
+    return passed
 
 
 def model_kind(configuration):
@@ -142,40 +270,37 @@ def model_kind(configuration):
     v = configuration.get("model", "TreeModel")
     name = v if isinstance(v, str) else getattr(v, "__name__", repr(v))
     return "sequential" if "sequential" in name.lower() else "tree"
-# model_config keys that are settled by what this build implements (checked, not mapped)
-_FIXED = {"one_step_planner": ("sh_pred", "continuous"), "binding": ("loss",),
-          "dense_rec_type": ("node_prob", "svg", "none", None)}
 
 
 def hparams_from_conf(configuration, model_config, **over):
     """(GCPHParams, trainer settings, ignored keys).  max_seq_len / img_sz come from the dataset spec in the reference
-    (data_loader.py); here they are overrides or the c2 defaults (T=80, 64x64)."""
+    (data_loader.py); here they are overrides or the c2 defaults (T=80, 64x64).  Every key goes through KEY_TABLE (above)."""
     fields = set(GCPHParams.__dataclass_fields__)
     kw, ignored = {}, []
     mc = dict(model_config)
-    for k, allowed in _FIXED.items():
-        if k in mc and mc[k] not in allowed:
-            raise ValueError(f"model_config[{k!r}] = {mc[k]!r}: only {allowed} is built")
-        mc.pop(k, None)
     if (mc.get("tree_lstm", "split_linear") or "") not in ("split_linear", "linear", "sum", ""):      # tree_lstm.py:52-60; '' / None = the
         raise ValueError(f"model_config['tree_lstm'] = {mc['tree_lstm']!r}: split_linear, linear, sum and '' are built")   # non-LSTM predictor
-    if mc.pop("add_weighted_pixel_copy", False):
+    if mc.get("add_weighted_pixel_copy", False):
         # hyperparameters.py:54; base_configs/base_tree.py and gcp_sequential.py set it, every room conf pops it again
         # (25room/gcp_tree/conf.py:43).  A conf that keeps it asks for a decoder with a pixel-copy stream, which is not built: training
         # a different decoder silently is worse than stopping
         raise ValueError("model_config['add_weighted_pixel_copy'] = True: the weighted pixel-copy decoder stream is not built "
                          "(the 25-room / 9-room confs pop the key: `model_config.pop('add_weighted_pixel_copy')`)")
+    if (mc.get("cost_mdl_params") or {}).get("use_path_dist_cost"):
+        raise ValueError("cost_mdl_params.use_path_dist_cost: the fast path needs state sequences; image trajectories use the "
+                         "generic cost (cost_mdl.py:81-117)")
+    unused = set(screen_keys("model", mc, "model_config"))
+    for k in list(_FIXED) + ["add_weighted_pixel_copy"]:
+        mc.pop(k, None)
     inv = mc.pop("inv_mdl_params", None) or {}
+    screen_keys("inv_mdl", inv, "model_config['inv_mdl_params']")
     if "n_actions" in inv:
         kw["n_actions"] = int(inv["n_actions"])
     if "temp_dist" in inv:
         kw["inv_mdl_temp_dist"] = int(inv["temp_dist"])
-    cost = mc.pop("cost_mdl_params", None) or {}
-    if cost.get("use_path_dist_cost"):
-        raise ValueError("cost_mdl_params.use_path_dist_cost: the fast path needs state sequences; image trajectories use the "
-                         "generic cost (cost_mdl.py:81-117)")
+    screen_keys("cost_mdl", mc.pop("cost_mdl_params", None) or {}, "model_config['cost_mdl_params']")
     for k, v in mc.items():
-        if k in fields:
+        if k in fields and k not in unused:
             kw[k] = v
         else:
             ignored.append(k)
@@ -187,6 +312,7 @@ def hparams_from_conf(configuration, model_config, **over):
     if kw.get("hierarchy_levels", 1) == 0:
         kw.pop("hierarchy_levels")        # the flat model's base config (base_configs/gcp_sequential.py) has no tree
     hp = GCPHParams(**kw)
+    screen_keys("trainer", configuration, "configuration")
     trainer = {k: configuration[k] for k in _TRAINER_KEYS if k in configuration}
     trainer["model"] = model_kind(configuration)
     ignored += [k for k in configuration if k not in _TRAINER_KEYS and k != "model"]
@@ -218,3 +344,215 @@ def load_conf(exp_dir, default="c2", name=None, **over):
             tr["model"] = model_kind(tr)
             return hp, tr, []
     return named_config(name or default, **over), {}, []
+
+
+# ---- control configurations: the reference's run.py <experiments/control/*/mod_hyper.py> -----------------------------------------------
+def exec_control_conf(path, environ=None):
+    """Run a reference-style `mod_hyper.py` (gcp/planning/run.py loads it and reads `config`) under the placeholder imports of
+    exec_conf_py; returns its `config` as plain dicts, classes as named placeholders.  The shipped files read
+    os.environ['GCP_DATA_DIR'] / ['GCP_EXP_DIR'] while they execute: the names given in `environ` are visible to the conf during the
+    execution only (the process environment is restored afterwards), and a name found in neither place raises ValueError."""
+    saved = dict(os.environ)
+    try:
+        os.environ.update({k: str(v) for k, v in (environ or {}).items()})
+        try:
+            ns = _exec_with_placeholders(path, "mod_hyper")
+        except KeyError as e:
+            name = e.args[0] if e.args else None
+            tb = e.__traceback__
+            while tb.tb_next is not None:
+                tb = tb.tb_next
+            if isinstance(name, str) and tb.tb_frame.f_code.co_filename == os.__file__:          # raised by os.environ[name]
+                raise ValueError(f"{path}: the configuration reads the environment variable {name}, which is not set "
+                                 f"(give it through `environ`, or --data_dir / --exp_dir of the planner)") from None
+            raise
+    finally:
+        for k in [k for k in os.environ if k not in saved]:
+            del os.environ[k]
+        os.environ.update(saved)
+    if "config" not in ns:
+        raise ValueError(f"{path}: a control configuration defines `config` (gcp/planning/run.py)")
+    return _plain(ns["config"])
+
+
+def _plain(v):
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return [_plain(x) for x in v]
+    if isinstance(v, tuple):
+        return tuple(_plain(x) for x in v)
+    return v
+
+
+def _resolve_weights(path, epoch):
+    """the weights file of a checkpoint directory (checkpoint_handler.py:31-42), None when it does not resolve"""
+    from .checkpoint import get_resume_ckpt_file, NoCheckpointsException
+    if not path or not os.path.isdir(path):
+        return None
+    try:
+        f = get_resume_ckpt_file("latest" if epoch is None else epoch, path)
+    except NoCheckpointsException:
+        return None
+    return f if os.path.isfile(f) else None
+
+
+def planner_from_control_conf(config, **over):
+    """A control conf's `config` (exec_control_conf) as a plain description of what to build:
+        hp           GCPHParams of the planner's model (policy.params through hparams_from_conf; `over` overrides fields)
+        model_kind   'tree' / 'sequential' (policy.model_cls, else the tree model: planner_policy.py:36)
+        planner      'hierarchical' (planning.HierarchicalCEMPlanner) or 'flat' (planning.CEMPlanner), decided by cem_params.sampler
+        planner_args keyword arguments of that planner; sampler / sampler_args (flat); cost / cost_args; verbose; horizon
+        policy_args  replan_interval, num_max_replans, closed_loop_execution of planning.ImageCEMPolicy
+        weights      dict(path, epoch, file, cost_path, cost_file): `file` / `cost_file` are None where nothing resolves
+        pairs        (start_index, end_index)
+        ignored      ['<key>:<reason>'] of everything that takes no part
+    Follows planner_policy.py:15-57,69-86,127-145,191-202 and cem_planner.py:24-53,166-218."""
+    ignored = []
+    for k, v in config.items():
+        if k not in ("agent", "policy", "start_index", "end_index"):
+            ignored.append(f"{k}:{'path' if k in ('current_dir', 'data_save_dir') else 'saver'}")
+    agent, policy = dict(config.get("agent") or {}), dict(config.get("policy") or {})
+    ptype = class_name(policy.get("type"))
+    if ptype != "ImageCEMPolicy":
+        raise ValueError(f"policy.type = {ptype}: only ImageCEMPolicy is built (the state-space CEMPolicy and the BC policy are not)")
+    ignored += [f"policy.{k}:{KEY_TABLE['policy']['inert'].get(k, 'default')}" for k in screen_keys("policy", policy, "policy")]
+    for k in agent:
+        if k not in ("T", "image_height", "image_width"):
+            ignored.append(f"agent.{k}:{'simulator' if k == 'env' else 'infrastructure'}")
+
+    # ---- the model (planner_policy.py:30-38) ----
+    params = dict(policy.get("params") or {})
+    H, W = agent.get("image_height"), agent.get("image_width")
+    if H is None or H != W:
+        raise ValueError(f"agent.image_height = {H}, agent.image_width = {W}: the planner's model takes square images")
+    if "img_sz" in params and params["img_sz"] != W:
+        raise ValueError(f"policy.params['img_sz'] = {params['img_sz']} but agent.image_width = {W} (planner_policy.py:38)")
+    params["img_sz"] = int(W)
+    if "max_seq_len" not in params:
+        if "T" not in agent:
+            raise ValueError("max_seq_len is neither in policy.params nor given as agent.T (planner_policy.py:32-33)")
+        params["max_seq_len"] = int(agent["T"])
+    kind = model_kind({"model": policy["model_cls"]} if policy.get("model_cls") is not None else {})
+    hp, _, ign = hparams_from_conf({"batch_size": 1}, params, **over)              # planner_policy.py:30: batch_size 1
+    ignored += [f"policy.params.{k}:{KEY_TABLE['model']['inert'].get(k, 'default')}" for k in ign if k != "batch_size"]
+
+    # ---- the planner (cem_planner.py:24-53,166-218) ----
+    cem = dict(policy.get("cem_params") or {})
+    unused = screen_keys("cem", cem, "cem_params")
+    ignored += [f"cem_params.{k}:{KEY_TABLE['cem']['inert'].get(k, 'default')}" for k in unused]
+    if cem.get("action_dim") != hp.nz_vae:
+        raise ValueError(f"cem_params.action_dim = {cem.get('action_dim')}: the planner samples the model's latents, nz_vae = {hp.nz_vae}")
+    if cem.get("max_seq_len") not in (None, hp.max_seq_len):        # planner_policy.py:132 overwrites it with the model's
+        raise ValueError(f"cem_params.max_seq_len = {cem['max_seq_len']}: the policy sets it to the model's, {hp.max_seq_len}")
+    horizon = cem.get("horizon")
+    if horizon is not None and horizon < hp.max_seq_len:
+        raise ValueError(f"cem_params.horizon = {horizon} < max_seq_len = {hp.max_seq_len}: capping rollouts to a horizon "
+                         "(cem_planner.py:151-155) is not built; at or above max_seq_len it caps nothing")
+    planner_cls = class_name(policy.get("cem_planner"))
+    sampler = class_name(cem.get("sampler", "HierarchicalTreeCEMSampler"))
+    cost = class_name(cem.get("cost_fcn", "LearnedCostEstimate"))
+    if cost not in _LEARNED_COSTS + _HAND_COSTS:
+        raise ValueError(f"cem_params.cost_fcn = {cost}: no counterpart in planning.py ({_LEARNED_COSTS + _HAND_COSTS})")
+    learned = cost in _LEARNED_COSTS
+    n_iters = cem.get("n_iters", 1)
+    clip = cem.get("sampler_clip_val", INF)
+    levels = cem.get("n_level_hierarchy")
+    if sampler in _HIERARCHICAL_SAMPLERS + ("SimpleTreeCEMSampler",):
+        if levels is None:
+            raise ValueError(f"cem_params.sampler = {sampler} needs cem_params.n_level_hierarchy")
+        if levels != hp.hierarchy_levels:
+            raise ValueError(f"cem_params.n_level_hierarchy = {levels} but the model's tree has {hp.hierarchy_levels} levels")
+    if sampler in _HIERARCHICAL_SAMPLERS:
+        if planner_cls not in (None, "HierarchicalImageCEMPlanner", "HierarchicalCEMPlanner"):
+            raise ValueError(f"policy.cem_planner = {planner_cls} cannot drive the hierarchical sampler {sampler} (cem_planner.py:109-113)")
+        rates = cem.get("sampling_rates_per_layer")
+        if rates is None:
+            raise ValueError("cem_params.sampling_rates_per_layer is needed by the hierarchical sampler")
+        rates = [int(r) for r in rates]
+        if n_iters != len(rates) + 1:                                # cem_planner.py:170-171
+            raise ValueError(f"cem_params.n_iters = {n_iters} but sampling_rates_per_layer = {rates}: "
+                             f"n_iters == len(rates) + 1 = {len(rates) + 1} (cem_planner.py:170-171)")
+        if not learned:
+            raise ValueError(f"cem_params.cost_fcn = {cost}: the hierarchical planner scores subgoals with a learned cost")
+        for k in ("batch_size", "elite_frac", "initial_std", "dense_cost", "final_step_cost_weight"):
+            if k in cem:
+                ignored.append(f"cem_params.{k}:unread")         # the hierarchical sampler draws its own populations (sampler.py:101-103)
+        planner = "hierarchical"
+        planner_args = dict(n_level_hierarchy=int(levels), sampling_rates_per_layer=rates, n_ll_samples=int(cem.get("n_ll_samples", 5)),
+                            action_dim=hp.nz_vae, max_seq_len=hp.max_seq_len, clip_val=clip)
+        sampler_args = {}
+    elif sampler in _FLAT_SAMPLERS:
+        # a hierarchical planner class given a flat sampler runs the flat loop (cem_planner.py:211-214)
+        for k in ("sampling_rates_per_layer", "n_ll_samples"):
+            if k in cem:
+                ignored.append(f"cem_params.{k}:unread")
+        planner = "flat"
+        planner_args = dict(n_iters=int(n_iters), batch_size=int(cem.get("batch_size", 64)), elite_frac=float(cem.get("elite_frac", 0.1)),
+                            max_seq_len=hp.max_seq_len)
+        sampler_args = dict(clip_val=clip, n_steps=hp.max_seq_len, action_dim=hp.nz_vae, initial_std=float(cem.get("initial_std", 3e-1)))
+        if sampler == "SimpleTreeCEMSampler":
+            sampler_args["n_level_hierarchy"] = int(levels)
+    else:
+        raise ValueError(f"cem_params.sampler = {sampler}: no counterpart in planning.py ({_HIERARCHICAL_SAMPLERS + _FLAT_SAMPLERS})")
+    cost_args = {} if learned else dict(dense_cost=bool(cem.get("dense_cost", False)),
+                                        final_step_weight=float(cem.get("final_step_cost_weight", 1.0)))
+
+    # ---- weights (planner_policy.py:48-50; the cost model's own checkpoint: cost_mdl.py:123-136) ----
+    cost_config = dict(cem.get("cost_config") or {})
+    ckpt, epoch = policy.get("checkpt_path"), policy.get("load_epoch")
+    cost_ckpt = cost_config.get("checkpt_path")
+    for k in cost_config:
+        if k not in ("checkpt_path", "load_epoch"):
+            screen_keys("cost_mdl", {k: cost_config[k]}, "cem_params.cost_config")
+    other = bool(cost_ckpt) and bool(ckpt) and os.path.abspath(cost_ckpt) != os.path.abspath(ckpt)
+    weights = dict(path=ckpt, epoch=epoch, file=_resolve_weights(ckpt, epoch), cost_path=cost_ckpt if other else None,
+                   cost_file=_resolve_weights(cost_ckpt, cost_config.get("load_epoch")) if other else None)
+    if not ckpt and cost_ckpt:
+        weights.update(path=cost_ckpt, file=_resolve_weights(cost_ckpt, cost_config.get("load_epoch")))
+    policy_args = dict(replan_interval=int(policy.get("replan_interval", 1)), num_max_replans=int(policy.get("num_max_replans", 10)),
+                       closed_loop_execution=bool(policy.get("closed_loop_execution", False)))
+    return AttrDict(hp=hp, model_kind=kind, planner=planner, planner_args=planner_args, sampler=sampler, sampler_args=sampler_args,
+                    cost=cost, cost_args=cost_args, verbose=bool(cem.get("verbose", False)),
+                    horizon=int(horizon) if horizon is not None else hp.max_seq_len, policy_args=policy_args, weights=weights,
+                    pairs=(config.get("start_index"), config.get("end_index")), ignored=ignored)
+
+
+def build_policy(description, device, weights=None, seed=0, random_weights=False, reference_rng=False, verbose=None):
+    """(model, planner, policy) of a planner_from_control_conf description on `device`: the planning.* objects a user who owns an
+    environment loop drives through `policy.act(t=..., images=..., goal_image=...)`.
+    weights: a checkpoint file instead of the conf's; random_weights: run on the seeded initialisation when no checkpoint resolves
+    (otherwise that raises); seed: of the initialisation, and seed + 1 of the planner's draws; reference_rng: the hierarchical
+    planner replays the reference's np.random sequence; verbose: keep the per-iteration elites (default: the conf's `verbose`)."""
+    from . import planning as P
+    from .checkpoint import load_weights
+    from .model import GCPTreeModel
+    from .params import init_params
+    d = description
+    if d.model_kind != "tree":
+        raise ValueError("policy.model_cls names the flat predictor: the image CEM policy is built for the tree model")
+    hp = d.hp
+    model = GCPTreeModel(hp, params=init_params(hp, seed=seed), device=device)
+    main = weights or d.weights["file"]
+    if main:
+        load_weights(main, model)
+        if d.weights["cost_path"] and not weights:
+            if not d.weights["cost_file"]:
+                raise ValueError(f"no checkpoint of the cost model at cost_config.checkpt_path = {d.weights['cost_path']}")
+            load_weights(d.weights["cost_file"], model, submodule_name="cost_mdl")
+    elif not random_weights:
+        raise ValueError(f"no checkpoint at policy.checkpt_path = {d.weights['path']!r} (load_epoch = {d.weights['epoch'] or 'latest'}): "
+                         "give a weights file, or ask for random weights")
+    model.eval()                                                     # planner_policy.py:51
+    sim = P.GCPImageSimulator(model)
+    cost = P.LearnedCostEstimate(model) if d.cost in _LEARNED_COSTS else getattr(P, d.cost)(d.cost_args["dense_cost"],
+                                                                                             d.cost_args["final_step_weight"])
+    verbose = d.verbose if verbose is None else bool(verbose)
+    if d.planner == "hierarchical":
+        planner = P.HierarchicalCEMPlanner(sim, cost, fast_draws=not reference_rng, seed=seed + 1, verbose=verbose, **d.planner_args)
+    else:
+        a = dict(d.sampler_args)
+        sampler = getattr(P, d.sampler)(a.pop("clip_val"), a.pop("n_steps"), a.pop("action_dim"), a.pop("initial_std"), device=device,
+                                        seed=seed + 1, **a)
+        planner = P.CEMPlanner(sim, cost, sampler, verbose=verbose, **d.planner_args)
+    return model, planner, P.ImageCEMPolicy(model, planner, **d.policy_args)

@@ -388,3 +388,76 @@ def log_outputs(model, panels_fn, outputs, inputs, losses, step, log_images, pha
         else:
             files.append(write_png(os.path.join(model.log_dir, f"{name}_{phase}_{step}.png"), canvas.reshape(-1, *canvas.shape[2:])))
     return files
+
+
+# ---- the planner's verbose pictures (ImageCEMPlanner.log_verbose, cem_planner.py:222-254) ---------------------------------------------
+def _elite_images(model, entry, start_state):
+    """per elite [len, 3, H, W] on the device.  Elites that were scored on latents only are decoded here, all of them in one batch
+    (the decoder takes its skip activations from the start image); the rows that stand for the raw goal image take it."""
+    import torch
+    from .planning import env2planner
+    if entry.elite_images is not None:
+        return [torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=model.device, dtype=torch.float32)
+                for x in entry.elite_images]
+    lat = entry.elite_latents
+    lens = [int(x.shape[0]) for x in lat]
+    I0 = env2planner(np.asarray(start_state)).to(model.device)[:1]
+    img = model.decoder.decode_seq({"I_0": I0}, torch.cat(lat)[None]).images[0]
+    out = list(torch.split(img, lens))
+    goal = env2planner(entry.goal_state).to(model.device)[0]
+    for x, rows in zip(out, entry.goal_rows or [[]] * len(out)):
+        for k in rows:
+            x[k] = goal
+    return out
+
+
+def planner_pictures(model, logs, start_state, horizon, renderer=None):
+    """The pictures of ONE planner call's verbose log (planner.verbose_logs[r]): [{name: uint8 canvas}] per iteration, names `overview`
+    (always), `goal`, and with a TrajectoryRenderer and 2-D elite states `inferStateTraj` (first elite) / `inferStateTrajDist`.
+    Composed on the device -- one gcpx_panel_compose per overview, one gcpx_topdown_trajectories per trajectory picture -- and each
+    copied to the host once.  `sources` of every entry: the host copies the numpy mirrors take (visualization.plan_overview_numpy,
+    render_trajectory_dist_numpy)."""
+    import torch
+    res_all = []
+    stream = torch.cuda.current_stream(model.device).cuda_stream
+    cache = model.__dict__.setdefault("_image_log_panels", {})
+    for entry in logs:
+        elites = _elite_images(model, entry, start_state)
+        E, res = len(elites), int(elites[0].shape[-1])
+        padded = torch.ones((E, horizon) + tuple(elites[0].shape[1:]), dtype=torch.float32, device=model.device)
+        for e, x in enumerate(elites):
+            padded[e, :min(x.shape[0], horizon)] = x[:horizon]
+        key = ("plan_overview", res, horizon, E)
+        dp = cache.get(key)
+        if dp is None:
+            dp = cache[key] = DevicePanel(V.plan_overview(res, horizon, E), model.device)
+        pics = {"overview": dp.compose(model.lib, dict(elites=padded), stream).cpu().numpy()[0].copy()}
+        sources = {"elites": [x.cpu().numpy() for x in elites]}
+        g = np.asarray(entry.goal_state)
+        g = g[0] if g.ndim == 4 else g
+        pics["goal"] = g if g.dtype == np.uint8 else V.to_uint8(g.astype(np.float32) / (np.float32(255) if g.max() > 1.0 else np.float32(1)))
+        st = entry.elite_states
+        if renderer is not None and st is not None and len(st) and int(st[0].shape[-1]) == 2:
+            st = [torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=model.device, dtype=torch.float32)
+                  for x in st if len(x)][:V.TRAJ_MAX_LAYERS]
+            if st:
+                P = max(int(x.shape[0]) for x in st)
+                pad = torch.zeros((len(st), P, 2), dtype=torch.float32, device=model.device)
+                for e, x in enumerate(st):
+                    pad[e, :x.shape[0]] = x
+                ln = torch.tensor([int(x.shape[0]) for x in st], dtype=torch.int64, device=model.device)
+                layers = [dict(states=pad[e:e + 1], length=ln[e:e + 1], color=V.RED) for e in range(len(st))]
+                pics["inferStateTraj"] = renderer.render(model.lib, layers[:1], 1, stream, key="plan_single").cpu().numpy()[0].copy()
+                pics["inferStateTrajDist"] = renderer.render(model.lib, layers, 1, stream, key="plan_dist").cpu().numpy()[0].copy()
+                sources["states"] = [x.cpu().numpy() for x in st]
+        res_all.append(dict(pictures=pics, sources=sources))
+    return res_all
+
+
+def write_planner_pictures(out_dir, pair, replan, pictures):
+    """`plan_{pair}_r{replan}_iter{i}_{name}.png` for what planner_pictures returned; the files written"""
+    files = []
+    for i, p in enumerate(pictures):
+        for name, canvas in p["pictures"].items():
+            files.append(write_png(os.path.join(out_dir, f"plan_{pair}_r{replan}_iter{i}_{name}.png"), canvas))
+    return files

@@ -411,11 +411,34 @@ def select_elites(scores, n_elite):
     return torch.argsort(scores, stable=True)[:n_elite]
 
 
+def elite_log_entry(goal_state, scores, images=None, latents=None, goal_rows=None, states=None):
+    """One iteration of a verbose planner log (cem_planner.py:72-78: elite_rollouts, elite_scores, goal_state, elite_states).
+    images: per elite [len, 3, H, W] in [-1, 1] (device tensors or numpy), or None when the elites were scored on latents only; then
+    latents: per elite [len, nz_enc] on the device, what the decoder turns into those images, and goal_rows: per elite the rows that
+    stand for the raw goal image (a hierarchical plan ends in it).  states: per trajectory [len, state_dim], or None."""
+    return Outputs(elite_images=images, elite_latents=latents, goal_rows=goal_rows, elite_states=states, goal_state=np.asarray(goal_state),
+                   elite_scores=scores)
+
+
+def final_log_entry(final, goal_state, scores, n_latent):
+    """the last entry of a call's log (cem_planner.py:81-88): the final rollout, its image part split off the appended latent"""
+    imgs = []
+    for p in final.predictions:
+        p = np.asarray(p)
+        if p.ndim == 2:                                             # flat image (++ latent) rows (cem_simulator.py:54-59)
+            p = p[:, :p.shape[1] - n_latent]
+            side = int(round(np.sqrt(p.shape[1] / 3)))
+            p = p.reshape(p.shape[0], 3, side, side)
+        imgs.append(p)
+    st = final.get("states")
+    return elite_log_entry(goal_state, scores, images=imgs, states=None if st is None else [np.asarray(x) for x in st])
+
+
 class CEMPlanner:
     """Flat CEM over tree latents with device-resident rollouts and sharded candidates (cem_planner.py:55-135)."""
 
     def __init__(self, simulator, cost, sampler, n_iters=3, batch_size=512, elite_frac=0.1, max_seq_len=80,
-                 goal_in_cost=True, decode_candidates=False):
+                 goal_in_cost=True, decode_candidates=False, verbose=False):
         # decode_candidates: also decode the images of every candidate while scoring (what the reference's simulator does,
         # cem_simulator.py:29-59).  The learned cost reads latents only, so by default the images are decoded once, for the
         # plan that is returned; scores, elites and the returned plan are the same either way.
@@ -424,6 +447,9 @@ class CEMPlanner:
         self.n_iters, self.batch_size, self.elite_frac, self.max_seq_len = n_iters, batch_size, elite_frac, max_seq_len
         self.goal_in_cost = goal_in_cost
         self.logs = []
+        # verbose (cem_params.verbose, cem_planner.py:72-88): every call appends to `verbose_logs` one list holding, per iteration, the
+        # elites' rollouts and states, and last the final rollout (`elite_log_entry`).  Off: nothing is kept, copied or launched for it
+        self.verbose, self.verbose_logs, self._last_eval = bool(verbose), [], None
 
     def _shard(self, n):
         world = D.dist.get_world_size() if D.dist.is_initialized() else 1
@@ -466,9 +492,11 @@ class CEMPlanner:
         world = D.dist.get_world_size() if D.dist.is_initialized() else 1
         if world == 1:
             samples = self._sampler.sample(n)
-            scores, _ = self._evaluate_local(state, goal_state, samples, 0, n)
+            scores, r = self._evaluate_local(state, goal_state, samples, 0, n)
             idx = select_elites(scores, n_elite)
             best = samples[idx]
+            if self.verbose:
+                self._last_eval = (r, idx)
         else:
             assert self._sampler.n_shards() == world, "one shard of the population per rank"
             lo, per = self._shard(n)
@@ -495,9 +523,22 @@ class CEMPlanner:
         n_elite = max(int(self.batch_size * self.elite_frac), 1)
         best_samples = best_scores = None
         self.logs = []
+        if self.verbose:
+            assert not D.dist.is_initialized() or D.dist.get_world_size() == 1, "verbose planner logs: one process (the elites' rollouts " \
+                                                                                   "live on the rank that drew them)"
+            vlog = []
         for _ in range(self.n_iters):
             best_samples, best_scores, scores = self.iterate(state, goal_state)
             self.logs.append(Outputs(elite_scores=best_scores.clone(), mean_score=scores.mean()))
+            if self.verbose:
+                r, idx = self._last_eval
+                lens = r.lengths[idx].tolist()
+                vlog.append(elite_log_entry(
+                    goal_state, best_scores,
+                    images=None if r.images is None else [r.images[i, :l].clone() for i, l in zip(idx.tolist(), lens)],
+                    latents=[r.latents[i, :l].clone() for i, l in zip(idx.tolist(), lens)],
+                    states=None if r.states is None else [r.states[i, :l].clone() for i, l in zip(idx.tolist(), lens)]))
+                self._last_eval = None
         # final rollout of the best candidate (cem_planner.py:81-96); every rank computes it (tiny batch)
         kw = {}
         if getattr(self._sim, "pred_length", False) and hasattr(self._sampler, "sample_uniform"):
@@ -505,6 +546,9 @@ class CEMPlanner:
         final = self._sim.rollout(state, goal_state, best_samples[:1].cpu().numpy(), self.max_seq_len, **kw)
         actions = final.actions[0] if final.actions is not None else None
         states = final.get("states")
+        if self.verbose:
+            vlog.append(final_log_entry(final, goal_state, best_scores, final.latents[0].shape[-1] if self._sim._append_latent else 0))
+            self.verbose_logs.append(vlog)
         return Outputs(predictions=final.predictions[0], actions=actions, latents=final.latents[0], cost=float(best_scores[0]),
                        states=states[0] if states is not None else None)
 
@@ -566,7 +610,7 @@ class HierarchicalCEMPlanner:
     replicas; the flat `CEMPlanner` is the sharded one."""
 
     def __init__(self, simulator, cost, n_level_hierarchy, sampling_rates_per_layer, n_ll_samples=5, action_dim=256,
-                 max_seq_len=80, clip_val=float("inf"), device_resident=True, fast_draws=False, seed=0):
+                 max_seq_len=80, clip_val=float("inf"), device_resident=True, fast_draws=False, seed=0, verbose=False):
         # device_resident: the rollouts of every iteration stay on the device — subgoal pair costs, segment costs and the
         # selections are computed there and only the final plan crosses to the host.  False = the reference's data flow (every
         # rollout, image ++ latent, to numpy: cem_simulator.py:68-70), kept as the checker: both give the same search.
@@ -581,6 +625,7 @@ class HierarchicalCEMPlanner:
                                                         device_resident=self.device_resident,
                                                         rng=self._make_rng(fast_draws, seed))
         self.logs = []
+        self.verbose, self.verbose_logs = bool(verbose), []         # as CEMPlanner's
 
     def _make_rng(self, fast_draws, seed):
         """fast_draws: False -> None (the reference's np.random stream); True -> a seeded generator — on the model's device when the
@@ -605,6 +650,7 @@ class HierarchicalCEMPlanner:
         self.logs = []
         goal = np.asarray(goal_state)
         best_samples = best_scores = None
+        vlog = []
         for it in range(self.n_iters):
             samples = self._sampler.sample()
             if self.device_resident:
@@ -619,11 +665,31 @@ class HierarchicalCEMPlanner:
             if self._sampler._rng is None or it == self.n_iters - 1:
                 best_samples = self._sampler.sample()
             self.logs.append(Outputs(elite_rollouts=best_rollouts, elite_scores=best_scores))
+            if self.verbose:
+                vlog.append(self._verbose_entry(r if self.device_resident else rollouts, best_rollouts, best_scores, goal))
         final = self._sim.rollout(state, goal, best_samples, self.max_seq_len)
         actions = final.actions[0] if final.actions is not None else None
         states = final.get("states")
+        if self.verbose:
+            vlog.append(final_log_entry(final, goal, best_scores, final.latents[0].shape[-1] if self._sim._append_latent else 0))
+            self.verbose_logs.append(vlog)
         return Outputs(predictions=final.predictions[0], actions=actions, latents=final.latents[0],
                        cost=float(np.asarray(best_scores[0]).reshape(-1)[0]), states=states[0] if states is not None else None)
+
+    def _verbose_entry(self, r, best_rollouts, best_scores, goal):
+        """cem_planner.py:215-218 as logged at :72-78: the elite rollout is the one optimised plan, the elite states are the states of
+        ALL rollouts of the iteration.  Device-resident: the plan is (row, frame) references into the scoring rollout, which decoded
+        nothing: its latents are gathered (the forward's buffers are reused by the next rollout), (-1, -1) marks the raw goal image."""
+        if self.device_resident:
+            plan = best_rollouts[0]
+            rows = torch.tensor([[max(i, 0), max(t, 0)] for i, t in plan], device=r.latents.device)
+            lat = r.latents[rows[:, 0], rows[:, 1]]
+            lens = r.lengths.tolist()
+            st = None if r.states is None else [r.states[i, :l].clone() for i, l in enumerate(lens)]
+            return elite_log_entry(goal, best_scores, latents=[lat], goal_rows=[[k for k, (i, _) in enumerate(plan) if i < 0]], states=st)
+        st = r.get("states")
+        return elite_log_entry(goal, best_scores, images=[np.asarray(b) for b in best_rollouts],
+                               states=None if st is None else [np.asarray(x) for x in st])
 
     @property
     def fully_optimized(self):

@@ -178,6 +178,8 @@ class ModelTrainer:
             if k.startswith("defaulted:"):
                 print(f"[train] {k[10:]} is not in the configuration file (the reference reads it from the dataset spec): "
                       f"using {getattr(self.hp, k[10:])}", flush=True)
+            else:           # inert for what is computed (conf_loader.KEY_TABLE); a key that would change it has raised in the loader
+                print(f"[train] configuration key not used: {k}", flush=True)
         hp = self.hp
         self.exp_path = args.path or os.path.join("experiments", name)
         self.rank, self.local_rank, self.world = D.init_from_env()

@@ -296,3 +296,48 @@ def render_trajectories_numpy(assets, layers):
             if ok[m - 1]:
                 _paint_stamp(out[i], assets["goal_stamp"], assets["goal_color"], *pix[m - 1])
     return out
+
+
+# ---- the planner's verbose pictures (cem_planner.py:222-254) ---------------------------------------------------------------------------
+TRAJ_MAX_LAYERS = 64          # GCPX_TRAJ_MAX_LAYERS: the trajectories one call of gcpx_topdown_trajectories draws onto a canvas
+
+
+def plan_overview(res, horizon, n_elites):
+    """ImageCEMPlanner.log_verbose's `plan_r{r}_iter{i}_overview` (cem_planner.py:228-242): the elites stacked top to bottom, each a
+    row of `horizon` frames, values clip((x + 1) / 2, 0, 1).  Source: elites [n_elites, horizon, 3, res, res], every plan padded to
+    `horizon` frames with ones (which the rescale leaves white) -- `pad_elites_numpy`."""
+    p = Panel("plan_overview", 1, n_elites * res, horizon * res, 1.0)
+    p.add(**_frames("elites", res, horizon, nb=n_elites, nf=horizon, r_b=res, c_f=res, flags=RESCALE))
+    return p
+
+
+def pad_elites_numpy(elites, horizon):
+    """list of [len_e, 3, res, res] -> f32 [E, horizon, 3, res, res]: ones behind a shorter plan (cem_planner.py:232-233); a plan longer
+    than `horizon` (a hierarchical plan of max_seq_len frames with the goal image appended) shows its first `horizon` frames, where
+    the reference's reshape fails"""
+    first = np.asarray(elites[0])
+    out = np.ones((len(elites), horizon) + first.shape[1:], np.float32)
+    for e, x in enumerate(elites):
+        x = np.asarray(x, np.float32)[:horizon]
+        out[e, :x.shape[0]] = x
+    return out
+
+
+def plan_overview_numpy(elites, horizon):
+    """uint8 [E * res, horizon * res, 3]: the numpy mirror of the overview canvas"""
+    padded = pad_elites_numpy(elites, horizon)
+    panel = plan_overview(padded.shape[-1], horizon, padded.shape[0])
+    return to_uint8(compose(panel, dict(elites=padded)))[0]
+
+
+def trajectory_dist_layers(trajectories, color=RED):
+    """log_multiple_topdown_trajs (logger.py:262-269) as layers of ONE canvas: every trajectory [len, >= 2] drawn in turn, its lines
+    then its two stamps, onto what the previous one left -- which is the paint order of gcpx_topdown_trajectories' layers.  The first
+    TRAJ_MAX_LAYERS trajectories are drawn."""
+    return [dict(states=np.asarray(t, np.float32)[None, :, :2], length=np.array([len(t)]), color=color)
+            for t in trajectories[:TRAJ_MAX_LAYERS] if len(t)]
+
+
+def render_trajectory_dist_numpy(assets, trajectories, color=RED):
+    """uint8 [S, S, 3]: the numpy mirror of `inferStateTrajDist`"""
+    return render_trajectories_numpy(assets, trajectory_dist_layers(trajectories, color))[0]
