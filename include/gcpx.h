@@ -152,7 +152,8 @@ int gcpx_conv4x4s2_image(const float* x, const float* wpk, const float* bias, fl
 
 /* BatchNorm statistics -> (scale, shift):  scale = gamma * rsqrt(var + eps), shift = beta - mean * scale.
    partial: dev [n_partial][2][pitch] (fp32 partial sums written by the conv / gemm epilogues); column n
-   belongs to channel n % C (pitch is a multiple of C); count = elements per channel.  If running_mean/var are non-NULL they are updated with `momentum` (training). */
+   < (pitch / C) * C belongs to channel n % C, the columns behind those whole replicas are padding and are not read (pitch >= C);
+   count = elements per channel.  If running_mean/var are non-NULL they are updated with `momentum` (training). */
 int gcpx_bn_finalize(const float* partial, int32_t n_partial, int32_t pitch, int32_t C, double count,
                      const float* gamma, const float* beta, float eps, float* scale, float* shift,
                      float* running_mean, float* running_var, float momentum, float* mean_out, float* rstd_out,

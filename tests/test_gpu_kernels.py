@@ -183,6 +183,69 @@ def test_gemm_lstm_epilogue(env):
     assert_close(go, _lstm_gates_ref(cell, x, h), atol=1e-5, name="gates_out (exact f32 form)")
 
 
+@pytest.mark.parametrize("form", ["tile", "split", "planes"])
+def test_gemm_lstm_epilogue_with_saturated_gates(env, form):
+    """The LSTM-cell epilogue of the three row-GEMM forms with gates far outside the linear part of their sigmoid / tanh: the exact f32
+    kernel (csrc/gemm_tile.h: __expf sigmoid, tanhf), the split-f16 kernel (csrc/gemm_split.hip: the same) and the two-launch planes form
+    (csrc/gemm_planes.hip: exp2 + rcp hardware forms).  Saturation comes through the BIAS — per-column offsets 0, +-5, +-20, +-50, +-100,
+    a different one for each of the four gates of a unit — so the GEMM part and its 1e-5 bound are those of test_gemm_lstm_epilogue;
+    c_prev takes +-1e-3, +-1, +-30.  The smallest M each form accepts (16; 512 rows for the split and planes forms), H = 64: K = 2 H = 128
+    stays below the 256 from which the dispatcher may hand such a problem to the exact kernel's split-K blocks instead.
+    h, c, h_copy and gates_out against float64: all finite (an overflowing exp must end as 0 or 1, not as a NaN), the gates within
+    1e-5, c and h within 1e-5 + 2 eps |c| (c reaches 30: one rounding each of f x c_prev and of the sum).
+    worst error / tolerance on an MI355X (gates, c, h): tile 0.021, 0.24, 0.023; split 0.033, 0.38, 0.077; planes 0.036, 0.30, 0.077."""
+    rt, pk, lib, dev = env
+    M, H = (16 if form == "tile" else 512), 64
+    torch.manual_seed(23)
+    x, h = torch.randn(M, H), torch.randn(M, H)
+    cvals = torch.tensor([1e-3, -1e-3, 1.0, -1.0, 30.0, -30.0])
+    c = cvals[(torch.arange(M)[:, None] + torch.arange(H)[None]) % 6].contiguous()
+    cell = torch.nn.LSTMCell(H, H)
+    offs = torch.tensor([0.0, 5.0, -5.0, 20.0, -20.0, 50.0, -50.0, 100.0, -100.0])
+    u = torch.arange(H)
+    with torch.no_grad():                                                 # torch's bias is gate-major: [4][H]
+        for g_, mult in enumerate((1, 2, 4, 5)):                          # (multipliers coprime to 9: every gate meets every offset)
+            cell.bias_ih[g_ * H:(g_ + 1) * H] += offs[(mult * u + g_ * (u // 9)) % 9]
+    w, b = pk.lstm_gate_interleave(cell.weight_ih.detach(), cell.weight_hh.detach(), cell.bias_ih.detach(), cell.bias_hh.detach())
+    gates = _lstm_gates_ref(cell, x, h)                                   # [M][H][4] float64
+    assert float((gates[..., [0, 1, 3]] < 1e-6).double().mean()) > 0.2 and float((gates[..., [0, 1, 3]] > 1 - 1e-6).double().mean()) > 0.2
+    assert float((gates[..., 2].abs() > 1 - 1e-6).double().mean()) > 0.4
+    c_ref = gates[..., 1] * c.double() + gates[..., 0] * gates[..., 2]
+    h_ref = gates[..., 3] * torch.tanh(c_ref)
+    wp, bd = pk.pack_gemm(w).to(dev), b.to(dev)
+    xd, hd, cd = x.to(dev), h.to(dev), c.to(dev)
+    ho, co, hc = (torch.full((M, H), float("nan"), device=dev) for _ in range(3))
+    go = torch.full((M, H, 4), float("nan"), device=dev)
+    a = rt.GemmArgs()
+    a.src[0] = _rowsrc(rt, xd, 0, H, H)
+    a.src[1] = _rowsrc(rt, hd, 0, H, H)
+    a.nsrc, a.M, a.N, a.K, a.rpb = 2, M, 4 * H, 2 * H, M
+    a.wpk, a.bias, a.epi = wp.data_ptr(), bd.data_ptr(), rt.EPI_LSTM
+    a.c_prev, a.c_prev_stride, a.h_out, a.c_out, a.hb, a.hrow, a.h_copy = cd.data_ptr(), H, ho.data_ptr(), co.data_ptr(), 0, H, hc.data_ptr()
+    a.gates_out = go.data_ptr()
+    if form != "tile":
+        ws, e = pk.pack_gemm_split(w)
+        ws = ws.to(dev)
+        a.wpk_split, a.w_split_log2 = ws.data_ptr(), e
+    if form == "planes":
+        keep = _planes_workspace(rt, lib, a, dev)
+    rt.check(lib.gcpx_gemm(C.byref(a), _stream()), f"gemm lstm, {form}")
+    torch.cuda.synchronize()
+    if form == "planes":
+        assert not bool((keep[1][:M] == 77).any())                        # the conversion pass ran: this was the two-launch form
+    for name, got in (("h", ho), ("c", co), ("h_copy", hc), ("gates_out", go)):
+        assert bool(torch.isfinite(got).all()), f"{name} ({form}): {int((~torch.isfinite(got)).sum())} elements not finite"
+    ge = (go.double().cpu() - gates).abs()
+    tol = 1e-5 + 2 * 2.0 ** -24 * c_ref.abs()
+    ce, he, hce = (co.double().cpu() - c_ref).abs(), (ho.double().cpu() - h_ref).abs(), (hc.double().cpu() - h_ref).abs()
+    print(f"saturated lstm epilogue, {form}: worst err / tol gates {float(ge.max()) / 1e-5:.3g} c {float((ce / tol).max()):.3g} "
+          f"h {float((he / tol).max()):.3g} h_copy {float((hce / tol).max()):.3g}")
+    assert bool((ge <= 1e-5).all()), f"gates_out ({form}): max err {float(ge.max()):.3e}"
+    assert bool((ce <= tol).all()), f"c ({form}): worst err / tol {float((ce / tol).max()):.3g}"
+    assert bool((he <= tol).all()), f"h ({form}): worst err / tol {float((he / tol).max()):.3g}"
+    assert bool((hce <= tol).all()), f"h_copy ({form}): worst err / tol {float((hce / tol).max()):.3g}"
+
+
 @pytest.mark.parametrize("case", ["unit", "tiny", "row_scales", "k_growth", "outlier", "zero_rows"])
 @pytest.mark.parametrize("M,N,K", [(200, 2048, 1024), (130, 192, 128), (512, 512, 1024), (8200, 1024, 192)])
 def test_gemm_split_error_vs_float64(env, case, M, N, K):

@@ -383,7 +383,9 @@ extern "C" int gcpx_bn_finalize(const float* partial, int32_t n_partial, int32_t
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     GCPX_CHECK_ARG(partial && gamma && beta && scale && shift, "null pointer");
     GCPX_CHECK_ARG((mean_out == nullptr) == (rstd_out == nullptr), "mean_out and rstd_out go together");
-    GCPX_CHECK_ARG(n_partial > 0 && C > 0 && pitch >= C && pitch % C == 0 && count > 0, "bad sizes");
+    // (pitch need not be a multiple of C: a conv epilogue pads its rows to 16 columns, forward_plan.py: cpad; the kernel walks the
+    // pitch / C whole replicas and never reads the columns behind them)
+    GCPX_CHECK_ARG(n_partial > 0 && C > 0 && pitch >= C && count > 0, "bad sizes");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, stream, partial, n_partial, pitch, C, count, gamma,
                        beta, eps, scale, shift, running_mean, running_var, momentum, mean_out, rstd_out);
     GCPX_CHECK_LAUNCH();
