@@ -124,7 +124,8 @@ typedef struct gcpx_conv_args {
        (up = 0, no add) computes in a pass of its own over the same tensors.  NULL: plain data gradient */
     const float* bwd_r;
     const float *bwd_scale, *bwd_shift, *bwd_mean, *bwd_rstd;
-    /* Upsampling blocks with 32 / 64 output channels in split-f16 (conv3x3_up32_split_kernel): a raw NHWC tensor
+    /* Upsampling blocks with 32 / 64 output channels in split-f16 (conv3x3_up32_split_kernel), and with Cout == 16 the 16-channel
+       row-folded block only (GCPX_SPLIT_ROWFOLD16, conv3x3_up16_fold16_kernel: F must be a multiple of addend_frame_div): a raw NHWC tensor
        [F / addend_frame_div][Hout][Wout][out_pitch] added to the conv's result (before the BatchNorm partial sums and the store), frame f
        reading frame f / addend_frame_div.  The decoder concatenates the skip activations of I_0 — the same for the N nodes of a sequence
        — to every node's features (tree_dense_rec.py:42 -> blox ConvDecoder with skips); a conv is linear in its input channels, so the
@@ -136,7 +137,10 @@ typedef struct gcpx_conv_args {
 
 /* GCPX_SPLIT_HEAD32: the 100-channel mixture head's weights in 32x32x16 A-fragment order [9 taps][4 tiles][2 pieces][64][8]
    (packing.pack_head32_split / head32_index) for csrc/conv3x3_head32.hip — modes GCPX_HEAD_DLM_MEAN / _NLL / _NLL_GRAD only */
-typedef enum gcpx_split_layout { GCPX_SPLIT_PLAIN = 0, GCPX_SPLIT_ROWFOLD = 1, GCPX_SPLIT_HEAD32 = 2 } gcpx_split_layout;
+/* GCPX_SPLIT_ROWFOLD16: the row-folded weights of a 16 -> 16 channel upsampling block, two horizontal taps per k-step
+   (packing.pack_conv3x3_fold16 / conv3x3_fold16_index over the [24][16][Cin] scratch of gcpx_fold_upsample_weights): the node half / the
+   skip half of additional_conv_layer once the skip half is hoisted (gcpx_conv_args.addend) */
+typedef enum gcpx_split_layout { GCPX_SPLIT_PLAIN = 0, GCPX_SPLIT_ROWFOLD = 1, GCPX_SPLIT_HEAD32 = 2, GCPX_SPLIT_ROWFOLD16 = 3 } gcpx_split_layout;
 
 /* decoder block: (bilinear x2 upsample +) 3x3 conv, pad 1.  gcpx_conv3x3_grid(a) = number of workgroups that launch
    will use = rows of a->stats_partial (a->stats_partial must already be non-NULL in the query if it will be). */

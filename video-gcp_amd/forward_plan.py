@@ -137,18 +137,26 @@ class ForwardPlanMixin:
             hoist = (skip_idx >= 0 and rpb > 1 and F % rpb == 0 and self.split_f16 and cout in (32, 64) and c_prev % 32 == 0 and
                      c_skip % 32 == 0 and f"dec.{name}" in self.pk_split and "fold" not in self.pk_split[f"dec.{name}"] and
                      os.environ.get("GCPX_NO_SKIP_HOIST") is None)
-            # (the 16 + 16 -> 16 channel block, additional_conv_layer, stays one launch of the 32-channel row-folded kernel: hoisted through
-            # 16-channel row-folded packs it measured 282 against 234 us at c2, profiles/r06_skip_hoist.txt)
+            # ... and the 16 + 16 -> 16 channel block (additional_conv_layer) through the 16-channel row-folded packs (weights._pack_split
+            # builds them when the hoist can be planned): conv3x3_up16_fold16_kernel walks a sequence's nodes back to back at one tile and
+            # keeps bias + addend in registers, so the node launch does 144 instead of 216 MFMAs per item and reads the addend once per
+            # sequence and tile: 241 -> 12 + 156 us at c2, headline -0.05 ms (profiles/skip_hoist16.txt; the first form of that kernel read
+            # the addend in every item's epilogue and lost, 11 + 280 us).  GCPX_NO_SKIP_HOIST=1 turns this one off too
+            hoist16 = (skip_idx >= 0 and rpb > 1 and F % rpb == 0 and self.split_f16 and cout == 16 and c_prev == 16 and c_skip == 16 and
+                       f"dec.{name}.f16a" in self.pk_split and res % 4 == 0 and os.environ.get("GCPX_NO_SKIP_HOIST") is None)
             addend = None
-            if hoist:
+            if hoist or hoist16:
                 addend = self._buf(f"dec.{name}.skip", (F // rpb, 2 * res, 2 * res, cout))
                 t, C_, ssc, ssh, sact = skips[skip_idx]
                 zb = self._buf(f"dec.{name}.zero_bias", (cpad,), zero=True)
                 a_s = self._conv_args([(t.data_ptr(), C_, 1, ssc, ssh, sact)], F // rpb, res, res, 2 * res, 2 * res, cout, cout,
                                       P[f"dec.{name}.w"], zb, addend, upsample=1)
-                self._set_split(a_s, f"dec.{name}")
-                # the skip channels' k-steps follow the previous block's in the pack: [chunk][tap][CT][2][64] x 16 B, 32 channels per chunk
-                a_s.wpk_split = a_s.wpk_split + (c_prev // 32) * 9 * (cpad // 16) * 2048
+                if hoist16:
+                    self._set_split(a_s, f"dec.{name}.f16b")     # the skip channels' own 16-channel pack
+                else:
+                    self._set_split(a_s, f"dec.{name}")
+                    # the skip channels' k-steps follow the previous block's in the pack: [chunk][tap][CT][2][64] x 16 B, 32 channels per chunk
+                    a_s.wpk_split = a_s.wpk_split + (c_prev // 32) * 9 * (cpad // 16) * 2048
                 plan.keep.append(a_s)
                 # (16 frames: a latency-bound 18 us launch, in line.  On lane 1 beside the previous block it measured SLOWER — 2.62-2.66 ms
                 # against 2.60-2.61 in line, three rounds: a fork / join pair in the middle of the decoder chain costs more than it hides)
@@ -158,9 +166,9 @@ class ForwardPlanMixin:
                 srcs_main = srcs
             a = self._conv_args(srcs_main, F, res, res, 2 * res, 2 * res, cout, cout, P[f"dec.{name}.w"], P[f"dec.{name}.b"],
                                 o, upsample=1, stats=(o if self.training else None))     # placeholder pointer for the query
-            if hoist:
+            if hoist or hoist16:
                 a.addend, a.addend_frame_div = addend.data_ptr(), rpb
-            self._set_split(a, f"dec.{name}")
+            self._set_split(a, f"dec.{name}.f16a" if hoist16 else f"dec.{name}")
             Gl = lib.gcpx_conv3x3_grid(C.byref(a))
             assert Gl > 0, rt.lib().gcpx_last_error()
             st = self._buf(f"dec.st.{name}", (Gl, 2, cpad)) if self.training else None

@@ -83,9 +83,12 @@ class WeightsMixin:
             if self.head32 and hp.n_mixtures == 10 and hp.head_channels == 100:
                 # the same weights in 32x32x16 fragment order for csrc/conv3x3_head32.hip (mean-only and fused-likelihood modes)
                 todo.append(("dec.head32", "decoder.gen_head.conv.weight", ("head32", pk.dlm_channel_perm(hp.n_mixtures))))
+        hoist16 = set()                                      # 16 + 16 -> 16 channel blocks whose skip half forward_plan hoists
         for name, c_prev, c_skip, skip_idx, cout in decoder_layers(hp):
             if cout == 16 and c_prev + c_skip == 32:         # bilinear rows folded into the weights (conv3x3_up16_fold_kernel)
                 todo.append((f"dec.{name}", f"decoder.net.{name}.conv.weight", "rowfold"))
+                if self.split_f16 and skip_idx >= 0 and c_prev == 16 and c_skip == 16 and os.environ.get("GCPX_NO_SKIP_HOIST") is None:
+                    hoist16.add(f"dec.{name}")
             elif cout == 16:                                 # the wave-autonomous 16-channel blocks (conv3x3_up16_split_kernel)
                 todo.append((f"dec.{name}", f"decoder.net.{name}.conv.weight", None))
             elif cout in (32, 64) and (c_prev + c_skip) % 32 == 0:     # the workgroup-tiled blocks (conv3x3_up32_split_kernel)
@@ -111,6 +114,16 @@ class WeightsMixin:
             d.update(idx=idx, out=torch.zeros(2 * idx.numel(), dtype=torch.int16, device=self.device),
                      log2=torch.zeros(1, dtype=torch.int32, device=self.device))
             self.pk_split[name] = d
+            if perm == "rowfold" and name in hoist16:
+                # the same folded weights as two 16-channel packs (two horizontal taps per k-step, GCPX_SPLIT_ROWFOLD16): the node half
+                # and the skip half of a block whose skip channels are convolved once per sequence (forward_plan: gcpx_conv_args.addend).
+                # They gather from the block's fold scratch (folded once, above) and ride in the same grouped split launch; only the
+                # blocks whose hoist can be planned have them
+                for tag, cbase in (("f16a", 0), ("f16b", 16)):
+                    i16 = pk.conv3x3_fold16_index(shp[1], cbase).to(self.device)
+                    self.pk_split[f"{name}.{tag}"] = dict(fold=d["fold"], fold16=True, idx=i16,
+                                                          out=torch.zeros(2 * i16.numel(), dtype=torch.int16, device=self.device),
+                                                          log2=torch.zeros(1, dtype=torch.int32, device=self.device))
         self.repack_split()
 
     def repack_split(self, stream=None):
@@ -174,7 +187,7 @@ class WeightsMixin:
         if self.split_f16 and d is not None:
             a.wpk_split, a.w_split_log2_dev = d["out"].data_ptr(), d["log2"].data_ptr()
             if layout is None:
-                layout = rt.SPLIT_ROWFOLD if "fold" in d else rt.SPLIT_PLAIN
+                layout = rt.SPLIT_ROWFOLD16 if d.get("fold16") else (rt.SPLIT_ROWFOLD if "fold" in d else rt.SPLIT_PLAIN)
             a.split_layout = layout
 
     def _pack_fused_embed(self):
