@@ -1192,6 +1192,62 @@ int gcpx_grad_health(const float* x, int64_t n, const gcpx_grad_chunk* chunks, i
                      const float* extra, int32_t n_extra, int32_t* partial, int64_t n_partial, int32_t* seg_bad, int32_t* summary,
                      float* gate, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Nav data generator: the PRM expert of the reference's data collection (video-gcp_amd/nav_gen.py; csrc/prm.hip).  One workgroup per
+ * trajectory, a batch of B independent trajectories per call.  All geometry is float64, nothing contracted.  Ragged inputs: the points
+ * of trajectory b are px / py [pt_off[b] .. pt_off[b + 1]) of total_pts, at most max_pts of them; per-trajectory outputs have a fixed
+ * capacity of `cap` nodes, max_pts + 2 <= cap <= GCPX_PRM_MAX_NODES.  start_goal [B][4] = (sx, sy, gx, gy).  Every launch is on
+ * `stream`; nothing is allocated, nothing synchronises.  The numpy restatements nav_gen.sample_points_numpy, prm_numpy and
+ * spline_numpy are the definitions.
+ *
+ * gcpx_prm_sample_points: the sample points of PrmPolicy._sample_points (prm_policy.py:99-124) from RoomSampler2d's boxes
+ *   (sampling_fcns.py:27-45): point p of trajectory b lies in box pt_box[p] of boxes [n_boxes][4] = (centre x, centre y, width x,
+ *   width y):  (u - 0.5) * width + centre, u in [0, 1) = 53 bits of mix64(mix64(mix64(seed) ^ traj_key[b]) ^ c), mix64 the splitmix64
+ *   output function, c = 2 * draw for x and 2 * draw + 1 for y, draw = draw0[b] + (p - pt_off[b]).  A trajectory's points depend on
+ *   (seed, its key, its draws) alone, not on the batch.  The generator is this build's own: np.random is not mirrored.  A box index
+ *   outside [0, n_boxes) gives NaN.
+ *
+ * gcpx_prm_roadmap: sample_points with `sampled_points` given (prm.py:229-257), then generate_roadmap / is_collision (:96-159).
+ *   kept [total_pts]: 1 iff the sample's nearest obstacle point is at distance >= rr.  Nodes of b: its kept samples in order, then
+ *   start, then goal; n_nodes[b] = their number n; node_xy [B][2][cap] (x row, y row; 0 past n).  adj [B][cap][n_knn]: row i = the
+ *   first n_knn nodes j != i in ascending d = sqrt(dx^2 + dy^2) (ties: lower j) whose edge does not collide, -1 past the list and in
+ *   rows >= n.  An edge collides if d >= max_edge_len, or if one of the rint(d / rr) points starting at node i and advanced by repeated
+ *   addition of (rr cos yaw, rr sin yaw), yaw = atan2(dy, dx), or the point j itself, has an obstacle point at distance <= rr.
+ *   The cloud enters as a uniform grid built once per layout (nav_gen.obstacle_grid): obs_x / obs_y [n_obs] sorted by cell
+ *   (cell = cy * grid_x + cx, c. = floor((. - grid_.0) / cell)), cell_start [grid_x * grid_y + 1]; cell > rr, so the 3 x 3 cells around
+ *   a query hold every point within rr and the decisions equal a brute-force scan's.
+ *
+ * gcpx_prm_shortest_path: dijkstra_planning (prm.py:162-226): the shortest directed path from node n - 2 to node n - 1 over adj under
+ *   cost d ** cost_power, costs summed from the start.  Bounded Bellman-Ford sweeps (at most n, early exit when nothing changed); the
+ *   predecessor of j is the lowest i with cost[i] + w(i, j) == cost[j].  success[b] = 1, n_vert[b], path [B][cap] (vertex indices
+ *   start .. goal) and cost[b]; when the goal is unreachable (or n < 2) success[b] = 0 and the other outputs are NOT written.
+ *
+ * gcpx_prm_resample: PrmPolicy._plan's resampling (prm_policy.py:173-185) and the recorded episode.  plan [B][T][2] (float64, the
+ *   planner's units): the cubic spline that interpolates the n_vert[b] path vertices over the normalised cumulative chord length with
+ *   not-a-knot ends -- splprep(s=0) -- evaluated at linspace(0, 1, ns), ns = clamp(n_steps[b], 0, T); rows >= ns are 0.  ok[b] = 0
+ *   (and a zero plan) when n_vert[b] is outside [4, GCPX_PRM_MAX_PATH], a vertex repeats (splprep raises), an index is out of range
+ *   or ns < 2.  states / actions / pad_mask (all three or none; float32): states [B][T + 1][5] = (x, y, heading, goal x, goal y) in
+ *   the environment's units 27 * (x, -y) (the inverse of multiroom3d_env.py:196-199) for the ns plan states and the state after the
+ *   `done` step's zero action (prm_policy.py:82-90), heading = atan2 of the step taken from the state; actions [B][T][2] = the ns - 1
+ *   state differences (transform_plan, multiroom3d_env.py:141-144), then zeros; pad_mask [B][T + 1] = get_pad_mask(ns, T)
+ *   (hdf5_saver.py:39-53).  Rows past the episode, and everything of a trajectory with ok = 0, are 0. */
+#define GCPX_PRM_MAX_NODES 2048
+#define GCPX_PRM_MAX_KNN 32
+#define GCPX_PRM_MAX_PATH 1024
+#define GCPX_PRM_MAX_EDGE_STEPS 4096
+int gcpx_prm_sample_points(const double* boxes, int32_t n_boxes, const int32_t* pt_box, const int32_t* pt_off, const int64_t* traj_key,
+                           const int32_t* draw0, int32_t B, int32_t total_pts, int32_t max_pts, int64_t seed, double* px, double* py,
+                           void* stream);
+int gcpx_prm_roadmap(const double* obs_x, const double* obs_y, const int32_t* cell_start, int32_t n_obs, int32_t grid_x, int32_t grid_y,
+                     double grid_x0, double grid_y0, double cell, const double* px, const double* py, const int32_t* pt_off,
+                     const double* start_goal, int32_t B, int32_t total_pts, int32_t max_pts, int32_t cap, int32_t n_knn, double rr,
+                     double max_edge_len, uint8_t* kept, int32_t* n_nodes, double* node_xy, int32_t* adj, void* stream);
+int gcpx_prm_shortest_path(const double* node_xy, const int32_t* n_nodes, const int32_t* adj, int32_t B, int32_t cap, int32_t n_knn,
+                           double cost_power, int32_t* success, int32_t* n_vert, int32_t* path, double* cost, void* stream);
+int gcpx_prm_resample(const double* node_xy, const int32_t* n_nodes, const int32_t* path, const int32_t* n_vert, const int32_t* n_steps,
+                      const double* start_goal, int32_t B, int32_t cap, int32_t T, double* plan, int32_t* ok, float* states,
+                      float* actions, float* pad_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,8 @@ the crop and the two dots.  Recorded images are neither read nor uploaded: an it
 goal's pixel, and gcpx_topdown_assemble_batch (csrc/topdown_assemble.hip) renders, resizes and converts in the launch that writes the
 model's inputs.  The model gets states[..., :2] (MazeGlobalSplit..., data_loader.py:292-296).
 
-Not here: reading `.h5` (h5py), building the top-down picture from textures, filters other than bilinear.
+Not here: reading `.h5` (h5py), building the top-down picture from textures (nav_gen.py writes an untextured one with a whole nav
+dataset: `python -m video_gcp_amd.gen_nav`), filters other than bilinear.
 """
 import glob
 import math

@@ -274,6 +274,11 @@ SYMBOLS = [
     ("gcpx_grad_segment_norms", C.c_int, [vp, i64, vp, i32, vp, i32, C.c_float, vp, vp, i64, vp, vp, vp]),
     ("gcpx_kl_layerwise", C.c_int, [vp, vp, i32, i32, i32, i64, i64, C.c_float, vp, vp, vp]),
     ("gcpx_grad_health", C.c_int, [vp, i64, vp, i32, vp, i32, vp, i32, vp, i64, vp, vp, vp, vp]),
+    ("gcpx_prm_sample_points", C.c_int, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i64, vp, vp, vp]),
+    ("gcpx_prm_roadmap", C.c_int, [vp, vp, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, i32, i32, i32, i32, i32,
+                                   C.c_double, C.c_double, vp, vp, vp, vp, vp]),
+    ("gcpx_prm_shortest_path", C.c_int, [vp, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]),
+    ("gcpx_prm_resample", C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
 ]
 
 _lib = None
