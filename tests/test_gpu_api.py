@@ -195,3 +195,68 @@ def test_decoder_nll_and_binding_handles(setup):
     assert torch.equal(lo.cpu(), torch.full((hp.batch_size, 1), -1)) and torch.equal(hi.cpu(), inputs["end_ind"][:, None] + 1)
     t = model.tree_module.binding.comp_timestep(torch.tensor([-1, -1, 3]), torch.tensor([0, 4, 8]))
     assert t.tolist() == [0, 1, 5]                                  # (-1 + 0) / 2 truncates to 0 under torch 1.3, not to -1
+
+
+def _forward_tensors(model, dev_in, noise):
+    """one phase-'train' forward with fed noise: private copies of every tensor of out.raw and of the loss vector"""
+    out = model(dev_in, "train", noise=noise)
+    torch.cuda.synchronize()
+    res = {k: v.clone() for k, v in out.raw.items() if torch.is_tensor(v)}
+    res["loss vector"] = out.raw["losses"].clone()
+    return res
+
+
+def _assert_same_tensors(got, want, what):
+    assert got.keys() == want.keys(), what
+    for k in want:
+        assert torch.equal(got[k], want[k]), (what, k)
+
+
+def test_dropped_plans_are_closed_and_the_rebuilt_forward_is_bit_identical(setup):
+    """model._clear_plans() releases the events and graphs of every plan (a closed plan runs no more) and forgets them; the plan built
+    by the next forward computes the same bits into the same persistent buffers.  Three drops in a row."""
+    hp, sd, model = setup
+    model.train(True)
+    try:
+        inputs, noise, _ = make_inputs(hp, seed=13, variant="B")
+        dev_in, nz = {k: v.cuda() for k, v in inputs.items()}, noise.cuda()
+        model._clear_plans()
+        first = _forward_tensors(model, dev_in, nz)
+        assert len(model._plans) == 1
+        for drop in range(3):
+            old = model._last_plan
+            assert not old.closed and model._plans[old.key] is old and model._plan_of(old.outs) is old
+            model._clear_plans()
+            assert old.closed and old.graph is None and model._plans == {} and model._last_plan is None
+            with pytest.raises(RuntimeError):
+                old.run(model._streams)
+            _assert_same_tensors(_forward_tensors(model, dev_in, nz), first, drop)
+            assert len(model._plans) == 1 and model._last_plan is not old
+    finally:
+        model.eval()
+        model._clear_plans()
+
+
+def test_force_replay_cycle_gives_the_same_bits(setup):
+    """force_replay "graph" -> "eager" -> "auto" with a forward after each: the same launches however they are replayed ("auto" destroys
+    the forced graph and captures and times the plan anew), and replay_info() names the forced mode."""
+    hp, sd, model = setup
+    was = model.use_graph
+    model.train(True)
+    try:
+        inputs, noise, _ = make_inputs(hp, seed=14, variant="B")
+        dev_in, nz = {k: v.cuda() for k, v in inputs.items()}, noise.cuda()
+        model._clear_plans()
+        first = _forward_tensors(model, dev_in, nz)
+        for mode in ("graph", "eager", "auto"):
+            model.force_replay(mode)
+            _assert_same_tensors(_forward_tensors(model, dev_in, nz), first, mode)
+            info = model.replay_info()
+            assert info["policy"] == mode
+            if mode != "auto":
+                assert info["mode"] == mode
+        assert len(model._plans) == 1 and model._last_plan.graph is not None
+    finally:
+        model.use_graph = was
+        model.eval()
+        model._clear_plans()

@@ -150,7 +150,7 @@ def test_sequential_backward_schedules_agree(env, monkeypatch):
         tr2.backward(dev_in, noise.cuda())
     torch.cuda.synchronize()
     if "GCPX_BWD_SEGMENTS" in env:
-        assert any(op[0] == "@graph" for op in (tr2.last_bplan.rec.get("_segments") or [])) == (env["GCPX_BWD_SEGMENTS"] != "-1")
+        assert any(op[0] == "@graph" for op in (tr2.last_bplan.segments or [])) == (env["GCPX_BWD_SEGMENTS"] != "-1")
         assert torch.equal(tr.grad, tr2.grad)
         return
     g1, g2 = tr.named_grads(), tr2.named_grads()

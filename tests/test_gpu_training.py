@@ -275,7 +275,7 @@ def test_grouped_level_launches_give_the_gradient_of_single_launches():
     # the grouped Predictor launch itself is bit-identical
     tb2 = tb
     tb2.group_mlp_bwd = True
-    tb2._bplans.clear()
+    tb2._drop_bplans()
     tb2.backward(dev_in, noise.cuda())
     torch.cuda.synchronize()
     gc = tb2.named_grads()
@@ -530,3 +530,51 @@ def test_supervised_decoder_leaves_the_state_regressor_out():
     assert all(float(got[k].abs().max()) == 0.0 for k in got if k.startswith("state_regressor."))
     fwd = model(dev_in, "train", noise=noise.cuda())
     assert "regressed_state" not in fwd
+
+
+def test_a_trainer_whose_plans_are_dropped_keeps_identical_parameters():
+    """Trainer A takes four steps; trainer B two, then model._clear_plans() — which closes B's forward plans and, through the listener,
+    its backward plans: events and graphs destroyed behind a device synchronise — then two more on rebuilt plans.  Same bits in the
+    parameters and both moment vectors."""
+    hp, sd, ma, ta = _setup("c1", "auto", batch_size=3)
+    _, _, mb, tb = _setup("c1", "auto", batch_size=3)
+    for step in range(4):
+        inputs, noise, _ = make_inputs(hp, seed=70 + step, variant="B")
+        dev_in, nz = {k: v.cuda() for k, v in inputs.items()}, noise.cuda()
+        ta.step(dev_in, nz)
+        tb.step(dev_in, nz)
+        if step == 1:
+            old_f, old_b = mb._last_plan, tb.last_bplan
+            assert not old_f.closed and not old_b.closed and tb._bplans[old_f.key] is old_b
+            mb._clear_plans()
+            assert old_f.closed and old_b.closed and mb._plans == {} and tb._bplans == {}
+    torch.cuda.synchronize()
+    assert tb.last_bplan is not old_b and not tb.last_bplan.closed and len(tb._bplans) == 1
+    assert torch.equal(ma.theta, mb.theta) and torch.equal(ta.exp_avg, tb.exp_avg) and torch.equal(ta.exp_avg_sq, tb.exp_avg_sq)
+
+
+def test_a_sequential_trainer_whose_segment_graphs_are_dropped_keeps_identical_gradients():
+    """The flat model's trainer replays runs of its backward plan as small graphs by default (`bplan.segments`, captured in the first
+    backward, replayed from the second).  Three backwards, the plans dropped (the segment graphs destroyed with them), three more — against
+    a twin that never dropped: the same gradient bit for bit."""
+    import video_gcp_amd as V
+    from video_gcp_amd.sequential import GCPSequentialModel
+    from video_gcp_amd.training_sequential import SequentialTrainStep
+    hp = V.config("c1", nz_mid_lstm=128, lstm_init="zero", batch_size=3)
+    sd = V.init_params_sequential(hp, seed=1, randomize_affine=True)
+    m1, m2 = (GCPSequentialModel(hp, params=sd, device="cuda") for _ in range(2))
+    tr1, tr2 = SequentialTrainStep(m1, lr=1e-3), SequentialTrainStep(m2, lr=1e-3)
+    has_graph = lambda bplan: any(op[0] == "@graph" for op in bplan.segments or [])
+    for i in range(6):
+        inputs, noise, _ = make_inputs(hp, seed=80 + i, variant="B")
+        dev_in, nz = {k: v.cuda() for k, v in inputs.items()}, noise[:, :hp.max_seq_len - 1].contiguous().cuda()
+        tr1.backward(dev_in, nz)
+        tr2.backward(dev_in, nz)
+        if i == 2:
+            old = tr2.last_bplan
+            assert has_graph(old) and not old.closed
+            m2._clear_plans()
+            assert old.closed and old.segments is None and tr2._bplans == {}
+    torch.cuda.synchronize()
+    assert tr2.last_bplan is not old and has_graph(tr2.last_bplan) and has_graph(tr1.last_bplan)
+    assert torch.equal(tr1.grad, tr2.grad)

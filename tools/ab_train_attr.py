@@ -29,7 +29,8 @@ for r in range(rounds):
         setattr(obj, attr_, v)
         if on_model:
             tr.m._clear_plans()
-        tr._bplans.clear()
+        torch.cuda.synchronize()
+        tr._drop_bplans()
         for _ in range(2):
             tr.step(dev_in)
         torch.cuda.synchronize()

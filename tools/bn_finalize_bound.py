@@ -16,7 +16,7 @@ d = {k: v.cuda() for k, v in inputs.items()}
 for _ in range(3):
     m(d, "train")
 torch.cuda.synchronize()
-plan = [v[1] for v in m._plans.values()][-1]
+plan = m._last_plan
 full = list(plan.ops)
 nofin = [op for op in full if not op[0].startswith("bn_finalize")]
 print(f"{len(full)} ops, {len(full) - len(nofin)} bn_finalize launches")

@@ -16,7 +16,7 @@ dinp = {k: v.cuda() for k, v in inputs.items() if k in ("traj_seq", "I_0", "I_g"
 for _ in range(3):
     model(dinp, "train", noise=noise.cuda())
 torch.cuda.synchronize()
-plan = [v[1] for v in model._plans.values()][-1]
+plan = model._last_plan
 names = [o[0] for o in plan.ops]
 L = hp.hierarchy_levels
 def lvl_start(l):

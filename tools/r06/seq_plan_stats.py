@@ -16,12 +16,12 @@ for _ in range(3):
 torch.cuda.synchronize()
 bp = tr.last_bplan
 print("segment_graphs", tr.segment_graphs, "ranges", bp.rec.get("segment_ranges"), "caller_lane", bp.rec.get("caller_lane"))
-for label, ops in (("plan", bp.ops), ("replayed", bp.rec.get("_segments") or bp.ops)):
+for label, ops in (("plan", bp.ops), ("replayed", bp.segments or bp.ops)):
     c = collections.Counter((o[0] if o[0].startswith("@") else f"launch lane {o[3]}") for o in ops)
     print(label, len(ops), dict(c))
 import time
 lanes = tr._backward_streams() + [torch.cuda.current_stream().cuda_stream]
-for label, ops in (("plan", bp.ops), ("replayed", bp.rec.get("_segments") or bp.ops)):
+for label, ops in (("plan", bp.ops), ("replayed", bp.segments or bp.ops)):
     torch.cuda.synchronize(); t0 = time.perf_counter(); bp.run(lanes, ops=ops); t1 = time.perf_counter(); torch.cuda.synchronize()
     print(label, "host issue %.2f ms, until done %.2f ms" % ((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3))
 

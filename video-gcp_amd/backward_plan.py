@@ -25,8 +25,7 @@ class BackwardPlanMixin:
     def _build_backward(self, fplan):
         m, hp, lib = self.m, self.m._hp, self.m.lib
         rec, o = fplan.rec, fplan.outs
-        key, tin = rec["key"], rec["tin"]
-        B = key[0]
+        tin, B = rec["tin"], fplan.key.B
         L, T, N = hp.hierarchy_levels, hp.max_seq_len, hp.n_nodes
         nz, nv, H, SD, nl = hp.nz_enc, hp.nz_vae, hp.nz_mid_lstm, hp.lstm_state_dim, hp.n_lstm_layers
         PS = 2 ** L + 1

@@ -188,8 +188,7 @@ class ForwardPlanMixin:
     # ------------------------------------------------------------------------------------------------
     def _build_plan(self, key, tin):
         hp, P, lib = self._hp, self.pk, self.lib
-        B, has_traj, has_z, sample_prior, phase = key[0], key[1], key[2], key[3], key[4]
-        pred_len = key[9]
+        B, has_traj, has_z, sample_prior, phase, pred_len = key.B, key.has_traj, key.has_z, key.sample_prior, key.phase, key.pred_len
         train_aux = has_traj and phase == "train" and not sample_prior    # the posterior path of a training / validation-loss forward
         L, T, N = hp.hierarchy_levels, hp.max_seq_len, hp.n_nodes
         nz, nv, H, SD = hp.nz_enc, hp.nz_vae, hp.nz_mid_lstm, hp.lstm_state_dim
@@ -558,7 +557,7 @@ class ForwardPlanMixin:
             plan.keep.append(la)
             return la, kl_b
 
-        decode, with_loss = key[8], key[7]
+        decode, with_loss = key.decode, key.with_loss
         # Everything of the loss that needs no decoded frame — the KL and the latent-side terms — goes in front of the decoder in one
         # launch (gcpx_loss_pre); behind the head only the reconstruction sum and the total remain (gcpx_loss_final).  (The adaptive
         # model's pruning target comes out of the soft-DTW matching of decoded frames: it keeps the single combine at the end.)
@@ -573,7 +572,6 @@ class ForwardPlanMixin:
             prev = self._plan_decoder_features(plan, self._rowsrc(_addr(E, nz), PS * nz, nz, nz), F, N, skips)
             images = self._buf("images_df", (B, N, hp.input_nc, S, S))
             distr = matched_distr = None
-            with_loss = key[7]
             dlm = hp.decoder_distribution == "discrete_logistic_mixture"
             head_out, row_map = None, None
             fused_nll = None
@@ -730,7 +728,7 @@ class ForwardPlanMixin:
 
         outs.update(E=E, Hid=Hid, Z=Z, PZ=PZ, QZ=QZ, node_t=node_t, leave=leave, frame2node=f2n, seq_len=seq_len,
                     kept_idx=kept_idx, enc_traj_seq=enc_traj, inf_enc_seq=inf_enc, node2row=node2row, etilde_row=etrow)
-        plan.rec.update(head_src=(prev if decode else None), tin=tin, key=key)
+        plan.rec.update(head_src=(prev if decode else None), tin=tin)
         if with_loss:
             plan.rec["loss_args"] = la
         plan.outs = outs

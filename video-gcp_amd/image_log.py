@@ -170,7 +170,7 @@ def tree_panels(model, outputs, inputs, phase):
     traj = _frames_on(model, inputs)
     matching = "match_dist_df" in o
     src = dict(traj_seq=traj, images_df=o["images_df"], node_t=_node_steps(model, outputs, matching), end_ind=outputs.end_ind)
-    gamma = model._plans_rec(o).get("gamma")
+    gamma = model._plan_of(o).rec.get("gamma")
     attentive = gamma is not None
     if attentive:
         src.update({f"gamma{l}": g for l, g in gamma.items()})

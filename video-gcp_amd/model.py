@@ -51,7 +51,8 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         self._use_pred_length = False
         self.materialize_distr = materialize_distr
         self._bufs = {}
-        self._plans = {}
+        self._plans = {}                      # PlanKey -> _Plan
+        self._last_plan = None                # the plan of the latest forward()
         # state other parts of the class create later, declared here (weights.py, replay.py, training.GCPTrainStep)
         self.pk_split = {}                    # split-f16 twins of the conv weights: name -> (pieces, log2 scale)   (weights._pack_split)
         self._split_tab = None                #   ... and the device table their re-split reads
@@ -147,15 +148,14 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         """the output head stores the frames of the balanced tree that belong to a row of the sequence there itself
         (gcpx_conv_args.images_rows): split-f16 mixture head, decoded frames wanted"""
         hp = self._hp
-        return bool(key[8] and not hp.adaptive and self.split_f16 and "dec.head" in self.pk_split and hp.img_sz % 16 == 0 and
+        return bool(key.decode and not hp.adaptive and self.split_f16 and "dec.head" in self.pk_split and hp.img_sz % 16 == 0 and
                     hp.decoder_distribution == "discrete_logistic_mixture" and not self.materialize_distr and
                     os.environ.get("GCPX_HEAD_NO_ROWS") is None and type(self)._build_plan is GCPTreeModel._build_plan)
 
     def _head_grad_fused(self, key):
         """training forward (posterior path with losses, backward to follow) of the balanced model: the head kernel writes the
         likelihood gradient itself"""
-        has_traj, sample_prior, phase, with_loss = key[1], key[3], key[4], key[7]
-        return bool(self.save_for_backward and with_loss and has_traj and not sample_prior and phase == "train" and
+        return bool(self.save_for_backward and key.with_loss and key.has_traj and not key.sample_prior and key.phase == "train" and
                     not self._hp.adaptive and self._head_nll_fusable() and type(self)._build_plan is GCPTreeModel._build_plan)
 
     def _default_params(self, hp, seed):
@@ -215,9 +215,15 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         self._clear_plans()
 
     def _clear_plans(self):
-        self._plans.clear()
+        """Drop every plan and release its events and graphs.  The device synchronise makes that safe (nothing of a plan is still in
+        flight); it runs only here, where plans are dropped, never on the replay path."""
+        torch.cuda.synchronize(self.device)
+        for plan in self._plans.values():
+            plan.close()
         for cb in self._plan_listeners:
             cb()
+        self._plans.clear()
+        self._last_plan = None
 
     def __call__(self, inputs, phase="train", noise=None):
         return self.forward(inputs, phase, noise)
@@ -257,10 +263,12 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         out._lazy = (o, tin)
         return out
 
-    def _plans_rec(self, o):
-        return [v[1].rec for v in self._plans.values() if v[1].outs is o][0]
+    def _plan_of(self, o):
+        """the forward plan whose `outs` is the raw output dict `o` (outputs.raw)"""
+        return [p for p in self._plans.values() if p.outs is o][0]
 
     # ---- eager helpers used by the planner (cost model / inverse model on arbitrary rows) ----
+    # (their throw-away plans need no close(): _mlp, _plan_encoder and _plan_decoder_features never fork, so no event is created)
     def predictor_rows(self, name, *inputs):
         """Run one packed Predictor (self.pk[name]) on dense row tensors [R, C_i] -> [R, out_dim]."""
         W = self.pk[name]
@@ -466,7 +474,7 @@ class TreeView:
         if name == "p_n":
             return o["p_n_df"]
         if name in ("gamma", "e_tilde"):              # attentive posterior (attentive_inference.py:31); stored per level
-            rec = self._m._plans_rec(o)[name]
+            rec = self._m._plan_of(o).rec[name]
             B = o["E"].shape[0]
             bf = torch.cat([rec[l].view(B, 2 ** l, -1) for l in range(self.depth)], 1)
             inv = torch.empty_like(self._bf2df)

@@ -3,14 +3,11 @@ helpers that turn one layer of the model into one C-ABI call of the plan: argume
 gcpx_bn_finalize over the model's buffers (PlanOpsMixin, mixed into model.GCPTreeModel)."""
 import ctypes as C
 import os
-from contextlib import contextmanager
+from typing import NamedTuple
 
 import torch
 
-from . import packing as pk
 from . import runtime as rt
-from .hparams import GCPHParams
-from .params import init_params, encoder_layers, encoder_skip_layers, decoder_layers
 
 
 def _addr(t, off_elems=0):
@@ -20,13 +17,32 @@ def _addr(t, off_elems=0):
 N_LANES = 3
 
 
+class PlanKey(NamedTuple):
+    """Everything that selects a forward plan's buffers and launches (replay.forward): the key of `model._plans`."""
+    B: int
+    has_traj: bool
+    has_z: bool
+    sample_prior: bool
+    phase: str
+    training: bool
+    materialize_distr: bool
+    with_loss: bool
+    decode: bool
+    pred_len: bool
+    shapes: tuple
+
+
 class _Plan:
     """A recorded launch sequence (C entry point + argument struct) over up to N_LANES streams: lane 0 is the
     model's main stream, lanes 1.. are side streams for independent branches.  `fork`/`join` order the lanes with
-    events; under hipGraph capture they become parallel paths of the graph.  Replayed eagerly or as a graph."""
+    events; under hipGraph capture they become parallel paths of the graph.  Replayed eagerly or as a graph.
+    The plan owns the HIP events and graphs made for it and releases them in `close()`, nowhere else."""
+
+    closed = False           # set by close(): run() refuses
 
     def __init__(self, lib):
         self.lib = lib
+        self.key = None      # the PlanKey a forward plan is registered under (replay.forward)
         self.ops = []        # (name, fn, args, lane) | ("@fork"/"@join", None, (lanes, events), 0)
         self.keep = []       # keeps argument structs / tensors alive
         self.graph = None
@@ -37,6 +53,8 @@ class _Plan:
         self.tuned = None    # (graph, eager) seconds per replay measured by the one-time comparison (replay._eager_replays_faster)
         self.timed_ops = None   # (op name, op list with event marks around it): the eager replay with one op timed (replay._run_timed)
         self.split = None    # (graph before, graph behind) the timed op: the graph replay with one op timed
+        self.segments = None   # the op list of `compact`: runs of launches as `@graph` ops (the trainers' backward replay)
+        self._evs = []     # every event of the plan's ops
 
     def add(self, name, fn, *args):
         self.ops.append((name, fn, args, self.lane))
@@ -47,6 +65,7 @@ class _Plan:
             e = C.c_void_p()
             rt.check(self.lib.gcpx_event_create_sync(C.byref(e)), "event_create")
             evs.append(e)
+        self._evs += evs
         return evs
 
     def fork(self, lanes):
@@ -77,7 +96,8 @@ class _Plan:
     def compact(self, streams, min_len=3, ranges=None):
         """The op list with every run of >= min_len consecutive launches on ONE lane replaced by a captured linear graph (`@graph`):
         lane order, events and marks stay what they are — only the host issues one call per run instead of one per launch.
-        ranges: [(first, end)] index ranges of self.ops to look at (None: everywhere)."""
+        ranges: [(first, end)] index ranges of self.ops to look at (None: everywhere).  The list is kept as `self.segments`."""
+        assert self.segments is None, "compacted already: its graphs would be forgotten"
         lib, out, run = self.lib, [], []
         inside = (lambda i: True) if ranges is None else (lambda i: any(a <= i < b for a, b in ranges))
 
@@ -99,9 +119,27 @@ class _Plan:
                 flush()
             (out if ctl else run).append(op)
         flush()
+        self.segments = out
         return out
 
+    def close(self):
+        """Destroy the plan's graphs, then its events, each once; the plan cannot run afterwards.  Nothing of the plan may still be in
+        flight: the caller synchronises the device first (model._clear_plans)."""
+        if self.closed:
+            return
+        graphs = [g for g in (self.graph,) + (self.split or ()) if g is not None]
+        graphs += [op[2][0] for op in self.segments or () if op[0] == "@graph"]
+        events = self._evs
+        self.graph = self.split = self.segments = None
+        self._evs, self.closed = [], True
+        for g in graphs:
+            rt.check(self.lib.gcpx_graph_destroy(g), "graph_destroy")
+        for e in events:
+            rt.check(self.lib.gcpx_event_destroy(e), "event_destroy")
+
     def run(self, streams, ops=None, on_mark=None):
+        if self.closed:
+            raise RuntimeError("this launch plan was closed: its events and graphs are gone")
         lib = self.lib
         for name, fn, args, lane in (self.ops if ops is None else ops):
             if name == "@mark":

@@ -3,15 +3,11 @@ lanes (whichever a one-time comparison per plan finds faster), one op optionally
 (ReplayMixin, mixed into model.GCPTreeModel)."""
 import ctypes as C
 import os
-from contextlib import contextmanager
 
 import torch
 
-from . import packing as pk
 from . import runtime as rt
-from .hparams import GCPHParams
-from .params import init_params, encoder_layers, encoder_skip_layers, decoder_layers
-from .plan_ops import _Plan, _addr, N_LANES
+from .plan_ops import PlanKey
 
 
 # Replay policy "auto".  One process: graph against eager replay timed once per plan (ReplayMixin._eager_replays_faster).  Under a
@@ -176,13 +172,15 @@ class ReplayMixin:
                 self._sync_rng_state()
         # the plan (and its captured graph) bakes in buffer addresses and sizes: everything that selects buffers is part of the key
         shapes = tuple((k, tuple(tin[k].shape)) for k in sorted(tin))
-        key = (B, has_traj, has_z, self._sample_prior, phase, self.training, self.materialize_distr, with_loss, self._decode, pred_len,
-               shapes)             # (a plan that draws its own noise has "rng_all" among its inputs: part of `shapes`)
-        if key not in self._plans:
-            plan = self._build_plan(key, tin)
+        key = PlanKey(B=B, has_traj=has_traj, has_z=has_z, sample_prior=self._sample_prior, phase=phase, training=self.training,
+                      materialize_distr=self.materialize_distr, with_loss=with_loss, decode=self._decode, pred_len=pred_len,
+                      shapes=shapes)             # (a plan that draws its own noise has "rng_all" among its inputs: part of `shapes`)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self._build_plan(key, tin)
+            plan.key = key
             plan.keep.append(tin)
-            self._plans[key] = (None, plan)
-        plan = self._plans[key][1]
+        self._last_plan = plan
         stream = self._stream.cuda_stream
         if self._timed_op is not None:
             self._run_timed(plan, stream)
@@ -242,7 +240,7 @@ class ReplayMixin:
     def replay_info(self):
         """How the plan of the latest forward() is replayed and what the one-time comparison measured (bench.py reports it):
         {"mode": "graph" | "eager", "policy": the GCPX_FORWARD_REPLAY setting, "tuned_ms": {"graph", "eager"} or None}."""
-        plan = [v[1] for v in self._plans.values()][-1]
+        plan = self._last_plan
         tuned = plan.tuned
         return {"mode": "eager" if (plan.eager or not self.use_graph) else "graph",
                 "policy": {True: "graph", False: "eager"}.get(self.use_graph, "auto"),
@@ -250,10 +248,14 @@ class ReplayMixin:
 
     def force_replay(self, mode):
         """Replay every existing plan as a hipGraph ("graph"), by eager launches ("eager") or as the one-time comparison chose ("auto",
-        re-measured on the next call).  Measurement aid (bench.py's also.forward_graph / forward_eager legs)."""
+        re-measured on the next call: the old graphs are destroyed, behind a device synchronise).  Measurement aid (bench.py's
+        also.forward_graph / forward_eager legs)."""
         self.use_graph = {"graph": True, "eager": False, "auto": "auto"}[mode]
-        for _, plan in self._plans.values():
-            if mode == "auto":
+        if mode == "auto":
+            torch.cuda.synchronize(self.device)
+        for plan in self._plans.values():
+            if mode == "auto" and plan.graph is not None:
+                rt.check(self.lib.gcpx_graph_destroy(plan.graph), "graph_destroy")
                 plan.graph = None
             plan.eager = mode == "eager"
 
@@ -270,7 +272,12 @@ class ReplayMixin:
     # ---- one op of the plan bracketed by HIP events on the launch stream (roofline measurement) ----
     def set_timed_op(self, name):
         self._timed_op = name
-        self._timed_events = []
+        self._release_timed_events()             # (pairs nobody read with timed_op_ms)
+
+    def _release_timed_events(self):
+        pairs, self._timed_events = self._timed_events, []
+        for e in (e for pair in pairs for e in pair):
+            rt.check(self.lib.gcpx_event_destroy(e), "event_destroy")
 
     def _run_timed(self, plan, stream):
         names = [op[0] for op in plan.ops]
@@ -309,7 +316,7 @@ class ReplayMixin:
         Tuning aid; not used on the hot path."""
         self.forward(inputs, phase, noise)
         torch.cuda.synchronize()
-        plan = [v[1] for v in self._plans.values()][-1]
+        plan = self._last_plan
         res = []
         with torch.cuda.stream(self._stream):
             for name, fn, args, _ in plan.ops:
@@ -332,7 +339,5 @@ class ReplayMixin:
             ms = C.c_float()
             rt.check(self.lib.gcpx_event_elapsed_ms(e0, e1, C.byref(ms)), "event_elapsed")
             out.append(ms.value)
-            self.lib.gcpx_event_destroy(e0)
-            self.lib.gcpx_event_destroy(e1)
-        self._timed_events = []
+        self._release_timed_events()
         return out

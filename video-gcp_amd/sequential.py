@@ -191,7 +191,7 @@ class GCPSequentialModel(GCPTreeModel):
 
     def _build_plan(self, key, tin):
         hp, P, lib = self._hp, self.pk, self.lib
-        B, has_traj, has_z, sample_prior, phase, with_loss = key[0], key[1], key[2], key[3], key[4], key[7]
+        B, has_traj, has_z, sample_prior, phase, with_loss = key.B, key.has_traj, key.has_z, key.sample_prior, key.phase, key.with_loss
         T, nz, nv, H, nl = hp.max_seq_len, hp.nz_enc, hp.nz_vae, hp.nz_mid_lstm, hp.n_lstm_layers
         S = hp.img_sz
         plan = _Plan(lib)
@@ -566,7 +566,7 @@ class GCPSequentialModel(GCPTreeModel):
             outs["losses"], outs["nll_bt"], outs["kl_b"] = loss_out, nll_bt, kl_b
             plan.rec["loss_args"] = la
         outs["enc_traj_seq"] = enc_traj
-        plan.rec.update(head_src=prev, tin=tin, key=key, seq_row_map=row_map)
+        plan.rec.update(head_src=prev, tin=tin, seq_row_map=row_map)
         plan.outs = outs
         return plan
 

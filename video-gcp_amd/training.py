@@ -93,7 +93,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self._live_gemm_split()
         self._bplans = {}
         # backward plans are built from forward plans: drop them whenever the model drops those (load_state_dict, build_arena)
-        model._plan_listeners = model._plan_listeners + [self._bplans.clear]
+        model._plan_listeners = model._plan_listeners + [self._drop_bplans]
         self.wgroup_min_blocks = int(os.environ.get("GCPX_WGROUP_MIN", "256"))
         self.fused_image_wgrad = os.environ.get("GCPX_IMAGE_WGRAD_UNFUSED") is None
         self.split_wgrad = os.environ.get("GCPX_WGRAD_NOSPLIT") is None     # decoder conv weight gradients on the split-f16 kernel
@@ -155,10 +155,10 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             raise ValueError("the training step needs traj_seq and pad_mask")
         if self.nan_guard:
             self._health_extra = out.raw["losses"]        # the device loss vector: tested beside the gradient (base_gcp.py:302-303)
-        key = [k for k, v in m._plans.items() if v[1].outs is out.raw][0]
-        if key not in self._bplans:
-            self._bplans[key] = self._build_backward(m._plans[key][1])
-        bplan = self._bplans[key]
+        fplan = m._plan_of(out.raw)
+        bplan = self._bplans.get(fplan.key)
+        if bplan is None:
+            bplan = self._bplans[fplan.key] = self._build_backward(fplan)
         caller = torch.cuda.current_stream(m.device)
         self._caller = caller
         self._applied = set()
@@ -172,18 +172,24 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         if (self.segment_graphs > 0 or (seg_ranges and self.segment_graphs == 0)) and not bplan.rec.get("caller_lane"):
             # runs of launches on one lane as small linear graphs (fewer host calls; lanes, events and marks unchanged): everywhere
             # (GCPX_BWD_SEGMENTS=n) or where the plan asks for it (`segment_ranges`: chains with slack, GCPX_BWD_SEGMENTS=-1: nowhere)
-            if bplan.rec.get("_segments") is None:
+            if bplan.segments is None:
                 bplan.run(lanes, on_mark=self._on_mark)
                 torch.cuda.synchronize(m.device)
-                bplan.rec["_segments"] = bplan.compact(self._backward_streams(), max(self.segment_graphs, 3), seg_ranges)
+                bplan.compact(self._backward_streams(), max(self.segment_graphs, 3), seg_ranges)
                 self.last_bplan = bplan
                 caller.wait_stream(m._stream)
                 return out
-            ops = bplan.rec["_segments"]
+            ops = bplan.segments
         bplan.run(lanes, ops=ops, on_mark=self._on_mark)
         caller.wait_stream(m._stream)
         self.last_bplan = bplan
         return out
+
+    def _drop_bplans(self):
+        """the model's plan listener: behind model._clear_plans' device synchronise"""
+        for bplan in self._bplans.values():
+            bplan.close()
+        self._bplans.clear()
 
     def _on_mark(self, tag, payload):
         if tag == "slices":

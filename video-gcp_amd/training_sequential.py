@@ -159,8 +159,7 @@ class SequentialTrainStep(GCPTrainStep):
     def _build_backward(self, fplan):
         m, hp, lib = self.m, self.m._hp, self.m.lib
         rec, o = fplan.rec, fplan.outs
-        key, tin = rec["key"], rec["tin"]
-        B = key[0]
+        tin, B = rec["tin"], fplan.key.B
         T, nz, nv, H, nl = hp.max_seq_len, hp.nz_enc, hp.nz_vae, hp.nz_mid_lstm, hp.n_lstm_layers
         S_ = hp.img_sz
         div = float(T * hp.input_nc * S_ * S_)
