@@ -1248,6 +1248,51 @@ int gcpx_prm_resample(const double* node_xy, const int32_t* n_nodes, const int32
                       const double* start_goal, int32_t B, int32_t cap, int32_t T, double* plan, int32_t* ok, float* states,
                       float* actions, float* pad_mask, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The maze environment of the control experiments (video-gcp_amd/nav_env.py, control.py; csrc/nav_env.hip): E independent episodes
+ * advanced together, one launch per step -- what GeneralAgent.rollout does one episode at a time on the host through
+ * TopdownMultiroom3dEnv.step (gcp/planning/infra/agent/general_agent.py, .../multiroom3d/multiroom3d_env.py) and BaseMiniworldEnv.eval
+ * (base_miniworld_env.py:29-40).  gym-miniworld is absent: the dynamics are this build's own, defined by the numpy
+ * restatements nav_env.step_numpy and nav_env.goal_dist_numpy.  One thread per episode; float64 geometry, nothing contracted; every
+ * launch is on `stream`, nothing is allocated, nothing synchronises.
+ *
+ * Units: state [E][3] = (x, y, heading) float32 in the environment's units, 27 * (x, -y) of the table coordinates the layout uses
+ *   (the inverse of multiroom3d_env.py:196-199); a position in table coordinates is ((double)x / 27, -((double)y / 27)).
+ * walls [n_walls][4] float64 = (x0, y0, x1, y1): nav_layout.wall_segments centred on (0, 0) as Layout centres its cloud.
+ * goal_table [E][rooms_per_side^2][3] float64, built by the host at reset (nav_env.goal_table): row r of episode e serves a position in
+ *   room r (Layout.coords2ridx): (first door centre x, y, length from that door over the remaining door centres of
+ *   plan_room_seq(r, goal room) to the goal); the goal room's row is (goal x, goal y, -1); every row's third entry is NaN when a
+ *   coordinate of the goal lies outside [-0.5, 0.5].
+ *   goal distance of a position p = 10 when a coordinate of p lies outside [-0.5, 0.5] or the row's third entry is NaN; else
+ *   |p - (row x, y)| + max(third entry, 0): PrmPolicy.compute_shortest_path (prm_policy.py:198-216).  The room coordinates
+ *   floor((c + table_size / 2) / (1 / 3)) are clamped to [0, rooms_per_side - 1].
+ * pix [E][2] int32: dataset.topdown_pixels of the position (float32: (x, -y) / 27 + half_table, times render_scale, truncated;
+ *   (v_x + cw, S + cw - v_y)), what gcpx_topdown_assemble_batch takes as the agent's pixel.
+ *
+ * gcpx_nav_env_reset: full_traj [E][T + 1][3] row 0 = state, path_len [E] (float64) = 0, goal_dist [E][T + 1] (float64) entry 0, pix.
+ *
+ * gcpx_nav_env_step: step t of T.  action [E][2] float32.  Proposed position p' = p + a, one float32 add per coordinate.
+ *   a == (0, 0): the move is free, nothing changes.  Otherwise the move is BLOCKED iff p' is not finite or the closed segment [p, p']
+ *   (table coordinates) comes within `radius` of a wall: for some wall NOT (d2 > radius^2), d2 = 0 when the two segments cross properly
+ *   (both orientation tests strictly of opposite sign), else the least of the four squared end-point-to-segment distances.  A blocked
+ *   move is rejected whole: position and heading stay.  A free move: position p', heading (float)atan2(dy, dx) of the step
+ *   (float64 differences of the float32 coordinates, environment units).
+ *   Written: state; full_traj row t + 1; blocked [E][T] entry t (1 / 0); path_len[e] += the Euclidean length of the step taken (0 when
+ *   blocked; environment units); goal_dist entry t + 1 and pix of the new position.
+ *
+ * GCPX_ERR_INVALID_ARG, nothing launched: a null pointer, E or T outside [1, 2^20], t outside [0, T), n_walls outside
+ *   [1, GCPX_NAV_MAX_WALLS], rooms_per_side outside [1, GCPX_NAV_MAX_ROOMS_PER_SIDE], radius negative or not finite, table_size <= 0,
+ *   S outside [1, 16384], cw outside [0, 16384]. */
+#define GCPX_NAV_MAX_WALLS 1024
+#define GCPX_NAV_MAX_ROOMS_PER_SIDE 16
+int gcpx_nav_env_reset(const float* state, const double* goal_table, int32_t rooms_per_side, double table_size, int32_t E, int32_t T,
+                       float half_table, float render_scale, int32_t S, int32_t cw, float* full_traj, double* path_len, double* goal_dist,
+                       int32_t* pix, void* stream);
+int gcpx_nav_env_step(float* state, const float* action, const double* walls, int32_t n_walls, double radius, const double* goal_table,
+                      int32_t rooms_per_side, double table_size, int32_t E, int32_t T, int32_t t, float half_table, float render_scale,
+                      int32_t S, int32_t cw, float* full_traj, double* path_len, double* goal_dist, uint8_t* blocked, int32_t* pix,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,164 @@
+"""Executed steps per second of the closed-loop control experiment at the 9-room and 25-room control shapes, random weights.
+
+  batched   control.ControlRunner over --E tasks at once: nav_env.NavEnvBatch (gcpx_nav_env_step, gcpx_topdown_assemble_batch), plans per
+            episode, the closed-loop encoder one frame per call, the inverse model on all rows;
+  serial    the same tasks (the first --serial of them) one episode at a time, the way the reference's GeneralAgent.rollout runs:
+            planning.ImageCEMPolicy.act on the frames so far, nav_env.step_numpy, dataset.render_topdown_numpy + resize_frames_numpy.
+Both loops make the same plans per episode (at t = 0 and when a plan is used up); the time inside the planner is measured apart, so
+that `steps_per_s` (everything) and `exec_steps_per_s` (planner time taken out) can both be read.  --steps caps agent.T.
+Also measured once: the largest difference between the encoder + inverse model on a frame alone and on the same frame in a batch of 3
+(`row_alone_vs_batch3_max_abs`), the figure behind the runner's one-frame-per-call encoding.
+Prints one JSON line per shape; --out appends them to a file under profiles/.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import textwrap
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# the settings of experiments/control/{9room,25room}/gcp_tree/mod_hyper.py
+CONF = textwrap.dedent('''
+    from blox import AttrDict
+    from gcp.planning.infra.agent.benchmarking_agent import BenchmarkAgent
+    from gcp.planning.infra.envs.miniworld_env.multiroom3d.multiroom3d_env import TopdownMultiroom3dEnv
+    from gcp.planning.planner_policy import ImageCEMPolicy
+    from gcp.planning.cem.sampler import ImageHierarchicalTreeCEMSampler
+    from gcp.planning.cem.cem_planner import HierarchicalImageCEMPlanner
+    from gcp.planning.cem.cost_fcn import ImageLearnedCostEstimate
+    from experiments.prediction.base_configs import gcp_tree as base_conf
+
+    agent = AttrDict(type=BenchmarkAgent, env=(TopdownMultiroom3dEnv, dict(init_pos=None, goal_pos=None, n_rooms={n_rooms},
+                     heading_smoothing=0.1, crop_window=40)), T={T}, image_height=32, image_width=32)
+    h_config = AttrDict(base_conf.model_config)
+    h_config.update(dict(state_dim=2, ngf=16, max_seq_len={seq}, hierarchy_levels={levels}, nz_mid_lstm=512, n_lstm_layers=3, nz_mid=128,
+                         nz_enc=128, nz_vae=256, regress_length=True, attach_state_regressor=True, attach_inv_mdl=True,
+                         inv_mdl_params=AttrDict(n_actions=2, use_convs=False, build_encoder=False),
+                         decoder_distribution='discrete_logistic_mixture'))
+    h_config.pop("add_weighted_pixel_copy")
+    cem_params = AttrDict(prune_final=True, horizon={seq}, action_dim=256, verbose=False, n_iters=3, batch_size=10,
+                          n_level_hierarchy={levels}, sampler=ImageHierarchicalTreeCEMSampler, sampling_rates_per_layer=[10, 10],
+                          cost_fcn=ImageLearnedCostEstimate, cost_config=AttrDict(checkpt_path='none'))
+    policy = AttrDict(type=ImageCEMPolicy, params=h_config, checkpt_path='none', cem_planner=HierarchicalImageCEMPlanner,
+                      cem_params=cem_params, replan_interval=agent.T + 2, closed_loop_execution=True)
+    config = AttrDict(start_index=0, end_index=99, agent=agent, policy=policy)
+''')
+SHAPES = {9: dict(n_rooms=9, T=200, seq=100, levels=7), 25: dict(n_rooms=25, T=400, seq=200, levels=8)}
+
+
+class TimedPlanner:
+    """the planner, with the wall time spent inside it (device work included) and its calls counted"""
+
+    def __init__(self, planner, torch):
+        self.planner, self.torch, self.seconds, self.calls = planner, torch, 0.0, 0
+
+    def __call__(self, state, goal):
+        self.torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = self.planner(state, goal)
+        self.torch.cuda.synchronize()
+        self.seconds += time.perf_counter() - t0
+        self.calls += 1
+        return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--E", type=int, default=100)
+    ap.add_argument("--serial", type=int, default=None, help="episodes of the one-at-a-time loop (default: --E)")
+    ap.add_argument("--steps", type=int, default=None, help="steps per episode (default: the conf's agent.T, 200 / 400)")
+    ap.add_argument("--rooms", type=int, nargs="+", default=[9, 25])
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import video_gcp_amd  # noqa: F401
+    from video_gcp_amd import conf_loader as CL
+    from video_gcp_amd import control as CT
+    from video_gcp_amd import dataset as DS
+    from video_gcp_amd import nav_env as NE
+    from video_gcp_amd import planning as P
+
+    dev = torch.device("cuda", 0)
+    lines = []
+    for n_rooms in a.rooms:
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "mod_hyper.py")
+            with open(path, "w") as f:
+                f.write(CONF.format(**SHAPES[n_rooms]))
+            conf = CL.exec_control_conf(path, {})
+        desc, env_desc = CL.planner_from_control_conf(conf), CL.environment_from_control_conf(conf)
+        model, planner, _ = CL.build_policy(desc, dev, seed=0, random_weights=True, verbose=False)
+        T = min(a.steps or env_desc.T, env_desc.T)
+        tasks = NE.draw_tasks(n_rooms, 0, range(a.E))
+        env = NE.NavEnvBatch(n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev)
+
+        # one frame alone against the same frame in a batch of 3: encoder + inverse model
+        obs = NE.NavEnvBatch(n_rooms, env_desc.crop_window, 1, env_desc.img_sz, dev).reset({k: v[:3] for k, v in tasks.items()})
+        target = torch.randn(3, model._hp.nz_enc, generator=torch.Generator().manual_seed(0)).to(dev)
+        together = model.inv_mdl.run_single(model.encode(obs), target)
+        alone = torch.cat([model.inv_mdl.run_single(model.encode(obs[e:e + 1]), target[e:e + 1]) for e in range(3)])
+        row_diff = float((together - alone).abs().max())
+        enc_diff = float((model.encode(obs) - torch.cat([model.encode(obs[e:e + 1]) for e in range(3)])).abs().max())
+
+        # batched
+        timed = TimedPlanner(planner, torch)
+        runner = CT.ControlRunner(model, timed, env, **desc.policy_args)
+        runner.run({k: v[:2] for k, v in tasks.items()})            # warm-up: plans and buffers of both kinds of call
+        timed.seconds, timed.calls = 0.0, 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = runner.run(tasks)
+        torch.cuda.synchronize()
+        wall_b, plan_b, calls_b = time.perf_counter() - t0, timed.seconds, timed.calls
+
+        # one episode at a time
+        n_serial = min(a.serial or a.E, a.E)
+        walls = NE.wall_table(env.rps)
+        timed = TimedPlanner(planner, torch)
+        goal_pix = DS.topdown_pixels(tasks["goal"], n_rooms, env.scale, env.S, env.cw)
+
+        def frame_of(state, e):
+            pix = DS.topdown_pixels(state[None, :2], n_rooms, env.scale, env.S, env.cw)
+            return DS.resize_frames_numpy(DS.render_topdown_numpy(env.assets, pix, goal_pix[e]), env_desc.img_sz)[0]
+
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        final = []
+        for e in range(n_serial):
+            policy = P.ImageCEMPolicy(model, timed, **desc.policy_args)
+            state = tasks["start"][e].copy()
+            goal_image = frame_of(np.concatenate([tasks["goal"][e], [0.0]]).astype(np.float32), e)[None]
+            frames = [frame_of(state, e)]
+            for t in range(T):
+                act = np.asarray(policy.act(t=t, i_tr=e, images=np.stack(frames), goal_image=goal_image).actions, dtype=np.float32)
+                state = NE.step_numpy(state, act, walls)["state"]
+                frames.append(frame_of(state, e))
+            final.append(state)
+        torch.cuda.synchronize()
+        wall_s, plan_s, calls_s = time.perf_counter() - t0, timed.seconds, timed.calls
+        lines.append({"workload": "control_time", "n_rooms": n_rooms, "E": a.E, "T": T, "max_seq_len": desc.hp.max_seq_len,
+                      "batched_wall_s": round(wall_b, 3), "batched_planner_s": round(plan_b, 3), "batched_plans": calls_b,
+                      "batched_steps_per_s": round(a.E * T / wall_b, 1),
+                      "batched_exec_steps_per_s": round(a.E * T / max(wall_b - plan_b, 1e-9), 1),
+                      "serial_episodes": n_serial, "serial_wall_s": round(wall_s, 3), "serial_planner_s": round(plan_s, 3),
+                      "serial_plans": calls_s, "serial_steps_per_s": round(n_serial * T / wall_s, 1),
+                      "serial_exec_steps_per_s": round(n_serial * T / max(wall_s - plan_s, 1e-9), 1),
+                      "blocked_fraction": round(float(res["blocked"].mean()), 4),
+                      "row_alone_vs_batch3_max_abs": row_diff, "encoder_alone_vs_batch3_max_abs": enc_diff})
+        print(json.dumps(lines[-1]), flush=True)
+        del model, planner, runner, env
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for l in lines:
+                f.write(json.dumps(l) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -556,3 +556,51 @@ def build_policy(description, device, weights=None, seed=0, random_weights=False
                                         seed=seed + 1, **a)
         planner = P.CEMPlanner(sim, cost, sampler, verbose=verbose, **d.planner_args)
     return model, planner, P.ImageCEMPolicy(model, planner, **d.policy_args)
+
+
+# ---- the environment of a control configuration (video-gcp_amd/control.py) -------------------------------------------------------------
+# Multiroom3dEnv._default_hparams (multiroom3d_env.py:59-71) and TopdownMultiroom3dEnv's crop_window, with KEY_TABLE's discipline:
+#   mapped   a NavEnvBatch parameter;  inert   cannot change what the batched environment computes;  unbuilt  {key: the reference's
+#   default}: any other value raises.  A key in none of the three raises as unknown.
+ENV_KEY_TABLE = {
+    "mapped": {"n_rooms": 9, "crop_window": None},
+    "inert": {"heading_smoothing": "the heading is the direction of the step taken, unsmoothed (as the generator records it)",
+              "obs_height": "no first-person camera: the observation is the top-down frame",
+              "obs_width": "no first-person camera: the observation is the top-down frame"},
+    "unbuilt": {"init_pos": None, "goal_pos": None},
+}
+DEFAULT_CROP_WINDOW = 40      # what the shipped confs and the data collection use (nav_gen.experiment_settings)
+
+
+def environment_from_control_conf(config):
+    """A control conf's `config` (exec_control_conf) -> the batched environment's settings: n_rooms, crop_window, T (agent.T), img_sz
+    (agent.image_height == agent.image_width) and `ignored`, ['<key>:<reason>'] of the environment keys that take no part.  Reads
+    agent.env = (TopdownMultiroom3dEnv, env_params); any other environment class, an unknown key, and init_pos / goal_pos other than
+    None raise.  planner_from_control_conf is not touched: it goes on listing agent.env as the simulator it does not build."""
+    agent = dict(config.get("agent") or {})
+    env = agent.get("env")
+    if not isinstance(env, (list, tuple)) or len(env) != 2 or not isinstance(env[1], dict):
+        raise ValueError(f"agent.env = {env!r}: expected (TopdownMultiroom3dEnv, env_params)")
+    cls = class_name(env[0])
+    if cls != "TopdownMultiroom3dEnv":
+        raise ValueError(f"agent.env names {cls}: only TopdownMultiroom3dEnv is built (the observation is the cropped top-down frame)")
+    out, ignored = dict(ENV_KEY_TABLE["mapped"]), []
+    for k, v in env[1].items():
+        if k in ENV_KEY_TABLE["mapped"]:
+            out[k] = v
+        elif k in ENV_KEY_TABLE["unbuilt"]:
+            if v is not ENV_KEY_TABLE["unbuilt"][k]:
+                raise ValueError(f"agent.env[{k!r}] = {v!r}: not built (only the reference's default, None, is): the tasks give start and goal")
+            ignored.append(f"agent.env.{k}:default")
+        elif k in ENV_KEY_TABLE["inert"]:
+            ignored.append(f"agent.env.{k}:{ENV_KEY_TABLE['inert'][k]}")
+        else:
+            raise ValueError(f"agent.env: unknown TopdownMultiroom3dEnv parameter {k!r}")
+    H, W = agent.get("image_height"), agent.get("image_width")
+    if H is None or H != W:
+        raise ValueError(f"agent.image_height = {H}, agent.image_width = {W}: the observation is a square frame")
+    if "T" not in agent:
+        raise ValueError("agent.T is missing: the number of steps of an episode (GeneralAgent.rollout)")
+    crop = out["crop_window"]
+    return AttrDict(n_rooms=int(out["n_rooms"]), crop_window=int(crop) if crop else DEFAULT_CROP_WINDOW, T=int(agent["T"]), img_sz=int(W),
+                    ignored=ignored)

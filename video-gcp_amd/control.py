@@ -1,0 +1,198 @@
+"""Closed-loop control experiments: `python -m video_gcp_amd.control --experiment <experiments/control/.../mod_hyper.py> --exp_dir D
+--data_dir D [--random_weights 1] [--tasks tasks.npz | --task_seed S] [--n_tasks K] --out OUT`, the reference's
+`python gcp/planning/run.py <mod_hyper.py>`: the planner's actions are executed in the maze, the agent re-observes, and the executed
+trajectories are written for video_gcp_amd.control_perf (compute_control_perf.py).
+
+ControlRunner is the batched form of BenchmarkAgent + ImageCEMPolicy (general_agent.py `rollout`, planner_policy.py:89-113,222-227): the
+executed steps of all E tasks advance together on the device (nav_env.NavEnvBatch).
+  planning    per episode through the planner object, at t = 0 and whenever ImageCEMPolicy.act's condition holds for that episode; a plan's
+              length is known on the host when it is made, so the execution counters are host integers.  A re-plan reads that episode's
+              current frame back: the only read-back of the loop.
+  plans       padded device tensors: latents [E, Lmax, nz], actions [E, Lmax, 2]
+  a step      gather the next planned latent (closed loop) or the planned action (open loop) of every row; the encoder on the current
+              frames; inv_mdl.run_single on all rows; env.step; env.observe
+  the encoder its split-f16 convolution blocks share one power-of-two scale among the frames a workgroup stages (csrc/conv_enc_split.hip),
+              so a frame's latent depends on its batch-mates in the last bits: the closed-loop encoding runs one frame per call, which is
+              the call ImageCEMPolicy._infer_action makes.  The inverse model's rows are independent (csrc/mlp.hip: a row is a column of the
+              MFMA tile) and run as one batch.
+The loop runs agent.T steps, as GeneralAgent.rollout does: no early stop."""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+
+class ControlRunner:
+    """ControlRunner(model, planner, env, replan_interval, num_max_replans, closed_loop_execution).run(tasks) -> results (numpy)"""
+
+    def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False):
+        self.model, self.planner, self.env = model, planner, env
+        self.replan_interval, self.num_max_replans = int(replan_interval), int(num_max_replans)
+        self.closed_loop_execution = bool(closed_loop_execution)
+        self.plans = []               # per episode: [(t, image_plan, action_plan, latent_plan, cost)] of every plan made (host copies)
+
+    # -- planning: ImageCEMPolicy.act's condition and _plan, per episode --
+    def _needs_plan(self, e, t):
+        return (self.plan_len[e] is None or self.plan_len[e] - 1 <= self.exec_step[e]
+                or (t % self.replan_interval == 0 and self.num_replans[e] < self.num_max_replans))
+
+    def _store(self, e, actions, latents):
+        dev = self.env.device
+        n = max(len(latents), len(actions), 1)
+        if self.lat is None:                                # the first plan gives the latents' width
+            self.lat = torch.zeros(self.env.E, max(n, self._lmax), np.asarray(latents).shape[-1], device=dev)
+            self.act = torch.zeros(self.env.E, max(n, self._lmax), self.model._hp.n_actions, device=dev)
+        if n > self.lat.shape[1]:                           # a longer plan than any before: grow the padded tensors
+            grow = lambda x: torch.cat([x, torch.zeros(x.shape[0], n - x.shape[1], x.shape[2], device=dev)], dim=1)
+            self.lat, self.act = grow(self.lat), grow(self.act)
+        self.lat[e, :len(latents)] = torch.as_tensor(np.asarray(latents), dtype=torch.float32).to(dev)
+        if len(actions):
+            self.act[e, :len(actions)] = torch.as_tensor(np.asarray(actions), dtype=torch.float32).reshape(len(actions), -1).to(dev)
+        self.lat_len[e], self.act_len[e] = len(latents), len(actions)
+
+    def _plan(self, e, t):
+        frame = self.env.frames[e, t].cpu().numpy()         # the read-back of a re-plan
+        goal = self.goal_frames_np[e]
+        image_plan, action_plan, latent_plan, cost = self.planner(frame[None], goal[None])
+        actions = np.zeros((0, 2), dtype=np.float32) if action_plan is None else np.asarray(action_plan)
+        self._store(e, actions, np.asarray(latent_plan))
+        self.plan_len[e], self.exec_step[e] = int(np.asarray(image_plan).shape[0]), 0
+        self.num_replans[e] += 1
+        self.plans[e].append(dict(t=t, image_plan=np.asarray(image_plan), action_plan=actions, latent_plan=np.asarray(latent_plan),
+                                  cost=cost))
+
+    # -- acting: ImageCEMPolicy.get_action for all rows --
+    def _encode(self, obs):
+        return torch.cat([self.model.encode(obs[e:e + 1]) for e in range(obs.shape[0])], dim=0)
+
+    def _actions(self, obs):
+        E, dev = self.env.E, self.env.device
+        if self.closed_loop_execution:
+            idx = [s + 1 for s in self.exec_step]
+            bad = [e for e in range(E) if idx[e] >= self.lat_len[e]]
+            if bad:
+                raise IndexError(f"episodes {bad}: the plan has no latent {[idx[e] for e in bad]} (ImageCEMPolicy.get_action)")
+            target = self.lat[torch.arange(E, device=dev), torch.tensor(idx, device=dev)]
+            return self.model.inv_mdl.run_single(self._encode(obs), target)
+        idx =[min(s, max(n - 1, 0)) for s, n in zip(self.exec_step, self.act_len)]
+        bad = [e for e in range(E) if self.act_len[e] >= 1 and self.exec_step[e] >= self.act_len[e]]
+        if bad:
+            raise IndexError(f"episodes {bad}: the action plan is used up (ImageCEMPolicy.get_action)")
+        a = self.act[torch.arange(E, device=dev), torch.tensor(idx, device=dev)]
+        for e in range(E):                                  # planner_policy.py:215-216: an empty action plan acts at random
+            if self.act_len[e] < 1:
+                a[e] = torch.as_tensor(0.05 * np.random.rand(2), dtype=torch.float32).to(dev)
+        return a
+
+    def run(self, tasks):
+        env = self.env
+        obs = env.reset(tasks)
+        E, T, hp = env.E, env.T, self.model._hp
+        self._lmax, self.lat, self.act = hp.max_seq_len + 2, None, None
+        self.plan_len, self.exec_step, self.num_replans = [None] * E, [None] * E, [0] * E
+        self.lat_len, self.act_len = [0] * E, [0] * E
+        self.plans = [[] for _ in range(E)]
+        self.goal_frames_np = env.goal_frames.cpu().numpy()
+        for t in range(T):
+            for e in range(E):
+                if self._needs_plan(e, t):
+                    self._plan(e, t)
+            env.step(self._actions(obs))
+            self.exec_step = [s + 1 for s in self.exec_step]
+            obs = env.observe()
+        res = env.eval()
+        res["reset_state"] = np.concatenate([np.asarray(tasks["start"], dtype=np.float32).reshape(E, 3),
+                                             np.asarray(tasks["goal"], dtype=np.float32).reshape(E, 2)], axis=1)
+        res["term_t"] = np.full(E, T - 1, dtype=np.int64)   # every episode runs its T steps
+        res["actions"] = env.actions.cpu().numpy()
+        res["n_replans"] = np.array(self.num_replans, dtype=np.int64)
+        return res
+
+
+RESULT_KEYS = ("improvement", "initial_dist", "final_dist", "all_goal_distances", "full_traj", "goal", "path_len", "blocked", "reset_state",
+               "term_t", "actions")
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--experiment", required=True, help="a control configuration in the reference's format (mod_hyper.py)")
+    p.add_argument("--data_dir", default="", help="GCP_DATA_DIR as the --experiment file sees it")
+    p.add_argument("--exp_dir", default="", help="GCP_EXP_DIR as the --experiment file sees it")
+    p.add_argument("--random_weights", type=int, default=0, help="1 = run on the seeded initialisation when the conf's checkpoint does not "
+                   "resolve (an error otherwise)")
+    p.add_argument("--weights", default="", help="a checkpoint file instead of the conf's")
+    p.add_argument("--tasks", default="", help=".npz with `start` [K, 3] and `goal` [K, 2] in the environment's units")
+    p.add_argument("--task_seed", type=int, default=0, help="without --tasks: the seed of the drawn tasks (NavGenerator.draw_task)")
+    p.add_argument("--n_tasks", type=int, default=None, help="at most this many of the tasks start_index .. end_index of the conf")
+    p.add_argument("--batch", type=int, default=100, help="episodes advanced together")
+    p.add_argument("--T", type=int, default=None, help="steps per episode instead of the conf's agent.T")
+    p.add_argument("--topdown_assets", default="", help="a nav dataset's topdown_assets.npz: the observation is rendered from its picture "
+                   "(what the model was trained on), and OUT/task_{i}_traj.png shows the executed trajectory of every task")
+    p.add_argument("--out", required=True, help="directory for control_results.npz")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--reference_rng", action="store_true", help="the hierarchical planner replays the reference's np.random sequence")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    from . import conf_loader as CL
+    from . import nav_env as NE
+    args = get_args(argv)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    # the shipped confs read both names while they execute; a name given nowhere gets a placeholder (with --random_weights no path is read)
+    environ = {k: v or k.lower() for k, v in (("GCP_DATA_DIR", args.data_dir), ("GCP_EXP_DIR", args.exp_dir)) if v or k not in os.environ}
+    conf = CL.exec_control_conf(args.experiment, environ)
+    desc, env_desc = CL.planner_from_control_conf(conf), CL.environment_from_control_conf(conf)
+    for k in env_desc.ignored:
+        print(f"[control] not used from {os.path.basename(args.experiment)}: {k}", flush=True)
+    model, planner, _ = CL.build_policy(desc, dev, weights=args.weights or None, seed=args.seed, random_weights=bool(args.random_weights),
+                                        reference_rng=args.reference_rng, verbose=False)
+    if not model._hp.attach_inv_mdl:
+        raise ValueError("the control loop needs the inverse model (attach_inv_mdl) for its actions")
+    assets = None
+    if args.topdown_assets:
+        from .dataset import load_topdown_assets
+        assets = load_topdown_assets(args.topdown_assets)
+    T = int(args.T) if args.T else env_desc.T
+    # run.py: the tasks start_index .. end_index (inclusive)
+    lo = int(desc.pairs[0] or 0)
+    if args.tasks:
+        tasks = NE.load_tasks(args.tasks)
+        hi = min(int(desc.pairs[1]) if desc.pairs[1] is not None else len(tasks["start"]) - 1, len(tasks["start"]) - 1)
+        idx = list(range(lo, hi + 1))
+        tasks = {k: v[idx] for k, v in tasks.items()}
+    else:
+        hi = int(desc.pairs[1]) if desc.pairs[1] is not None else lo + (args.n_tasks or 100) - 1
+        idx = list(range(lo, hi + 1))
+        if args.n_tasks is not None:
+            idx = idx[:args.n_tasks]
+        tasks = NE.draw_tasks(env_desc.n_rooms, args.task_seed, idx)
+    if args.n_tasks is not None:
+        idx = idx[:args.n_tasks]
+        tasks = {k: v[:args.n_tasks] for k, v in tasks.items()}
+    if not idx:
+        raise ValueError("no task selected (start_index .. end_index of the conf, --n_tasks)")
+    env = NE.NavEnvBatch(env_desc.n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev, assets=assets)
+    runner = ControlRunner(model, planner, env, **desc.policy_args)
+    parts = []
+    for s in range(0, len(idx), max(args.batch, 1)):
+        parts.append(runner.run({k: v[s:s + max(args.batch, 1)] for k, v in tasks.items()}))
+    res = {k: np.concatenate([p[k] for p in parts], axis=0) for k in RESULT_KEYS}
+    os.makedirs(args.out, exist_ok=True)
+    path = os.path.join(args.out, "control_results.npz")
+    np.savez_compressed(path, task_index=np.array(idx, dtype=np.int64), **res)
+    if args.topdown_assets:
+        from .image_log import TrajectoryRenderer, write_trajectory_png
+        renderer = TrajectoryRenderer(assets, dev)
+        for k, i in enumerate(idx):
+            write_trajectory_png(os.path.join(args.out, f"task_{i}_traj.png"), renderer, res["full_traj"][k, :, :2], dev, lib=model.lib)
+    print(json.dumps({"tasks": len(idx), "T": T, "results": path, "mean_final_dist": float(np.mean(res["final_dist"])),
+                      "blocked_steps": int(res["blocked"].sum())}), flush=True)
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,7 @@ Counterpart of the device path behind /root/reference/gcp/planning/run.py: for e
 (`CEMPlanner` / `HierarchicalCEMPlanner`, gcp/planning/cem/cem_planner.py:55-218) searches the latent space of the
 goal-conditioned predictor and returns (image_plan, actions, latents, cost) (cem_planner.py:96).  What run.py adds around
 that — the MiniWorld simulator, agents, policies, trajectory savers (gcp/planning/infra/*) — is host infrastructure outside
-SURVEY.md §8 and is not rebuilt: start / goal frames come from an .npz (`--pairs file.npz` with uint8 arrays `start`,
+SURVEY.md §8 and is not rebuilt here (the executed loop is video_gcp_amd.control): start / goal frames come from an .npz (`--pairs file.npz` with uint8 arrays `start`,
 `goal` [K, H, W, 3]) or are seeded synthetic images.  Two ways to use several GPUs, as in the reference and in SURVEY §8(e):
   * one process per GPU over disjoint pair ranges (run.py:78-94 splits start_index..end_index over workers) — `--split pairs`;
   * one process per GPU sharing every CEM population (candidates sharded, one all-gather of costs per iteration) —

@@ -279,6 +279,9 @@ SYMBOLS = [
                                    C.c_double, C.c_double, vp, vp, vp, vp, vp]),
     ("gcpx_prm_shortest_path", C.c_int, [vp, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]),
     ("gcpx_prm_resample", C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    ("gcpx_nav_env_reset", C.c_int, [vp, vp, i32, C.c_double, i32, i32, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp]),
+    ("gcpx_nav_env_step", C.c_int, [vp, vp, vp, i32, C.c_double, vp, i32, C.c_double, i32, i32, i32, C.c_float, C.c_float, i32, i32,
+                                    vp, vp, vp, vp, vp, vp]),
 ]
 
 _lib = None
