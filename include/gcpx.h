@@ -1293,6 +1293,43 @@ int gcpx_nav_env_step(float* state, const float* action, const double* walls, in
                       int32_t S, int32_t cw, float* full_traj, double* path_len, double* goal_dist, uint8_t* blocked, int32_t* pix,
                       void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The hierarchical latent search for K planning tasks at once (video-gcp_amd/tree_latent_search.py:
+ * BatchedDeviceTreeLatentOptimizer; csrc/tree_search.hip): the per-decision steps of
+ * HierarchicalTreeLatentOptimizer (gcp/planning/tree_optimizer.py), each one launch over all tasks.  Which level is drawn, optimised
+ * and how the population is laid out does not depend on the task, so K tasks share one walk; only these tables differ per task.
+ *
+ * lat [n_rows][T][nz] float32: the rollout's latents, rows k*n .. k*n+n-1 of task k, then one stand-in row [inf, 0, inf, 0 ...] for a
+ *   rollout too short to split (tree_optimizer.py:142-147).  nz % 4 == 0.
+ * views [K][G][3] int32 = (row, a, b): candidate g of task k is lat[row][a:b].
+ * goal [K][2] int32 = (row, frame); row < 0: every candidate's own last frame b - 1 (the raw goal image, tree_optimizer.py:99-101).
+ * Row and frame indices are clamped into `lat` before they are used.  Every launch is on `stream`; nothing is allocated or read back.
+ *
+ * gcpx_tree_subgoal_rows (tree_optimizer.py:92-105): the operands of both pair costs of every candidate, m = (b - a) / 2:
+ *   opa, opb [2][K][G][nz]: opa[0] = lat[row][a], opb[0] = opa[1] = lat[row][a + m], opb[1] = the goal latent; mids [K][G] = m.
+ * gcpx_tree_select (tree_optimizer.py:106-110, 81-82, 179): per task total[g] = c1[k][g] + c2[k][g] (one float32 add; c2 NULL: c1),
+ *   numpy's argmin over the candidates with mask[k][g] != 0 (mask NULL: all): the first NaN when there is one, else the first minimum
+ *   -> idx [K], cost [K]; no candidate: idx = -1, cost = +inf.  draw [K][G][zf] != NULL: best_z [K][zf] = the chosen row (zf % 4 == 0).
+ * gcpx_tree_split_views (tree_optimizer.py:142-155): short [K][G] = (b - a < 3); such a candidate becomes (dummy_row, 0, 3); then
+ *   c = (b - a) / 2, left = (row, a, a + c), right = (row, a + c, b), left_goal [K][2] = (row, a + c) of the task's candidate 0.
+ * gcpx_tree_segment_windows (tree_optimizer.py:79-84, 175-180): seg [K*G][tmax][nz] = lat[row][a:b] zero padded, lens [K*G] =
+ *   min(b - a, tmax), goal_rows [K*G][nz]: what gcpx_seq_pairs / gcpx_masked_row_sum take.
+ * gcpx_tree_short_alternative (tree_optimizer.py:157-163): c = lc[k] + rc[k] (one float32 add); use_short[k] = sidx[k] >= 0 and
+ *   (sc[k] < c or isnan(c)); cost[k] = use_short ? sc[k] : c.
+ *
+ * GCPX_ERR_INVALID_ARG, nothing launched: a null pointer (c2, mask, draw with best_z may be NULL), a size <= 0, K*G > 2^24,
+ *   nz or zf not a multiple of 4, dummy_row < 0. */
+int gcpx_tree_subgoal_rows(const float* lat, const int32_t* views, const int32_t* goal, float* opa, float* opb, int32_t* mids,
+                           int32_t K, int32_t G, int32_t n_rows, int32_t T, int32_t nz, void* stream);
+int gcpx_tree_select(const float* c1, const float* c2, const int32_t* mask, const float* draw, float* best_z, int32_t* idx, float* cost,
+                     int32_t K, int32_t G, int32_t zf, void* stream);
+int gcpx_tree_split_views(const int32_t* views, int32_t dummy_row, int32_t* left, int32_t* right, int32_t* left_goal, int32_t* short_,
+                          int32_t K, int32_t G, void* stream);
+int gcpx_tree_segment_windows(const float* lat, const int32_t* views, const int32_t* goal, float* seg, int32_t* lens, float* goal_rows,
+                              int32_t K, int32_t G, int32_t n_rows, int32_t T, int32_t tmax, int32_t nz, void* stream);
+int gcpx_tree_short_alternative(const float* lc, const float* rc, const float* sc, const int32_t* sidx, float* cost, int32_t* use_short,
+                                int32_t K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

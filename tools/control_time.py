@@ -8,6 +8,10 @@ Both loops make the same plans per episode (at t = 0 and when a plan is used up)
 that `steps_per_s` (everything) and `exec_steps_per_s` (planner time taken out) can both be read.  --steps caps agent.T.
 Also measured once: the largest difference between the encoder + inverse model on a frame alone and on the same frame in a batch of 3
 (`row_alone_vs_batch3_max_abs`), the figure behind the runner's one-frame-per-call encoding.
+--batch_plans: instead of the serial loop, the batched loop twice over the same tasks, --repeats times each: plans per episode (the
+planner call of the loop above) and plans per step (ControlRunner(batch_plans=True): HierarchicalCEMPlanner.plan_batch); planner
+seconds, calls, tasks per call and the t = 0 call (all --E tasks) apart, each as the list of the repeats.  --max_rows: the rows per
+forward of plan_batch (one value: used by the loop; several: the t = 0 call alone is timed with each first).
 Prints one JSON line per shape; --out appends them to a file under profiles/.
 """
 import argparse
@@ -55,6 +59,20 @@ class TimedPlanner:
 
     def __init__(self, planner, torch):
         self.planner, self.torch, self.seconds, self.calls = planner, torch, 0.0, 0
+        self.tasks_per_call, self.first_call_s, self.max_rows = [], None, None
+
+    def plan_batch(self, states, goals):
+        self.torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = self.planner.plan_batch(states, goals, max_rows=self.max_rows)
+        self.torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        self.seconds += dt
+        self.calls += 1
+        self.tasks_per_call.append(len(states))
+        if self.first_call_s is None:
+            self.first_call_s = dt
+        return out
 
     def __call__(self, state, goal):
         self.torch.cuda.synchronize()
@@ -66,6 +84,55 @@ class TimedPlanner:
         return out
 
 
+def time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T):
+    """the batched loop with plans per episode and with plans per step, --repeats runs each, on the same tasks"""
+    import numpy as np
+    row = {"workload": "control_time", "batch_plans": True, "n_rooms": n_rooms, "E": a.E, "T": T, "max_seq_len": desc.hp.max_seq_len,
+           "repeats": a.repeats}
+    sweep = a.max_rows or [planner.MAX_ROWS]
+    if len(sweep) > 1:                                   # the t = 0 call alone, per rows-per-forward (second of two calls: the first warms up)
+        env.reset(tasks)
+        frames, goals = env.frames[:, 0].cpu().numpy(), env.goal_frames.cpu().numpy()
+        row["t0_call_s_by_max_rows"] = {}
+        for mr in sweep:
+            timed = TimedPlanner(planner, torch)
+            timed.max_rows = mr
+            timed.plan_batch(frames, goals)
+            timed.first_call_s = None
+            timed.plan_batch(frames, goals)
+            row["t0_call_s_by_max_rows"][str(mr)] = round(timed.first_call_s, 4)
+        best = min(sweep, key=lambda mr: row["t0_call_s_by_max_rows"][str(mr)])
+    else:
+        best = sweep[0]
+    row["max_rows"] = best
+    runs = {False: [], True: []}
+    for flag in (False, True):
+        timed = TimedPlanner(planner, torch)
+        timed.max_rows = best
+        runner = CT.ControlRunner(model, timed, env, batch_plans=flag, **desc.policy_args)
+        runner.run({k: v[:2] for k, v in tasks.items()})            # warm-up: plans and buffers of both kinds of call
+        for _ in range(a.repeats):
+            timed.seconds, timed.calls, timed.tasks_per_call, timed.first_call_s = 0.0, 0, [], None
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = runner.run(tasks)
+            torch.cuda.synchronize()
+            runs[flag].append(dict(wall=time.perf_counter() - t0, planner=timed.seconds, calls=timed.calls, plans=int(res["n_replans"].sum()),
+                                   tasks=list(timed.tasks_per_call), first=timed.first_call_s))
+    per, bat = runs[False], runs[True]
+    r3 = lambda xs: [round(x, 4) for x in xs]
+    row.update(per_episode_wall_s=r3([r["wall"] for r in per]), per_episode_planner_s=r3([r["planner"] for r in per]),
+               per_episode_plans=[r["plans"] for r in per],
+               per_episode_ms_per_plan=r3([1e3 * r["planner"] / max(r["plans"], 1) for r in per]),
+               batched_wall_s=r3([r["wall"] for r in bat]), batched_planner_s=r3([r["planner"] for r in bat]),
+               batched_plans=[r["plans"] for r in bat], plan_batch_calls=[r["calls"] for r in bat],
+               tasks_per_call_mean=r3([float(np.mean(r["tasks"])) for r in bat]), tasks_per_call_max=[int(max(r["tasks"])) for r in bat],
+               batched_ms_per_plan=r3([1e3 * r["planner"] / max(r["plans"], 1) for r in bat]),
+               t0_call_s=r3([r["first"] for r in bat]),
+               t0_call_ms_per_plan=r3([1e3 * r["first"] / r["tasks"][0] for r in bat]))
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--E", type=int, default=100)
@@ -73,6 +140,9 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="steps per episode (default: the conf's agent.T, 200 / 400)")
     ap.add_argument("--rooms", type=int, nargs="+", default=[9, 25])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batch_plans", action="store_true", help="time planning per step (plan_batch) beside planning per episode")
+    ap.add_argument("--repeats", type=int, default=3, help="--batch_plans: runs of each loop")
+    ap.add_argument("--max_rows", type=int, nargs="+", default=None, help="--batch_plans: candidate rows per forward of plan_batch")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -104,6 +174,13 @@ def main():
         alone = torch.cat([model.inv_mdl.run_single(model.encode(obs[e:e + 1]), target[e:e + 1]) for e in range(3)])
         row_diff = float((together - alone).abs().max())
         enc_diff = float((model.encode(obs) - torch.cat([model.encode(obs[e:e + 1]) for e in range(3)])).abs().max())
+
+        if a.batch_plans:
+            lines.append(time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T))
+            print(json.dumps(lines[-1]), flush=True)
+            del model, planner, env
+            torch.cuda.empty_cache()
+            continue
 
         # batched
         timed = TimedPlanner(planner, torch)

@@ -7,7 +7,8 @@ ControlRunner is the batched form of BenchmarkAgent + ImageCEMPolicy (general_ag
 executed steps of all E tasks advance together on the device (nav_env.NavEnvBatch).
   planning    per episode through the planner object, at t = 0 and whenever ImageCEMPolicy.act's condition holds for that episode; a plan's
               length is known on the host when it is made, so the execution counters are host integers.  A re-plan reads that episode's
-              current frame back: the only read-back of the loop.
+              current frame back: the only read-back of the loop.  With batch_plans (--batch_plans 1) the episodes that plan at a step
+              plan together: one read-back of their frames, one HierarchicalCEMPlanner.plan_batch call.
   plans       padded device tensors: latents [E, Lmax, nz], actions [E, Lmax, 2]
   a step      gather the next planned latent (closed loop) or the planned action (open loop) of every row; the encoder on the current
               frames; inv_mdl.run_single on all rows; env.step; env.observe
@@ -25,10 +26,13 @@ import torch
 
 
 class ControlRunner:
-    """ControlRunner(model, planner, env, replan_interval, num_max_replans, closed_loop_execution).run(tasks) -> results (numpy)"""
+    """ControlRunner(model, planner, env, replan_interval, num_max_replans, closed_loop_execution).run(tasks) -> results (numpy)
+    batch_plans: the episodes that plan at a step plan together, one `planner.plan_batch` call (HierarchicalCEMPlanner) and one read-back
+    of their frames per step; off (the default), every episode plans through its own planner call."""
 
-    def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False):
+    def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_plans=False):
         self.model, self.planner, self.env = model, planner, env
+        self.batch_plans = bool(batch_plans)
         self.replan_interval, self.num_max_replans = int(replan_interval), int(num_max_replans)
         self.closed_loop_execution = bool(closed_loop_execution)
         self.plans = []               # per episode: [(t, image_plan, action_plan, latent_plan, cost)] of every plan made (host copies)
@@ -56,6 +60,15 @@ class ControlRunner:
         frame = self.env.frames[e, t].cpu().numpy()         # the read-back of a re-plan
         goal = self.goal_frames_np[e]
         image_plan, action_plan, latent_plan, cost = self.planner(frame[None], goal[None])
+        self._record(e, t, image_plan, action_plan, latent_plan, cost)
+
+    def _plan_batch(self, due, t):
+        """the episodes `due` at step t through one planner.plan_batch call; their frames come back in one copy"""
+        frames = self.env.frames[torch.as_tensor(due, device=self.env.device), t].cpu().numpy()
+        for e, r in zip(due, self.planner.plan_batch(frames, self.goal_frames_np[due])):
+            self._record(e, t, r.predictions, r.actions, r.latents, r.cost)
+
+    def _record(self, e, t, image_plan, action_plan, latent_plan, cost):
         actions = np.zeros((0, 2), dtype=np.float32) if action_plan is None else np.asarray(action_plan)
         self._store(e, actions, np.asarray(latent_plan))
         self.plan_len[e], self.exec_step[e] = int(np.asarray(image_plan).shape[0]), 0
@@ -96,9 +109,14 @@ class ControlRunner:
         self.plans = [[] for _ in range(E)]
         self.goal_frames_np = env.goal_frames.cpu().numpy()
         for t in range(T):
-            for e in range(E):
-                if self._needs_plan(e, t):
-                    self._plan(e, t)
+            if self.batch_plans:
+                due = [e for e in range(E) if self._needs_plan(e, t)]
+                if due:
+                    self._plan_batch(due, t)
+            else:
+                for e in range(E):
+                    if self._needs_plan(e, t):
+                        self._plan(e, t)
             env.step(self._actions(obs))
             self.exec_step = [s + 1 for s in self.exec_step]
             obs = env.observe()
@@ -133,6 +151,8 @@ def get_args(argv=None):
     p.add_argument("--out", required=True, help="directory for control_results.npz")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reference_rng", action="store_true", help="the hierarchical planner replays the reference's np.random sequence")
+    p.add_argument("--batch_plans", type=int, default=0, help="1 = the episodes that plan at a step plan together (the hierarchical planner's "
+                   "plan_batch): not the per-episode planner's bits, see DESIGN.md 5.7; not with --reference_rng")
     return p.parse_args(argv)
 
 
@@ -140,6 +160,8 @@ def main(argv=None):
     from . import conf_loader as CL
     from . import nav_env as NE
     args = get_args(argv)
+    if args.batch_plans and args.reference_rng:
+        raise ValueError("--batch_plans 1 plans on a device generator; the reference's np.random stream (--reference_rng) is defined per plan")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     # the shipped confs read both names while they execute; a name given nowhere gets a placeholder (with --random_weights no path is read)
@@ -176,7 +198,9 @@ def main(argv=None):
     if not idx:
         raise ValueError("no task selected (start_index .. end_index of the conf, --n_tasks)")
     env = NE.NavEnvBatch(env_desc.n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev, assets=assets)
-    runner = ControlRunner(model, planner, env, **desc.policy_args)
+    if args.batch_plans and not hasattr(planner, "plan_batch"):
+        raise ValueError(f"--batch_plans 1 needs the hierarchical planner; the conf builds {type(planner).__name__}")
+    runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), **desc.policy_args)
     parts = []
     for s in range(0, len(idx), max(args.batch, 1)):
         parts.append(runner.run({k: v[s:s + max(args.batch, 1)] for k, v in tasks.items()}))

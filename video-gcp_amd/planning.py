@@ -676,6 +676,82 @@ class HierarchicalCEMPlanner:
         return Outputs(predictions=final.predictions[0], actions=actions, latents=final.latents[0],
                        cost=float(np.asarray(best_scores[0]).reshape(-1)[0]), states=states[0] if states is not None else None)
 
+    # K tasks per forward: measured at the 25-room control shape — the scoring rollouts of whole tasks are chunked so
+    # that one forward carries at most this many candidate rows
+    MAX_ROWS = 1000
+
+    def _rollout_chunks(self, states, goals, z, n, max_rows, decode, len_u):
+        """sim.rollout_device (decode=False) / sim.rollout (decode=True) of K * n rows, task k's n rows with its own start and goal image,
+        whole tasks per forward"""
+        K = states.shape[0]
+        per = max(int(max_rows) // n, 1)
+        parts = []
+        for lo in range(0, K, per):
+            hi = min(lo + per, K)
+            rows = slice(lo * n, hi * n)
+            kw = {} if len_u is None else dict(len_u=len_u((hi - lo) * n))
+            s, g = np.repeat(states[lo:hi], n, axis=0), np.repeat(goals[lo:hi], n, axis=0)
+            if decode:
+                parts.append(self._sim.rollout(s, g, z[rows], self.max_seq_len, **kw))
+                continue
+            r = self._sim.rollout_device(s, g, z[rows], self.max_seq_len, decode=False, **kw)
+            # (the forward's buffers are reused by the next rollout of the same size)
+            parts.append((r.latents.clone(), r.lengths.clone()) if K > per else (r.latents, r.lengths))
+        if decode or len(parts) == 1:
+            return parts
+        return [(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))]
+
+    def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None):
+        """K tasks planned together: states, goals [K, H, W, 3] env images -> a list of K Outputs with the fields of `plan`.
+        One walk of the search tree for all tasks (tree_latent_search.BatchedDeviceTreeLatentOptimizer): every iteration is one
+        population draw, the scoring rollout of the K * n candidates (whole tasks per forward, at most `max_rows` rows), and one
+        launch per decision over all tasks; nothing of the search is read back before the end.  Then one decoded rollout of the K
+        optimised trees.  Under a process group every rank runs the whole batch, as `plan` does.
+
+        Not the bits of `plan` task by task: the generator's draws are consumed in another order, and a forward of K * n rows need
+        not equal one of n rows in the last bits (the encoder's split-f16 blocks share a scale among the frames a workgroup
+        stages) — the same search on another sample, which is why this is a path of its own.  Needs the device-resident search on a
+        device generator (`fast_draws`): the reference's np.random stream is defined per plan, and so are the verbose logs.
+        record: keep the draw blocks, the populations, the scoring rollouts' latents and lengths and the optimizer in `self.batch_record`.
+        len_u: f(rows) -> the length draws of a rollout of that many rows (default: the model's own), for pred_length simulators."""
+        from .tree_latent_search import BatchedDeviceTreeLatentOptimizer
+        s = self._sampler
+        if self.verbose:
+            raise ValueError("plan_batch keeps no verbose logs (they are defined per plan): use plan()")
+        if not self.device_resident or not isinstance(s._rng, torch.Generator):
+            raise ValueError("plan_batch needs the device-resident search with fast_draws on the model's device; the reference's np.random "
+                             "stream is defined per plan: use plan()")
+        states, goals = np.asarray(states), np.asarray(goals)
+        if states.ndim != 4 or states.shape != goals.shape:
+            raise ValueError("plan_batch takes states and goals [K, H, W, 3]")
+        K = states.shape[0]
+        max_rows = self.MAX_ROWS if max_rows is None else int(max_rows)
+        opt = BatchedDeviceTreeLatentOptimizer(s._action_dim, s._rates.copy(), s._n_levels, s._sub_cost, s._ll_cost, s._n_ll, K, s._rng,
+                                               record=record)
+        clip = (lambda z: z.clamp(-s._clip_val, s._clip_val)) if np.isfinite(s._clip_val) else (lambda z: z)
+        self.logs, rollouts, populations = [], [], []
+        for it in range(self.n_iters):
+            z = clip(opt.sample())                                                 # [K, n, nodes, dim]
+            n = z.shape[1]
+            (lat, lens), = self._rollout_chunks(states, goals, z.reshape((K * n,) + tuple(z.shape[2:])), n, max_rows, False, len_u)
+            if record:
+                populations.append(z)
+                rollouts.append((lat.clone(), lens.clone()))
+            cost = opt.optimize(Outputs(latents=lat, lengths=lens))
+            self.logs.append(Outputs(elite_scores=cost))
+        opt.record = False
+        best = clip(opt.sample())[:, 0]                                            # everything optimised: no randomness left in it
+        self.batch_record = Outputs(optimizer=opt, draws=opt.draws, populations=populations, rollouts=rollouts, best_samples=best) if record else None
+        costs = cost.cpu().numpy()
+        zb = best.cpu().numpy()
+        out = []
+        for k0, final in zip(range(0, K, max(max_rows, 1)), self._rollout_chunks(states, goals, zb, 1, max_rows, True, len_u)):
+            st = final.get("states")
+            for j in range(len(final.predictions)):
+                out.append(Outputs(predictions=final.predictions[j], actions=final.actions[j] if final.actions is not None else None,
+                                   latents=final.latents[j], cost=float(costs[k0 + j]), states=st[j] if st is not None else None))
+        return out
+
     def _verbose_entry(self, r, best_rollouts, best_scores, goal):
         """cem_planner.py:215-218 as logged at :72-78: the elite rollout is the one optimised plan, the elite states are the states of
         ALL rollouts of the iteration.  Device-resident: the plan is (row, frame) references into the scoring rollout, which decoded

@@ -282,6 +282,11 @@ SYMBOLS = [
     ("gcpx_nav_env_reset", C.c_int, [vp, vp, i32, C.c_double, i32, i32, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp]),
     ("gcpx_nav_env_step", C.c_int, [vp, vp, vp, i32, C.c_double, vp, i32, C.c_double, i32, i32, i32, C.c_float, C.c_float, i32, i32,
                                     vp, vp, vp, vp, vp, vp]),
+    ("gcpx_tree_subgoal_rows", C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    ("gcpx_tree_select", C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    ("gcpx_tree_split_views", C.c_int, [vp, i32, vp, vp, vp, vp, i32, i32, vp]),
+    ("gcpx_tree_segment_windows", C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    ("gcpx_tree_short_alternative", C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp]),
 ]
 
 _lib = None

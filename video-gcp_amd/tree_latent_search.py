@@ -341,3 +341,326 @@ class DeviceHierarchicalTreeLatentOptimizer(ImageHierarchicalTreeLatentOptimizer
             results.append((best, cost))
         k = int(np.argmin(np.array([c for _, c in results])))
         return results[k]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# K tasks per walk
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The walk of _draw_device / _dopt* does not depend on the task: which level is drawn, which is optimised and how the population is laid
+# out are the same for every task; only the views, the short-rollout cases and the chosen indices differ.  Each decision below is one
+# library call over all K tasks (csrc/tree_search.hip) or, on CPU tensors, its torch mirror — the kernel's checker
+# (tests/test_gpu_tree_search.py) and what lets the walk run without a device in the CPU tests (the convention of
+# scalar_log.segment_norms_numpy); the mirrors are not a product path: tensors on a device always go through the library.
+
+def _at(lat, row, frame):
+    return lat[row.clamp(0, lat.shape[0] - 1), frame.clamp(0, lat.shape[1] - 1)]
+
+
+def _goal_latents(lat, views, goal):
+    v = views.long()
+    row, b = v[..., 0], v[..., 2]
+    gr, gf = goal[:, :1].long().expand_as(row), goal[:, 1:].long().expand_as(row)
+    raw = gr < 0
+    import torch
+    return _at(lat, torch.where(raw, row, gr), torch.where(raw, b - 1, gf))
+
+
+def subgoal_rows_torch(lat, views, goal):
+    """gcpx_tree_subgoal_rows: lat [R, T, nz], views int32 [K, G, 3], goal int32 [K, 2] -> opa, opb [2 K G, nz], mids int32 [K, G]"""
+    import torch
+    v = views.long()
+    row, a, b = v[..., 0], v[..., 1], v[..., 2]
+    m = torch.where(b > a, (b - a) // 2, torch.zeros_like(a))
+    start, sub, gl = _at(lat, row, a), _at(lat, row, a + m), _goal_latents(lat, views, goal)
+    nz = lat.shape[-1]
+    return torch.stack([start, sub]).reshape(-1, nz), torch.stack([sub, gl]).reshape(-1, nz), m.to(torch.int32)
+
+
+def select_torch(c1, c2=None, mask=None, draw=None):
+    """gcpx_tree_select: c1, c2 [K, G] float32, mask int32 [K, G], draw [K, G, zf] -> idx int32 [K], cost [K], best_z [K, zf] or None"""
+    import torch
+    total = c1 if c2 is None else c1 + c2
+    K, G = total.shape
+    ok = torch.ones_like(total, dtype=torch.bool) if mask is None else mask != 0
+    ar = torch.arange(G, device=total.device).expand(K, G)
+    none = torch.full_like(ar, G)
+    nan = torch.isnan(total) & ok
+    num = ok & ~nan
+    low = torch.where(num, total, torch.full_like(total, float("inf"))).min(1, keepdim=True).values
+    first_nan = torch.where(nan, ar, none).min(1).values
+    first_min = torch.where(num & (total == low), ar, none).min(1).values
+    idx = torch.where(first_nan < G, first_nan, first_min)                      # np.argmin: the first NaN, else the first minimum
+    found = idx < G
+    at = torch.where(found, idx, torch.zeros_like(idx))
+    cost = torch.where(found, total.gather(1, at[:, None])[:, 0], torch.full_like(total[:, 0], float("inf")))
+    best = None if draw is None else draw[torch.arange(K, device=total.device), at]
+    return torch.where(found, idx, torch.full_like(idx, -1)).to(torch.int32), cost, best
+
+
+def split_views_torch(views, dummy_row):
+    """gcpx_tree_split_views: views int32 [K, G, 3] -> left, right int32 [K, G, 3], left_goal int32 [K, 2], short int32 [K, G]"""
+    import torch
+    row, a, b = views[..., 0], views[..., 1], views[..., 2]
+    short = (b - a) < 3
+    row = torch.where(short, torch.full_like(row, dummy_row), row)
+    a = torch.where(short, torch.zeros_like(a), a)
+    b = torch.where(short, torch.full_like(b, 3), b)
+    c = (b - a) // 2
+    left, right = torch.stack([row, a, a + c], -1), torch.stack([row, a + c, b], -1)
+    return left, right, torch.stack([row[:, 0], (a + c)[:, 0]], -1), short.to(torch.int32)
+
+
+def segment_windows_torch(lat, views, goal, tmax):
+    """gcpx_tree_segment_windows: -> seg [K G, tmax, nz] (zero padded), lens int32 [K G], goal_rows [K G, nz]"""
+    import torch
+    v = views.long().reshape(-1, 3)
+    row, a, b = v[:, 0], v[:, 1], v[:, 2]
+    lens = (b - a).clamp(0, tmax)
+    t = torch.arange(tmax, device=lat.device)
+    seg = _at(lat, row[:, None].expand(-1, tmax), a[:, None] + t[None])
+    seg = torch.where((t[None] < lens[:, None])[..., None], seg, torch.zeros_like(seg))
+    return seg, lens.to(torch.int32), _goal_latents(lat, views, goal).reshape(-1, lat.shape[-1])
+
+
+def short_alternative_torch(lc, rc, sc, sidx):
+    """gcpx_tree_short_alternative: -> cost [K], use_short int32 [K]"""
+    import torch
+    c = lc + rc
+    use = (sidx >= 0) & ((sc < c) | torch.isnan(c))
+    return torch.where(use, sc, c), use.to(torch.int32)
+
+
+class BatchedDeviceTreeLatentOptimizer:
+    """DeviceHierarchicalTreeLatentOptimizer for K tasks at once: the same `_Level` tree and the same walk, a leading task axis on every
+    tensor.  `best_z`, `last_draw`, the views, the selections and the costs are device tensors; a decision is one launch over all K
+    tasks, a cost one Predictor call over the rows of all tasks, and nothing is read back until somebody asks for the plans.
+
+    Draws come from one torch.Generator, in the order and block shapes of `_draw` in generator mode, each block with a leading K.
+    Task k of the batch is the per-task search on the sample `[k]` of every block: tests/test_tree_search_cpu.py replays the blocks
+    into K per-task searches and compares populations, costs, plans and optimised trees bit for bit."""
+
+    def __init__(self, latent_dim, sampling_rates, depth, subgoal_cost_fcn, ll_cost_fcn, final_layer_samples, n_tasks, rng, record=False):
+        import torch
+        assert isinstance(rng, torch.Generator), "the batched search draws on the rollouts' device: rng is a torch.Generator"
+        self._rng, self._dim, self.n_tasks = rng, latent_dim, int(n_tasks)
+        self._pair_cost, self._seq_cost = subgoal_cost_fcn, ll_cost_fcn
+        self._root = _build(list(sampling_rates), depth, final_layer_samples)
+        self.record, self.draws = bool(record), []
+        self.costs, self._records, self._tables = [], [], None
+
+    # ------------------------------------------------------------------ sampling
+    def sample(self):
+        """[K, n, 2^depth - 1, latent_dim], node axis depth-first"""
+        return self._bdraw(self._root, False)
+
+    def _randn(self, s0, s1):
+        import torch
+        z = torch.randn(self.n_tasks, s0, s1, self._dim, generator=self._rng, device=self._rng.device)
+        if self.record:
+            self.draws.append(z)
+        return z
+
+    def _bdraw(self, lv, below):
+        import torch
+        if below:
+            assert not lv.done
+            return self._randn(1, 2 ** lv.depth - 1)
+        if lv.done:
+            z = lv.best_z[:, None]
+        else:
+            z = lv.last_draw = self._randn(lv.n_samples, lv.n_latents)
+        if lv.left is None:
+            return z
+        rows = []
+        for i, (cl, cr) in enumerate(zip(lv.left, lv.right)):
+            zl, zr = self._bdraw(cl, not lv.done), self._bdraw(cr, not lv.done)
+            rows.append(torch.cat([zl, z[:, i, None, :1].expand(-1, zl.shape[1], -1, -1), zr], dim=2))      # depth-first: left | node | right
+        return torch.cat(rows, dim=1)
+
+    # ------------------------------------------------------------------ the steps: library on a device, mirror on the host
+    def _lib(self):
+        from . import runtime as rt
+        return rt, rt.load_library()
+
+    @staticmethod
+    def _stream(t):
+        import torch
+        return torch.cuda.current_stream(t.device).cuda_stream
+
+    def _subgoal_rows(self, views, goal):
+        import torch
+        lat = self._lat
+        if not lat.is_cuda:
+            return subgoal_rows_torch(lat, views, goal)
+        rt, lib = self._lib()
+        K, G = views.shape[:2]
+        opa, opb = torch.empty(2 * K * G, lat.shape[2], device=lat.device), torch.empty(2 * K * G, lat.shape[2], device=lat.device)
+        mids = torch.empty(K, G, dtype=torch.int32, device=lat.device)
+        rt.check(lib.gcpx_tree_subgoal_rows(lat.data_ptr(), views.data_ptr(), goal.data_ptr(), opa.data_ptr(), opb.data_ptr(), mids.data_ptr(),
+                                            K, G, lat.shape[0], lat.shape[1], lat.shape[2], self._stream(lat)), "tree_subgoal_rows")
+        return opa, opb, mids
+
+    def _select(self, c1, c2=None, mask=None, draw=None):
+        import torch
+        if not c1.is_cuda:
+            return select_torch(c1, c2, mask, draw)
+        rt, lib = self._lib()
+        K, G = c1.shape
+        idx, cost = torch.empty(K, dtype=torch.int32, device=c1.device), torch.empty(K, device=c1.device)
+        zf = 0 if draw is None else draw[0, 0].numel()
+        best = None if draw is None else torch.empty((K,) + tuple(draw.shape[2:]), device=c1.device)
+        rt.check(lib.gcpx_tree_select(c1.data_ptr(), rt.ptr(c2), rt.ptr(mask), rt.ptr(draw), rt.ptr(best), idx.data_ptr(), cost.data_ptr(),
+                                      K, G, zf, self._stream(c1)), "tree_select")
+        return idx, cost, best
+
+    def _split_views(self, views):
+        import torch
+        if not views.is_cuda:
+            return split_views_torch(views, self._dummy)
+        rt, lib = self._lib()
+        K, G = views.shape[:2]
+        left, right = torch.empty_like(views), torch.empty_like(views)
+        lgoal, short = torch.empty(K, 2, dtype=torch.int32, device=views.device), torch.empty(K, G, dtype=torch.int32, device=views.device)
+        rt.check(lib.gcpx_tree_split_views(views.data_ptr(), self._dummy, left.data_ptr(), right.data_ptr(), lgoal.data_ptr(), short.data_ptr(),
+                                           K, G, self._stream(views)), "tree_split_views")
+        return left, right, lgoal, short
+
+    def _segment_windows(self, views, goal, tmax):
+        import torch
+        lat = self._lat
+        if not lat.is_cuda:
+            return segment_windows_torch(lat, views, goal, tmax)
+        rt, lib = self._lib()
+        K, G = views.shape[:2]
+        seg = torch.empty(K * G, tmax, lat.shape[2], device=lat.device)
+        lens, rows = torch.empty(K * G, dtype=torch.int32, device=lat.device), torch.empty(K * G, lat.shape[2], device=lat.device)
+        rt.check(lib.gcpx_tree_segment_windows(lat.data_ptr(), views.data_ptr(), goal.data_ptr(), seg.data_ptr(), lens.data_ptr(), rows.data_ptr(),
+                                               K, G, lat.shape[0], lat.shape[1], tmax, lat.shape[2], self._stream(lat)), "tree_segment_windows")
+        return seg, lens, rows
+
+    def _short_alternative(self, lc, rc, sc, sidx):
+        import torch
+        if not lc.is_cuda:
+            return short_alternative_torch(lc, rc, sc, sidx)
+        rt, lib = self._lib()
+        cost, use = torch.empty_like(lc), torch.empty_like(sidx)
+        rt.check(lib.gcpx_tree_short_alternative(lc.data_ptr(), rc.data_ptr(), sc.data_ptr(), sidx.data_ptr(), cost.data_ptr(), use.data_ptr(),
+                                                 lc.shape[0], self._stream(lc)), "tree_short_alternative")
+        return cost, use
+
+    # ------------------------------------------------------------------ optimisation
+    def optimize(self, rollout):
+        """rollout: Outputs(latents [K n, T, nz], lengths int32 [K n]) on the generator's device, the rows of task k at k n .. k n + n - 1.
+        Optimises one level of every task; returns the K costs [K] float32 (a device tensor, also appended to `costs`)."""
+        import torch
+        lat = rollout.latents
+        K = self.n_tasks
+        assert lat.shape[0] % K == 0, "every task rolls out the same number of candidates"
+        # the last row holds the reference's stand-in for a rollout too short to split, [inf, 0, inf] (tree_optimizer.py:142-147)
+        dummy = torch.zeros(1, lat.shape[1], lat.shape[2], device=lat.device)
+        dummy[0, 0] = float("inf")
+        if lat.shape[1] > 2:
+            dummy[0, 2] = float("inf")
+        self._lat = torch.cat([lat, dummy]).contiguous()
+        self._dummy = lat.shape[0]
+        lens = torch.as_tensor(rollout.lengths, device=lat.device).to(torch.int32)
+        rows = torch.arange(lat.shape[0], dtype=torch.int32, device=lat.device)
+        views = torch.stack([rows, torch.zeros_like(rows), lens], -1).reshape(K, -1, 3).contiguous()
+        raw = torch.full((K, 2), -1, dtype=torch.int32, device=lat.device)
+        cost, rec = self._bopt(self._root, views, raw, True, lat.shape[1])
+        self.costs.append(cost)
+        self._records.append((rec, self._dummy))
+        self._tables = None
+        return cost
+
+    def _segment_costs(self, views, goal, tmax):
+        seg, lens, rows = self._segment_windows(views, goal, tmax)
+        return self._seq_cost.sequence_cost_device(seg, lens, rows).reshape(views.shape[0], views.shape[1])
+
+    def _bopt(self, lv, views, goal, raw, tmax):
+        if lv.left is None:
+            idx, cost, lv.best_z = self._select(self._segment_costs(views, goal, tmax), draw=lv.last_draw)
+            lv.done = True
+            return cost, dict(kind="segment", views=views, idx=idx)
+        if not lv.done:
+            return self._bopt_subgoal(lv, views, goal, raw)
+        return self._bopt_children(lv, views, goal, raw, tmax)
+
+    def _bopt_subgoal(self, lv, views, goal, raw):
+        K, G = views.shape[:2]
+        opa, opb, mids = self._subgoal_rows(views, goal)
+        c = self._pair_cost.pair_cost(opa, opb).reshape(2, K, G)          # both pair costs of all candidates of all tasks: ONE Predictor launch
+        idx, cost, lv.best_z = self._select(c[0], c[1], draw=lv.last_draw)
+        lv.left, lv.right = lv.left[:1], lv.right[:1]                     # keep only the winning branch
+        lv.n_samples, lv.done = 1, True
+        return cost, dict(kind="subgoal", views=views, idx=idx, mids=mids, raw=raw)
+
+    def _bopt_children(self, lv, views, goal, raw, tmax):
+        assert lv.n_samples == 1                                          # an optimised level keeps one branch: the population is one group
+        left, right, lgoal, short = self._split_views(views)
+        half = max((tmax + 1) // 2, 2)                                    # a half is at most ceil(tmax / 2) frames; the stand-in's are 1 and 2
+        lc, lrec = self._bopt(lv.left[0], left, lgoal, False, half)
+        rc, rrec = self._bopt(lv.right[0], right, goal, raw, half)
+        # the short candidates (fewer than 3 frames) scored as dense segments; the window is 2 frames, whatever the others hold is masked
+        sidx, sc, _ = self._select(self._segment_costs(views, goal, 2), mask=short)
+        cost, use = self._short_alternative(lc, rc, sc, sidx)
+        return cost, dict(kind="children", views=views, sidx=sidx, use=use, left=lrec, right=rrec)
+
+    # ------------------------------------------------------------------ results
+    _TABLES = ("views", "idx", "mids", "sidx", "use")
+
+    def _walk(self, rec):
+        yield rec
+        if rec["kind"] == "children":
+            yield from self._walk(rec["left"])
+            yield from self._walk(rec["right"])
+
+    def _read_tables(self):
+        """every selection and view table of every iteration so far in ONE copy to the host"""
+        import torch
+        if self._tables is None:
+            ts = [(id(r), name, r[name]) for rec, _ in self._records for r in self._walk(rec) for name in self._TABLES if name in r]
+            flat = torch.cat([t.reshape(-1).to(torch.int32) for _, _, t in ts]).cpu().numpy()
+            self._tables, o = {}, 0
+            for key, name, t in ts:
+                self._tables[(key, name)] = flat[o:o + t.numel()].reshape(tuple(t.shape))
+                o += t.numel()
+        return self._tables
+
+    def plans(self, iteration=-1):
+        """the K plans of one iteration as lists of (row, frame) references, rows counted within the task (0 .. n - 1, n = the stand-in
+        row; (-1, -1) = the raw goal image), rebuilt on the host from the selection tables"""
+        tab = self._read_tables()
+        rec, dummy = self._records[iteration]
+        n = dummy // self.n_tasks
+
+        def local(k, row):
+            return n if row >= dummy else row - k * n
+
+        def build(r, k):
+            t = lambda name: tab[(id(r), name)]
+            if r["kind"] == "children" and not t("use")[k]:
+                return build(r["left"], k) + build(r["right"], k)
+            if r["kind"] == "subgoal":
+                j = t("idx")[k]
+                i, a, b = (int(x) for x in t("views")[k, j])
+                m = int(t("mids")[k, j])
+                return [(local(k, i), a)] + ([(local(k, i), a + m)] if m != 0 else []) + ([(-1, -1)] if r["raw"] else [])
+            j = t("sidx" if r["kind"] == "children" else "idx")[k]
+            i, a, b = (int(x) for x in t("views")[k, j])
+            return [(local(k, i), f) for f in range(a, b)]
+
+        return [build(rec, k) for k in range(self.n_tasks)]
+
+    def tables(self):
+        """the selection tables (numpy) of every decision of every iteration, in walk order: [(kind, {name: array})]"""
+        tab = self._read_tables()
+        return [[(r["kind"], {name: tab[(id(r), name)] for name in self._TABLES if name in r}) for r in self._walk(rec)] for rec, _ in self._records]
+
+    @property
+    def fully_optimized(self):
+        def full(lv):
+            if lv.left is None:
+                return lv.done
+            return lv.done and all(full(c) for c in lv.left) and all(full(c) for c in lv.right)
+        return full(self._root)
