@@ -1330,6 +1330,36 @@ int gcpx_tree_segment_windows(const float* lat, const int32_t* views, const int3
 int gcpx_tree_short_alternative(const float* lc, const float* rc, const float* sc, const int32_t* sidx, float* cost, int32_t* use_short,
                                 int32_t K, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The flat CEM loop for K planning tasks at once (video-gcp_amd/planning.py: CEMPlanner.plan_batch; csrc/cem_batch.hip): the
+ * per-iteration arithmetic of CEMPlanner.__call__ / _get_best_rollouts (gcp/planning/cem/cem_planner.py:55-135) and of
+ * FlatCEMSampler.sample / fit (gcp/planning/cem/sampler.py:33-48), each one launch over all tasks.  K Gaussians mean, std [K][D] over
+ * samples of D = n_steps * action_dim floats (no alignment asked of D), n candidates per task, float32 throughout.  Every float operation
+ * below is rounded on its own (nothing is contracted to an FMA), in the order written, so the torch mirrors in planning.py
+ * (cem_population_torch, cem_elites_torch, cem_refit_torch) give the same bits.  Every launch is on `stream`; nothing is allocated or
+ * read back.
+ *
+ * gcpx_cem_population (sampler.py:40-42: np.random.normal(loc=mean, scale=std) = mean + std * eps, then np.clip):
+ *   out[k][j][d] = clamp(mean[k][d] + std[k][d] * eps[k][j][d], -clip, clip), eps standard-normal numbers; a non-finite clip: no clamp.
+ *   A NaN stays a NaN.  One pass over the population; out may be eps (in place).
+ * gcpx_cem_elites (cem_planner.py:129-130: np.argsort(scores)[:n_elite], stable): per task the first n_elite entries of the stable
+ *   ascending order of scores [K][n] -> idx int32 [K][n_elite], elite_scores [K][n_elite] = the scores at idx.  Ties go to the lower
+ *   index, -0.0 == +0.0, -inf and +inf are ordered, every NaN comes after every number and NaNs among themselves by index.  One workgroup
+ *   per task, the task's scores staged in LDS, each score ranked by counting: n <= GCPX_CEM_MAX_N.
+ * gcpx_cem_refit (sampler.py:44-46: np.mean / np.std(axis=0) of the elites; cem_planner.py:81: best_samples[:1]): with e_j = idx[k][j],
+ *   x_j = samples[k][e_j][d]:  mean[k][d] = (((x_0 + x_1) + x_2) + ...) / n_elite;  std[k][d] = sqrt(((q_0 + q_1) + ...) / n_elite),
+ *   q_j = (x_j - mean) * (x_j - mean) (the population std, two passes);  best[k][d] = x_0.  One thread per (task, column).  Every idx is
+ *   range-checked before it is used: a task with an index outside [0, n) gets NaN in all three outputs, no load is made through it.
+ *
+ * GCPX_ERR_INVALID_ARG, nothing launched: a null pointer, a size <= 0, n_elite > n, n > GCPX_CEM_MAX_N (elites, refit), or more
+ *   than 2^30 workgroups (K n ceil(D / 1024) for the population, K ceil(D / 256) for the refit). */
+#define GCPX_CEM_MAX_N 8192     /* candidates per task: 32 KB of LDS keys in gcpx_cem_elites */
+int gcpx_cem_population(const float* mean, const float* std, const float* eps, float clip, float* out, int32_t K, int32_t n, int32_t D,
+                        void* stream);
+int gcpx_cem_elites(const float* scores, int32_t* idx, float* elite_scores, int32_t K, int32_t n, int32_t n_elite, void* stream);
+int gcpx_cem_refit(const float* samples, const int32_t* idx, float* mean, float* std, float* best, int32_t K, int32_t n, int32_t n_elite,
+                   int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

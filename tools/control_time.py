@@ -9,7 +9,7 @@ that `steps_per_s` (everything) and `exec_steps_per_s` (planner time taken out) 
 Also measured once: the largest difference between the encoder + inverse model on a frame alone and on the same frame in a batch of 3
 (`row_alone_vs_batch3_max_abs`), the figure behind the runner's one-frame-per-call encoding.
 --batch_plans: instead of the serial loop, the batched loop twice over the same tasks, --repeats times each: plans per episode (the
-planner call of the loop above) and plans per step (ControlRunner(batch_plans=True): HierarchicalCEMPlanner.plan_batch); planner
+planner call of the loop above) and plans per step (ControlRunner(batch_plans=True): the planner's plan_batch); planner
 seconds, calls, tasks per call and the t = 0 call (all --E tasks) apart, each as the list of the repeats.  --max_rows: the rows per
 forward of plan_batch (one value: used by the loop; several: the t = 0 call alone is timed with each first).
 Prints one JSON line per shape; --out appends them to a file under profiles/.
@@ -25,15 +25,15 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# the settings of experiments/control/{9room,25room}/gcp_tree/mod_hyper.py
+# the settings of experiments/control/{9room,25room}/{gcp_tree,gcp_sequential}/mod_hyper.py (--planner tree / flat)
 CONF = textwrap.dedent('''
     from blox import AttrDict
     from gcp.planning.infra.agent.benchmarking_agent import BenchmarkAgent
     from gcp.planning.infra.envs.miniworld_env.multiroom3d.multiroom3d_env import TopdownMultiroom3dEnv
     from gcp.planning.planner_policy import ImageCEMPolicy
-    from gcp.planning.cem.sampler import ImageHierarchicalTreeCEMSampler
+    from gcp.planning.cem.sampler import {sampler}
     from gcp.planning.cem.cem_planner import HierarchicalImageCEMPlanner
-    from gcp.planning.cem.cost_fcn import ImageLearnedCostEstimate
+    from gcp.planning.cem.cost_fcn import {cost}
     from experiments.prediction.base_configs import gcp_tree as base_conf
 
     agent = AttrDict(type=BenchmarkAgent, env=(TopdownMultiroom3dEnv, dict(init_pos=None, goal_pos=None, n_rooms={n_rooms},
@@ -44,13 +44,17 @@ CONF = textwrap.dedent('''
                          inv_mdl_params=AttrDict(n_actions=2, use_convs=False, build_encoder=False),
                          decoder_distribution='discrete_logistic_mixture'))
     h_config.pop("add_weighted_pixel_copy")
-    cem_params = AttrDict(prune_final=True, horizon={seq}, action_dim=256, verbose=False, n_iters=3, batch_size=10,
-                          n_level_hierarchy={levels}, sampler=ImageHierarchicalTreeCEMSampler, sampling_rates_per_layer=[10, 10],
-                          cost_fcn=ImageLearnedCostEstimate, cost_config=AttrDict(checkpt_path='none'))
+    cem_params = AttrDict(prune_final=True, horizon={seq}, action_dim=256, verbose=False, {cem_extra},
+                          n_level_hierarchy={levels}, sampler={sampler},
+                          cost_fcn={cost}, cost_config=AttrDict(checkpt_path='none'))
     policy = AttrDict(type=ImageCEMPolicy, params=h_config, checkpt_path='none', cem_planner=HierarchicalImageCEMPlanner,
                       cem_params=cem_params, replan_interval=agent.T + 2, closed_loop_execution=True)
     config = AttrDict(start_index=0, end_index=99, agent=agent, policy=policy)
 ''')
+# cem_params of .../gcp_tree/mod_hyper.py (the hierarchical planner) and of .../gcp_sequential/mod_hyper.py (the flat planner, same model)
+PLANNERS = {"tree": dict(sampler="ImageHierarchicalTreeCEMSampler", cost="ImageLearnedCostEstimate",
+                         cem_extra="n_iters=3, batch_size=10, sampling_rates_per_layer=[10, 10]"),
+            "flat": dict(sampler="SimpleTreeCEMSampler", cost="ImageWrappedLearnedCostFcn", cem_extra="n_iters=1, batch_size=5, elite_frac=1.0")}
 SHAPES = {9: dict(n_rooms=9, T=200, seq=100, levels=7), 25: dict(n_rooms=25, T=400, seq=200, levels=8)}
 
 
@@ -87,7 +91,7 @@ class TimedPlanner:
 def time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T):
     """the batched loop with plans per episode and with plans per step, --repeats runs each, on the same tasks"""
     import numpy as np
-    row = {"workload": "control_time", "batch_plans": True, "n_rooms": n_rooms, "E": a.E, "T": T, "max_seq_len": desc.hp.max_seq_len,
+    row = {"workload": "control_time", "batch_plans": True, "planner": a.planner, "n_rooms": n_rooms, "E": a.E, "T": T, "max_seq_len": desc.hp.max_seq_len,
            "repeats": a.repeats}
     sweep = a.max_rows or [planner.MAX_ROWS]
     if len(sweep) > 1:                                   # the t = 0 call alone, per rows-per-forward (second of two calls: the first warms up)
@@ -140,6 +144,8 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="steps per episode (default: the conf's agent.T, 200 / 400)")
     ap.add_argument("--rooms", type=int, nargs="+", default=[9, 25])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--planner", choices=sorted(PLANNERS), default="tree", help="the conf's planner: tree = gcp_tree (hierarchical), "
+                    "flat = gcp_sequential (CEMPlanner over all tree latents)")
     ap.add_argument("--batch_plans", action="store_true", help="time planning per step (plan_batch) beside planning per episode")
     ap.add_argument("--repeats", type=int, default=3, help="--batch_plans: runs of each loop")
     ap.add_argument("--max_rows", type=int, nargs="+", default=None, help="--batch_plans: candidate rows per forward of plan_batch")
@@ -159,7 +165,7 @@ def main():
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "mod_hyper.py")
             with open(path, "w") as f:
-                f.write(CONF.format(**SHAPES[n_rooms]))
+                f.write(CONF.format(**SHAPES[n_rooms], **PLANNERS[a.planner]))
             conf = CL.exec_control_conf(path, {})
         desc, env_desc = CL.planner_from_control_conf(conf), CL.environment_from_control_conf(conf)
         model, planner, _ = CL.build_policy(desc, dev, seed=0, random_weights=True, verbose=False)
@@ -224,7 +230,7 @@ def main():
                       "batched_exec_steps_per_s": round(a.E * T / max(wall_b - plan_b, 1e-9), 1),
                       "serial_episodes": n_serial, "serial_wall_s": round(wall_s, 3), "serial_planner_s": round(plan_s, 3),
                       "serial_plans": calls_s, "serial_steps_per_s": round(n_serial * T / wall_s, 1),
-                      "serial_exec_steps_per_s": round(n_serial * T / max(wall_s - plan_s, 1e-9), 1),
+                      "serial_exec_steps_per_s": round(n_serial * T / max(wall_s - plan_s, 1e-9), 1), "planner": a.planner,
                       "blocked_fraction": round(float(res["blocked"].mean()), 4),
                       "row_alone_vs_batch3_max_abs": row_diff, "encoder_alone_vs_batch3_max_abs": enc_diff})
         print(json.dumps(lines[-1]), flush=True)

@@ -8,7 +8,7 @@ executed steps of all E tasks advance together on the device (nav_env.NavEnvBatc
   planning    per episode through the planner object, at t = 0 and whenever ImageCEMPolicy.act's condition holds for that episode; a plan's
               length is known on the host when it is made, so the execution counters are host integers.  A re-plan reads that episode's
               current frame back: the only read-back of the loop.  With batch_plans (--batch_plans 1) the episodes that plan at a step
-              plan together: one read-back of their frames, one HierarchicalCEMPlanner.plan_batch call.
+              plan together: one read-back of their frames, one planner.plan_batch call (HierarchicalCEMPlanner or the flat CEMPlanner).
   plans       padded device tensors: latents [E, Lmax, nz], actions [E, Lmax, 2]
   a step      gather the next planned latent (closed loop) or the planned action (open loop) of every row; the encoder on the current
               frames; inv_mdl.run_single on all rows; env.step; env.observe
@@ -27,7 +27,8 @@ import torch
 
 class ControlRunner:
     """ControlRunner(model, planner, env, replan_interval, num_max_replans, closed_loop_execution).run(tasks) -> results (numpy)
-    batch_plans: the episodes that plan at a step plan together, one `planner.plan_batch` call (HierarchicalCEMPlanner) and one read-back
+    batch_plans: the episodes that plan at a step plan together, one `planner.plan_batch` call (any planner that has one:
+    HierarchicalCEMPlanner, CEMPlanner) and one read-back
     of their frames per step; off (the default), every episode plans through its own planner call."""
 
     def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_plans=False):
@@ -151,8 +152,8 @@ def get_args(argv=None):
     p.add_argument("--out", required=True, help="directory for control_results.npz")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reference_rng", action="store_true", help="the hierarchical planner replays the reference's np.random sequence")
-    p.add_argument("--batch_plans", type=int, default=0, help="1 = the episodes that plan at a step plan together (the hierarchical planner's "
-                   "plan_batch): not the per-episode planner's bits, see DESIGN.md 5.7; not with --reference_rng")
+    p.add_argument("--batch_plans", type=int, default=0, help="1 = the episodes that plan at a step plan together (the planner's plan_batch, "
+                   "hierarchical or flat): not the per-episode planner's bits, see DESIGN.md 5.7; not with --reference_rng")
     return p.parse_args(argv)
 
 
@@ -199,7 +200,7 @@ def main(argv=None):
         raise ValueError("no task selected (start_index .. end_index of the conf, --n_tasks)")
     env = NE.NavEnvBatch(env_desc.n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev, assets=assets)
     if args.batch_plans and not hasattr(planner, "plan_batch"):
-        raise ValueError(f"--batch_plans 1 needs the hierarchical planner; the conf builds {type(planner).__name__}")
+        raise ValueError(f"--batch_plans 1 needs a planner with plan_batch; the conf builds {type(planner).__name__}, which has none")
     runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), **desc.policy_args)
     parts = []
     for s in range(0, len(idx), max(args.batch, 1)):

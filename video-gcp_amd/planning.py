@@ -39,6 +39,13 @@ def env2planner(img):
     return img * 2 - 1.0
 
 
+class PlannerFrames:
+    """start or goal frames that are already in the planner's format (`env2planner`: NCHW in [-1, 1]) on the model's device, one per row"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+
 class GCPImageSimulator:
     """Simulator interface of the planner: candidate latents -> model rollouts."""
 
@@ -52,9 +59,19 @@ class GCPImageSimulator:
     def _bcast(self, img, n):
         """the (single) start / goal image is converted once and broadcast on the device (cem_simulator.py:18 repeats it on the host:
         512 x 64 x 64 x 3 numpy copies + two 25 MB pageable uploads were 42 ms of a 60 ms scoring rollout)"""
-        t = env2planner(np.asarray(img) if not torch.is_tensor(img) else img).to(self._model.device)
+        if isinstance(img, PlannerFrames):
+            t = img.frames
+        else:
+            t = env2planner(np.asarray(img) if not torch.is_tensor(img) else img).to(self._model.device)
         assert t.shape[0] in (1, n), "one image for all candidates, or one per candidate"
         return t.expand(n, *t.shape[1:]) if t.shape[0] == 1 else t
+
+    def task_frames(self, images, n):
+        """env images [k, H, W, 3] of k planning tasks -> the frames of k * n candidate rows, task by task, as `rollout_device` takes them:
+        every image is converted once, on the host as `_bcast` converts it, and repeated on the device (the same values as converting the
+        repeated images, without k n host copies and their upload)"""
+        t = env2planner(np.asarray(images) if not torch.is_tensor(images) else images).to(self._model.device)
+        return PlannerFrames(t.repeat_interleave(n, dim=0) if n > 1 else t)
 
     def rollout_device(self, state, goal_state, samples, rollout_len, decode=True, len_u=None):
         """Device-resident rollout.  state/goal_state: env images [1,H,W,3]; samples [n, N, nz_vae] (depth-first node
@@ -226,6 +243,27 @@ class CostFcn:
         x = x.contiguous()
         rt_.check(rt_.load_library().gcpx_rollout_cost(x.data_ptr(), ld, lengths.data_ptr(), g.data_ptr(), 0, out.data_ptr(), n, T, D, self.KIND,
                                                        int(bool(self._dense_cost)), float(self._final_step_weight),
+                                                       torch.cuda.current_stream(x.device).cuda_stream), "rollout_cost")
+        return out
+
+    def rollout_cost_rows_device(self, x, lengths, goals, repeat=1):
+        """`rollout_cost_device` with a goal of its own per row (the rows of several planning tasks in one rollout): goals holds one goal,
+        each what the host contract takes, per `repeat` consecutive rows of x [n, T, ld] -> costs [n].  One launch; a candidate's
+        cost is computed by its own workgroup from its own rows and goal (csrc/misc.hip: rollout_cost_kernel), so it is the number
+        `rollout_cost_device` gives that row among any other rows."""
+        from . import runtime as rt_
+        n, T, ld = x.shape
+        D = self._device_columns(ld)
+        if len(goals) * repeat != n:
+            raise ValueError(f"{len(goals)} goals x {repeat} rows for {n} rollouts")
+        g = torch.stack([self._device_goal(goal, D, x.device) for goal in goals])
+        if repeat > 1:
+            g = g.repeat_interleave(repeat, dim=0)
+        g = g.contiguous()
+        out = torch.empty(n, device=x.device)
+        x = x.contiguous()
+        rt_.check(rt_.load_library().gcpx_rollout_cost(x.data_ptr(), ld, lengths.data_ptr(), g.data_ptr(), g.shape[1], out.data_ptr(), n, T, D,
+                                                       self.KIND, int(bool(self._dense_cost)), float(self._final_step_weight),
                                                        torch.cuda.current_stream(x.device).cuda_stream), "rollout_cost")
         return out
 
@@ -411,6 +449,121 @@ def select_elites(scores, n_elite):
     return torch.argsort(scores, stable=True)[:n_elite]
 
 
+# ---- the flat CEM loop for K tasks at once: csrc/cem_batch.hip and its torch mirrors -----------------------------------------------------
+# Each mirror is the kernel's checker (tests/test_gpu_cem_batch.py: equal bit for bit) and what runs when the tensors are on the CPU
+# (tests/test_cem_batch_cpu.py); tensors on a device always go through the library.
+def cem_population_torch(mean, std, eps, clip):
+    """gcpx_cem_population: mean, std [K, ...], eps [K, n, ...] -> clamp(mean + std * eps, -clip, clip) [K, n, ...]; block k is
+    FlatCEMSampler.from_unit_noise(eps[k]) of a sampler holding task k's mean and std"""
+    raw = mean[:, None] + std[:, None] * eps
+    return raw.clamp(-clip, clip) if np.isfinite(clip) else raw
+
+
+def cem_elites_torch(scores, n_elite):
+    """gcpx_cem_elites: scores [K, n] -> idx int32 [K, n_elite], elite_scores [K, n_elite]: `select_elites` per task"""
+    idx = torch.argsort(scores, dim=1, stable=True)[:, :n_elite]
+    return idx.to(torch.int32), torch.gather(scores, 1, idx)
+
+
+def cem_refit_torch(samples, idx):
+    """gcpx_cem_refit: samples [K, n, ...], idx int32 [K, n_elite] -> mean, std, best [K, ...].  The elites are accumulated one at a
+    time in their order, each operation a float32 tensor operation of its own: the kernel's sequence of IEEE operations.  A task with an
+    index outside [0, n) gets NaN."""
+    K, n = samples.shape[:2]
+    n_elite = idx.shape[1]
+    i = idx.long()
+    bad = ((i < 0) | (i >= n)).any(dim=1)
+    i = i.clamp(0, n - 1)
+    ar = torch.arange(K, device=samples.device)
+    x = [samples[ar, i[:, j]] for j in range(n_elite)]
+    acc = x[0]
+    for j in range(1, n_elite):
+        acc = acc + x[j]
+    mean = acc / n_elite
+    d = x[0] - mean
+    sq = d * d
+    for j in range(1, n_elite):
+        d = x[j] - mean
+        sq = sq + d * d
+    # the correctly rounded float32 root, as the kernel's sqrtf: through float64 (53 >= 2 * 24 + 2 bits: rounding twice is rounding
+    # once), because torch's vectorised float32 sqrt on the CPU is not correctly rounded everywhere (0.7 % of its results are 1 ulp off)
+    std = torch.sqrt((sq / n_elite).double()).float()
+    best = x[0].clone()
+    if bool(bad.any()):
+        mean[bad] = std[bad] = best[bad] = float("nan")
+    return mean, std, best
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def cem_population(mean, std, eps, clip, inplace=False):
+    """the K populations [K, n, ...] that the noise blocks eps stand for; inplace: written over eps"""
+    if not eps.is_cuda:
+        return cem_population_torch(mean, std, eps, clip)
+    K, n = eps.shape[:2]
+    mean, std, eps = mean.contiguous(), std.contiguous(), eps.contiguous()
+    out = eps if inplace else torch.empty_like(eps)
+    rt.check(rt.load_library().gcpx_cem_population(mean.data_ptr(), std.data_ptr(), eps.data_ptr(), float(clip), out.data_ptr(), K, n,
+                                                   mean[0].numel(), _stream(eps)), "cem_population")
+    return out
+
+
+def cem_elites(scores, n_elite):
+    if not scores.is_cuda:
+        return cem_elites_torch(scores, n_elite)
+    K, n = scores.shape
+    scores = scores.contiguous()
+    idx, best = torch.empty(K, n_elite, dtype=torch.int32, device=scores.device), torch.empty(K, n_elite, device=scores.device)
+    rt.check(rt.load_library().gcpx_cem_elites(scores.data_ptr(), idx.data_ptr(), best.data_ptr(), K, n, n_elite, _stream(scores)), "cem_elites")
+    return idx, best
+
+
+def cem_refit(samples, idx):
+    if not samples.is_cuda:
+        return cem_refit_torch(samples, idx)
+    K, n = samples.shape[:2]
+    samples, idx = samples.contiguous(), idx.contiguous()
+    mean, std, best = (torch.empty((K,) + tuple(samples.shape[2:]), device=samples.device) for _ in range(3))
+    rt.check(rt.load_library().gcpx_cem_refit(samples.data_ptr(), idx.data_ptr(), mean.data_ptr(), std.data_ptr(), best.data_ptr(), K, n,
+                                              idx.shape[1], mean[0].numel(), _stream(samples)), "cem_refit")
+    return mean, std, best
+
+
+def rollout_chunks(sim, max_seq_len, states, goals, z, n, max_rows, decode, len_u, each=None, decode_device=False):
+    """The rollout of K * n rows, task k's n rows with its own start and goal image, whole tasks per forward of at most `max_rows` rows.
+    decode: sim.rollout (host lists), one Outputs per forward.  Otherwise sim.rollout_device: without `each` latents only, and the
+    (latents, lengths) of all rows come back as one pair; with `each`, each(r, goals of the forward's tasks) is called on every
+    forward's device rollout r before the next forward reuses its buffers (decode_device: with the images), and the list of what it
+    returned comes back.  len_u: f(rows) -> the length draws of a forward of that many rows, or None."""
+    K = states.shape[0]
+    per = max(int(max_rows) // n, 1)
+    parts = []
+    for lo in range(0, K, per):
+        hi = min(lo + per, K)
+        rows = slice(lo * n, hi * n)
+        kw = {} if len_u is None else dict(len_u=len_u((hi - lo) * n))
+        if hasattr(sim, "task_frames"):                  # each task's images converted once, repeated on the device
+            s, g = sim.task_frames(states[lo:hi], n), sim.task_frames(goals[lo:hi], n)
+        else:
+            s, g = np.repeat(states[lo:hi], n, axis=0), np.repeat(goals[lo:hi], n, axis=0)
+        if decode:
+            parts.append(sim.rollout(s, g, z[rows], max_seq_len, **kw))
+            continue
+        if each is not None:
+            if getattr(sim, "supports_latent_only", False):
+                kw["decode"] = decode_device
+            parts.append(each(sim.rollout_device(s, g, z[rows], max_seq_len, **kw), goals[lo:hi]))
+            continue
+        r = sim.rollout_device(s, g, z[rows], max_seq_len, decode=False, **kw)
+        # (the forward's buffers are reused by the next rollout of the same size)
+        parts.append((r.latents.clone(), r.lengths.clone()) if K > per else (r.latents, r.lengths))
+    if decode or each is not None or len(parts) == 1:
+        return parts
+    return [(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))]
+
+
 def elite_log_entry(goal_state, scores, images=None, latents=None, goal_rows=None, states=None):
     """One iteration of a verbose planner log (cem_planner.py:72-78: elite_rollouts, elite_scores, goal_state, elite_states).
     images: per elite [len, 3, H, W] in [-1, 1] (device tensors or numpy), or None when the elites were scored on latents only; then
@@ -552,6 +705,90 @@ class CEMPlanner:
         return Outputs(predictions=final.predictions[0], actions=actions, latents=final.latents[0], cost=float(best_scores[0]),
                        states=states[0] if states is not None else None)
 
+    # K tasks per forward: at most this many candidate rows in one scoring forward (HierarchicalCEMPlanner.MAX_ROWS)
+    MAX_ROWS = 1000
+
+    def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None):
+        """K tasks planned together: states, goals [K, H, W, 3] env images -> a list of K Outputs with the fields of `plan`.
+        The K Gaussians mean, std [K, n_steps, dim] live in this call, initialised as `sampler.init()` does; the sampler's own mean / std
+        are not touched.  Every iteration is one noise draw [K, n, n_steps, dim] from the sampler's rank-shared generator, one launch
+        for the K populations (gcpx_cem_population), the scoring rollout of the K * n rows -- task k's rows with its own start and goal
+        image, whole tasks per forward, at most `max_rows` rows (default MAX_ROWS), each forward scored before the next -- one launch
+        for the elites of all tasks (gcpx_cem_elites) and one for the refit (gcpx_cem_refit); nothing is read back inside the loop.
+        Then one decoded rollout of the K best candidates, and the K costs in one copy.
+
+        Not the bits of `plan` task by task: the generator is consumed in another order, a forward of K * n rows need not equal one
+        of n rows in the last bits (HierarchicalCEMPlanner.plan_batch), and the refit sums the elites one at a time where `fit` calls
+        torch.mean / torch.std -- the same search on another sample.
+        Out of scope, ValueError: verbose logs (defined per plan); a population sharded over ranks or sampler shards; PDDMSampler,
+        whose correlated draw and score-weighted refit the kernels do not compute.
+        record: `self.batch_record` keeps, per iteration, the noise blocks, populations, per-row scores, elite indices, the means and
+        stds after the refit, the scoring rollouts' (latents, lengths) and goal latents, and `best_samples` [K, n_steps, dim].
+        len_u: f(rows) -> the length draws of a forward of that many rows; default, for a simulator that predicts lengths:
+        sampler.sample_uniform(rows) per forward.
+        self.logs: per iteration Outputs(elite_scores [K, n_elite], mean_score [K])."""
+        s = self._sampler
+        if self.verbose:
+            raise ValueError("plan_batch keeps no verbose logs (they are defined per plan): use plan()")
+        if isinstance(s, PDDMSampler):
+            raise ValueError("plan_batch does not implement PDDMSampler (correlated draws, score-weighted refit): use plan()")
+        if not isinstance(s, FlatCEMSampler):
+            raise ValueError(f"plan_batch needs a FlatCEMSampler, not {type(s).__name__}")
+        if s.n_shards() != 1:
+            raise ValueError(f"plan_batch does not shard its populations ({s.n_shards()} sampler shards / ranks): use plan()")
+        if s._dtype != torch.float32:
+            raise ValueError("plan_batch keeps its distributions in float32")
+        states, goals = np.asarray(states), np.asarray(goals)
+        if states.ndim != 4 or states.shape != goals.shape:
+            raise ValueError("plan_batch takes states and goals [K, H, W, 3]")
+        K, n = states.shape[0], self.batch_size
+        n_elite = max(int(n * self.elite_frac), 1)
+        max_rows = self.MAX_ROWS if max_rows is None else int(max_rows)
+        sim, dev = self._sim, s.device
+        if len_u is None and getattr(sim, "pred_length", False):
+            len_u = s.sample_uniform
+        elif not getattr(sim, "pred_length", False):
+            len_u = None
+        learned = hasattr(self._cost, "sequence_cost_device")
+        mean = torch.zeros(K, s._n_steps, s._action_dim, device=dev)
+        std = s._initial_std * torch.ones(K, s._n_steps, s._action_dim, device=dev)
+        rec = Outputs(noise=[], populations=[], scores=[], elite_idx=[], means=[], stds=[], rollouts=[], goal_latents=[], best_samples=None)
+        kept = []
+
+        def score(r, chunk_goals):
+            if record:
+                kept.append((r.latents.clone(), r.lengths.clone(), r.e_goal.clone()))
+            if learned:
+                return self._cost.sequence_cost_device(r.latents, r.lengths, r.e_goal if self.goal_in_cost else None)
+            return self._cost.rollout_cost_rows_device(sim.predictions_device(r), r.lengths, [g[None] for g in chunk_goals], repeat=n)
+
+        self.logs, best, elite_scores = [], None, None
+        for _ in range(self.n_iters):
+            eps = torch.randn(K, n, s._n_steps, s._action_dim, device=dev, generator=s._gen)
+            pop = cem_population(mean, std, eps, s._clip_val, inplace=not record)
+            parts = rollout_chunks(sim, self.max_seq_len, states, goals, pop.reshape((K * n,) + tuple(pop.shape[2:])), n, max_rows, False,
+                                   len_u, each=score, decode_device=self.decode_candidates)
+            scores = (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(K, n)
+            idx, elite_scores = cem_elites(scores, n_elite)
+            mean, std, best = cem_refit(pop, idx)
+            self.logs.append(Outputs(elite_scores=elite_scores, mean_score=scores.mean(dim=1)))
+            if record:
+                for key, v in (("noise", eps), ("populations", pop), ("scores", scores), ("elite_idx", idx), ("means", mean), ("stds", std),
+                               ("rollouts", (torch.cat([p[0] for p in kept]), torch.cat([p[1] for p in kept]))),
+                               ("goal_latents", torch.cat([p[2] for p in kept]))):
+                    rec[key].append(v)
+                kept.clear()
+        rec.best_samples = best
+        self.batch_record = rec if record else None
+        costs = elite_scores[:, 0].cpu().numpy()
+        out = []
+        for k0, final in zip(range(0, K, max(max_rows, 1)), rollout_chunks(sim, self.max_seq_len, states, goals, best, 1, max_rows, True, len_u)):
+            st = final.get("states")
+            for j in range(len(final.predictions)):
+                out.append(Outputs(predictions=final.predictions[j], actions=final.actions[j] if final.actions is not None else None,
+                                   latents=final.latents[j], cost=float(costs[k0 + j]), states=st[j] if st is not None else None))
+        return out
+
 
 class ImageHierarchicalTreeCEMSampler:
     """sampler.py:79-143: draws come from the hierarchical latent optimizer, one tree level is fixed per iteration."""
@@ -682,24 +919,8 @@ class HierarchicalCEMPlanner:
 
     def _rollout_chunks(self, states, goals, z, n, max_rows, decode, len_u):
         """sim.rollout_device (decode=False) / sim.rollout (decode=True) of K * n rows, task k's n rows with its own start and goal image,
-        whole tasks per forward"""
-        K = states.shape[0]
-        per = max(int(max_rows) // n, 1)
-        parts = []
-        for lo in range(0, K, per):
-            hi = min(lo + per, K)
-            rows = slice(lo * n, hi * n)
-            kw = {} if len_u is None else dict(len_u=len_u((hi - lo) * n))
-            s, g = np.repeat(states[lo:hi], n, axis=0), np.repeat(goals[lo:hi], n, axis=0)
-            if decode:
-                parts.append(self._sim.rollout(s, g, z[rows], self.max_seq_len, **kw))
-                continue
-            r = self._sim.rollout_device(s, g, z[rows], self.max_seq_len, decode=False, **kw)
-            # (the forward's buffers are reused by the next rollout of the same size)
-            parts.append((r.latents.clone(), r.lengths.clone()) if K > per else (r.latents, r.lengths))
-        if decode or len(parts) == 1:
-            return parts
-        return [(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))]
+        whole tasks per forward (`rollout_chunks`, shared with CEMPlanner.plan_batch)"""
+        return rollout_chunks(self._sim, self.max_seq_len, states, goals, z, n, max_rows, decode, len_u)
 
     def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None):
         """K tasks planned together: states, goals [K, H, W, 3] env images -> a list of K Outputs with the fields of `plan`.

@@ -287,6 +287,9 @@ SYMBOLS = [
     ("gcpx_tree_split_views", C.c_int, [vp, i32, vp, vp, vp, vp, i32, i32, vp]),
     ("gcpx_tree_segment_windows", C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     ("gcpx_tree_short_alternative", C.c_int, [vp, vp, vp, vp, vp, vp, i32, vp]),
+    ("gcpx_cem_population", C.c_int, [vp, vp, vp, C.c_float, vp, i32, i32, i32, vp]),
+    ("gcpx_cem_elites", C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
+    ("gcpx_cem_refit", C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
 ]
 
 _lib = None
