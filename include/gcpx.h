@@ -1360,6 +1360,27 @@ int gcpx_cem_elites(const float* scores, int32_t* idx, float* elite_scores, int3
 int gcpx_cem_refit(const float* samples, const int32_t* idx, float* mean, float* std, float* best, int32_t K, int32_t n, int32_t n_elite,
                    int32_t D, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * The inference-mode encoder of F frames in one launch, each frame on its own (csrc/enc_frames.hip): what the closed-loop policy
+ * computes one frame per call, gcp/planning/planner_policy.py:222-227 (`self.planner.encoder(img)[0][:, :, 0, 0]`), for the frames of
+ * all episodes at once (video-gcp_amd/model.py: GCPTreeModel.encode_frames; control.py --batch_encode 1).
+ *
+ * images [F][3][S][S] float32 NCHW in [-1, 1], 16-byte aligned; row f of the result, nz_enc floats, is written to
+ * out + f * out_stride (floats; out_stride >= nz_enc).  weights: the blob of packing.pack_encoder_frames (16-byte aligned):
+ *   input    w [48 (ci, ky, kx)][16], bias [16]                                         4x4, stride 2, pad 1, bias, LeakyReLU
+ *   pyramid  w [16 taps][Cin/16][Cout/16][64][4], bias, scale, shift [Cout]  each     conv + bias, fmaf(raw, scale, shift), LeakyReLU
+ *   head     w [nz_enc][16 c_top (y, x, c)], bias [nz_enc]                              4x4 valid + bias
+ * with scale / shift the BatchNorm's running statistics folded as gcpx_bn_fold folds them, leaky_slope the LeakyReLU's slope.
+ * Exact f32 (f32 operands and accumulation).  The summation order of every output value is a function of (layer, pixel, channel)
+ * alone: a frame's row has the same bits whatever F, the frame's index or the grid.  Out-of-image taps contribute zeros and are never
+ * formed into an address; nothing at or beyond frame F is read or written.  One launch on `stream`; every argument is passed by value
+ * or points into memory the caller keeps: no host synchronisation is needed afterwards.
+ *
+ * GCPX_ERR_INVALID_ARG, no HIP call made: a null pointer, F <= 0, S other than 32 or 64, ngf other than 16, nz_enc not a multiple of 16
+ *   or above 256, out_stride < nz_enc, a misaligned images / weights pointer.  There is no fallback to gcpx_conv4x4s2. */
+int gcpx_encode_frames(const float* images, const float* weights, float* out, int64_t out_stride, int32_t F, int32_t S, int32_t ngf,
+                       int32_t nz_enc, float leaky_slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

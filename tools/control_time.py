@@ -12,6 +12,9 @@ Also measured once: the largest difference between the encoder + inverse model o
 planner call of the loop above) and plans per step (ControlRunner(batch_plans=True): the planner's plan_batch); planner
 seconds, calls, tasks per call and the t = 0 call (all --E tasks) apart, each as the list of the repeats.  --max_rows: the rows per
 forward of plan_batch (one value: used by the loop; several: the t = 0 call alone is timed with each first).
+--batch_encode: instead of the serial loop, the batched loop with the closed-loop encoder one frame per call and with one
+encode_frames launch per step (ControlRunner(batch_encode=True), csrc/enc_frames.hip), taking turns over the same tasks, --repeats times
+each: wall and planner seconds, executed steps per second and microseconds per episode-step with the planner time taken out.
 Prints one JSON line per shape; --out appends them to a file under profiles/.
 """
 import argparse
@@ -137,6 +140,36 @@ def time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T)
     return row
 
 
+def time_batch_encode(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T):
+    """the batched loop with one encoder call per frame and with one encode_frames launch per step, taking turns, --repeats runs each, on
+    the same tasks; plans per step when --batch_plans is given too"""
+    row = {"workload": "control_time", "batch_encode": True, "batch_plans": bool(a.batch_plans), "planner": a.planner, "n_rooms": n_rooms,
+           "E": a.E, "T": T, "max_seq_len": desc.hp.max_seq_len, "repeats": a.repeats}
+    timed = TimedPlanner(planner, torch)
+    timed.max_rows = (a.max_rows or [planner.MAX_ROWS])[0] if a.batch_plans else None
+    runners = {flag: CT.ControlRunner(model, timed, env, batch_plans=bool(a.batch_plans), batch_encode=flag, **desc.policy_args)
+               for flag in (False, True)}
+    for flag in (False, True):
+        runners[flag].run({k: v[:2] for k, v in tasks.items()})     # warm-up: plans and buffers of both kinds of call
+    runs = {False: [], True: []}
+    for _ in range(a.repeats):
+        for flag in (False, True):
+            timed.seconds, timed.calls, timed.tasks_per_call, timed.first_call_s = 0.0, 0, [], None
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = runners[flag].run(tasks)
+            torch.cuda.synchronize()
+            runs[flag].append(dict(wall=time.perf_counter() - t0, planner=timed.seconds, plans=int(res["n_replans"].sum())))
+    r3 = lambda xs: [round(x, 4) for x in xs]
+    for flag, tag in ((False, "per_frame"), (True, "batch_encode")):
+        rs = runs[flag]
+        row.update({f"{tag}_wall_s": r3([r["wall"] for r in rs]), f"{tag}_planner_s": r3([r["planner"] for r in rs]),
+                    f"{tag}_plans": [r["plans"] for r in rs],
+                    f"{tag}_exec_steps_per_s": [round(a.E * T / max(r["wall"] - r["planner"], 1e-9), 1) for r in rs],
+                    f"{tag}_exec_us_per_episode_step": r3([1e6 * (r["wall"] - r["planner"]) / (a.E * T) for r in rs])})
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--E", type=int, default=100)
@@ -149,6 +182,9 @@ def main():
     ap.add_argument("--batch_plans", action="store_true", help="time planning per step (plan_batch) beside planning per episode")
     ap.add_argument("--repeats", type=int, default=3, help="--batch_plans: runs of each loop")
     ap.add_argument("--max_rows", type=int, nargs="+", default=None, help="--batch_plans: candidate rows per forward of plan_batch")
+    ap.add_argument("--batch_encode", action="store_true", help="time the batched loop with one encoder call per frame and with one "
+                    "encode_frames launch per step (ControlRunner(batch_encode=True)), taking turns, --repeats runs each; with "
+                    "--batch_plans both plan per step")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -180,6 +216,13 @@ def main():
         alone = torch.cat([model.inv_mdl.run_single(model.encode(obs[e:e + 1]), target[e:e + 1]) for e in range(3)])
         row_diff = float((together - alone).abs().max())
         enc_diff = float((model.encode(obs) - torch.cat([model.encode(obs[e:e + 1]) for e in range(3)])).abs().max())
+
+        if a.batch_encode:
+            lines.append(time_batch_encode(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T))
+            print(json.dumps(lines[-1]), flush=True)
+            del model, planner, env
+            torch.cuda.empty_cache()
+            continue
 
         if a.batch_plans:
             lines.append(time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T))

@@ -15,7 +15,11 @@ executed steps of all E tasks advance together on the device (nav_env.NavEnvBatc
   the encoder its split-f16 convolution blocks share one power-of-two scale among the frames a workgroup stages (csrc/conv_enc_split.hip),
               so a frame's latent depends on its batch-mates in the last bits: the closed-loop encoding runs one frame per call, which is
               the call ImageCEMPolicy._infer_action makes.  The inverse model's rows are independent (csrc/mlp.hip: a row is a column of the
-              MFMA tile) and run as one batch.
+              MFMA tile) and run as one batch.  With batch_encode (--batch_encode 1) the frames of all episodes go through ONE launch of
+              the frame-independent encoder (model.encode_frames, csrc/enc_frames.hip: exact f32, a frame's latent depends on that frame
+              and the weights only), the call ImageCEMPolicy(batch_encode=True)._infer_action makes for one frame.  Not the bits of the
+              default path (split-f16 with shared scales); both are within the oracle's latent tolerance.  It combines
+              with --batch_plans and --reference_rng and changes nothing without closed_loop_execution.
 The loop runs agent.T steps, as GeneralAgent.rollout does: no early stop."""
 import argparse
 import json
@@ -29,11 +33,19 @@ class ControlRunner:
     """ControlRunner(model, planner, env, replan_interval, num_max_replans, closed_loop_execution).run(tasks) -> results (numpy)
     batch_plans: the episodes that plan at a step plan together, one `planner.plan_batch` call (any planner that has one:
     HierarchicalCEMPlanner, CEMPlanner) and one read-back
-    of their frames per step; off (the default), every episode plans through its own planner call."""
+    of their frames per step; off (the default), every episode plans through its own planner call.
+    batch_encode: closed-loop acting encodes the current frames of all episodes in one `model.encode_frames` launch; off (the default),
+    one `model.encode` call per frame.  An error if the model's encoder shape is not one `encode_frames` takes."""
 
-    def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_plans=False):
+    def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_plans=False,
+                 batch_encode=False):
         self.model, self.planner, self.env = model, planner, env
-        self.batch_plans = bool(batch_plans)
+        self.batch_plans, self.batch_encode = bool(batch_plans), bool(batch_encode)
+        if self.batch_encode:
+            from .packing import encoder_frames_unsupported
+            why = encoder_frames_unsupported(model._hp)
+            if why:
+                raise ValueError(f"batch_encode needs an encoder shape model.encode_frames takes ({why})")
         self.replan_interval, self.num_max_replans = int(replan_interval), int(num_max_replans)
         self.closed_loop_execution = bool(closed_loop_execution)
         self.plans = []               # per episode: [(t, image_plan, action_plan, latent_plan, cost)] of every plan made (host copies)
@@ -79,6 +91,8 @@ class ControlRunner:
 
     # -- acting: ImageCEMPolicy.get_action for all rows --
     def _encode(self, obs):
+        if self.batch_encode:
+            return self.model.encode_frames(obs)
         return torch.cat([self.model.encode(obs[e:e + 1]) for e in range(obs.shape[0])], dim=0)
 
     def _actions(self, obs):
@@ -154,6 +168,9 @@ def get_args(argv=None):
     p.add_argument("--reference_rng", action="store_true", help="the hierarchical planner replays the reference's np.random sequence")
     p.add_argument("--batch_plans", type=int, default=0, help="1 = the episodes that plan at a step plan together (the planner's plan_batch, "
                    "hierarchical or flat): not the per-episode planner's bits, see DESIGN.md 5.7; not with --reference_rng")
+    p.add_argument("--batch_encode", type=int, default=0, help="1 = closed-loop acting encodes the frames of all episodes in one launch of the "
+                   "frame-independent encoder (model.encode_frames): not the default encoder's bits, see DESIGN.md 5.7; no effect without "
+                   "closed_loop_execution; an error if the model's encoder shape is unsupported")
     return p.parse_args(argv)
 
 
@@ -201,7 +218,7 @@ def main(argv=None):
     env = NE.NavEnvBatch(env_desc.n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev, assets=assets)
     if args.batch_plans and not hasattr(planner, "plan_batch"):
         raise ValueError(f"--batch_plans 1 needs a planner with plan_batch; the conf builds {type(planner).__name__}, which has none")
-    runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), **desc.policy_args)
+    runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), batch_encode=bool(args.batch_encode), **desc.policy_args)
     parts = []
     for s in range(0, len(idx), max(args.batch, 1)):
         parts.append(runner.run({k: v[s:s + max(args.batch, 1)] for k, v in tasks.items()}))

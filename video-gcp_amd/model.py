@@ -61,6 +61,7 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         self._merge_side_rows = 1 << 60       # rows from which a level's merge GEMM runs on a side lane / on the planes GEMM (weights._pack_gemm_split)
         self._planes_min_rows = 1 << 60
         self._arena = None                    # one arena for every packed weight (weights.build_arena: the trainer's re-pack)
+        self._enc_frames_pack = None          # the blob encode_frames reads (packing.pack_encoder_frames): built on first use, dropped at every re-pack
         self._plan_listeners = []             # called when the plans are dropped (the trainer's backward plans hang off them)
         self._rng_seed = None                 # torch CUDA seed the in-plan Philox stream was started from (replay._sync_rng_state)
         self._rng_stream_id = GCPTreeModel._n_models      # distinct noise streams for the models of one process
@@ -211,6 +212,7 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
                 self.sd[k].copy_(v)
             elif strict:
                 raise KeyError(k)
+        self._enc_frames_pack = None
         self._pack_all()
         self._clear_plans()
 
@@ -224,6 +226,7 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
             cb()
         self._plans.clear()
         self._last_plan = None
+        self._enc_frames_pack = None
 
     def __call__(self, inputs, phase="train", noise=None):
         return self.forward(inputs, phase, noise)
@@ -306,6 +309,39 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
             skips = {k: (t.clone(), C_, None if sc is None else sc.clone(), None if sh is None else sh.clone(), act)
                      for k, (t, C_, sc, sh, act) in skips.items()}
         return out, (Skips(skips, Fr) if keep_skips else None)
+
+    def encode_frames(self, images, out=None):
+        """The latents [F, nz_enc] of F NCHW frames in [-1, 1], every frame on its own (csrc/enc_frames.hip: gcpx_encode_frames): row f
+        depends on frame f and the weights only, so the frames of many episodes go through ONE launch and each gets the bits it would get
+        alone -- what `encode` cannot promise, whose split-f16 blocks share a scale among the frames of a workgroup.  Exact f32, within the
+        oracle's latent tolerance but not the bits of `encode`.  Inference only (running BatchNorm statistics): ValueError in training
+        mode, and for a shape the kernel does not take (packing.encoder_frames_unsupported).  One launch on the current stream: no plan,
+        no host synchronisation, and with `out` (float32 [F, nz_enc] on the device, unit column stride) no allocation."""
+        hp = self._hp
+        if self.training:
+            raise ValueError("encode_frames runs the inference-mode encoder (running BatchNorm statistics): batch statistics are not "
+                             "frame-independent; call model.eval() first")
+        why = pk.encoder_frames_unsupported(hp)
+        if why:
+            raise ValueError(f"encode_frames: unsupported encoder shape ({why})")
+        x = torch.as_tensor(images).to(device=self.device, dtype=torch.float32).contiguous()
+        if x.dim() != 4 or x.shape[0] < 1 or tuple(x.shape[1:]) != (hp.input_nc, hp.img_sz, hp.img_sz):
+            raise ValueError(f"encode_frames: images {tuple(x.shape)}, expected [F >= 1, {hp.input_nc}, {hp.img_sz}, {hp.img_sz}]")
+        Fr = x.shape[0]
+        if out is None:
+            out = torch.empty(Fr, hp.nz_enc, device=self.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (Fr, hp.nz_enc)
+                  and out.stride(1) == 1 and (Fr == 1 or out.stride(0) >= hp.nz_enc)):
+            raise ValueError(f"encode_frames: out must be a float32 device tensor [{Fr}, {hp.nz_enc}] with unit column stride")
+        if self._enc_frames_pack is None:
+            self._enc_frames_pack = pk.pack_encoder_frames(self.sd, hp)
+        stride = out.stride(0) if Fr > 1 else hp.nz_enc
+        st = self.lib.gcpx_encode_frames(x.data_ptr(), self._enc_frames_pack.data_ptr(), out.data_ptr(), stride, Fr, hp.img_sz, hp.ngf,
+                                         hp.nz_enc, hp.leaky_slope, torch.cuda.current_stream(self.device).cuda_stream)
+        if st == -1:
+            raise ValueError((self.lib.gcpx_last_error() or b"").decode())
+        rt.check(st, "encode_frames")
+        return out
 
     def _decode_seq(self, inputs, enc):
         """DecoderModule.decode_seq (tree_dense_rec.py:42): enc [B, N, nz_enc(,1,1)] -> Outputs(images [B, N, 3, H, W])"""

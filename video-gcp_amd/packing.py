@@ -453,3 +453,106 @@ def lstm_gate_interleave(w_ih, w_hh, b_ih, b_hh):
     w = w.view(4, H, K).permute(1, 0, 2).reshape(4 * H, K)
     b = (b_ih + b_hh).view(4, H).t().reshape(4 * H)
     return w.contiguous(), b.contiguous()
+
+
+# ---- the frame-independent encoder (csrc/enc_frames.hip: gcpx_encode_frames) ----
+def unpack_conv4x4(wpk, cin, cout):
+    """inverse of pack_conv4x4: [16 taps][Cin/16][CT][64][4] -> w [Cout, Cin, 4, 4]"""
+    dev = wpk.device
+    wpk = wpk.reshape(16, cin // 16, cout // 16, 64, 4)
+    w = torch.zeros((cout, cin, 16), dtype=wpk.dtype, device=dev)
+    tap = torch.arange(16, device=dev)[:, None, None, None, None]
+    cg = torch.arange(cin // 16, device=dev)[None, :, None, None, None]
+    ct = torch.arange(cout // 16, device=dev)[None, None, :, None, None]
+    li = _LI.to(dev)[None, None, None, :, None]
+    lq = _LQ.to(dev)[None, None, None, :, None]
+    s = torch.arange(4, device=dev)[None, None, None, None, :]
+    w[(ct * 16 + li).expand_as(wpk), (cg * 16 + lq * 4 + s).expand_as(wpk), tap.expand_as(wpk)] = wpk
+    return w.reshape(cout, cin, 4, 4)
+
+
+def encoder_frames_unsupported(hp):
+    """why gcpx_encode_frames does not take this model's encoder, or None: input_nc 3, img_sz 32 or 64, ngf 16, nz_enc % 16 == 0 <= 256"""
+    if hp.input_nc != 3:
+        return f"input_nc = {hp.input_nc}: 3 is built"
+    if hp.img_sz not in (32, 64):
+        return f"img_sz = {hp.img_sz}: 32 and 64 are built"
+    if hp.ngf != 16:
+        return f"ngf = {hp.ngf}: 16 is built"
+    if hp.nz_enc <= 0 or hp.nz_enc % 16 or hp.nz_enc > 256:
+        return f"nz_enc = {hp.nz_enc}: a multiple of 16, at most 256"
+    return None
+
+
+def encoder_frames_layout(hp):
+    """{part: (float offset, shape)} of the blob, in its order (csrc/enc_frames.hip computes the same offsets):
+    input.w [48 (ci, ky, kx)][16], input.b; per pyramid layer <name>.w [16 taps][Cin/16][Cout/16][64][4] (pack_conv4x4), .b, .scale, .shift
+    [Cout]; head.w [nz_enc][16 c_top (y, x, c)], head.b.  Every part starts on a 16-byte boundary."""
+    from .params import encoder_layers
+    why = encoder_frames_unsupported(hp)
+    if why:
+        raise ValueError(f"encode_frames: unsupported encoder shape ({why})")
+    layers, c_top = encoder_layers(hp)
+    parts = [("input.w", (48, hp.ngf)), ("input.b", (hp.ngf,))]
+    for name, cin, cout, norm in layers[1:]:
+        parts += [(f"{name}.w", (16, cin // 16, cout // 16, 64, 4)), (f"{name}.b", (cout,)), (f"{name}.scale", (cout,)), (f"{name}.shift", (cout,))]
+    parts += [("head.w", (hp.nz_enc, 16 * c_top)), ("head.b", (hp.nz_enc,))]
+    lay, off = {}, 0
+    for k, shp in parts:
+        n = 1
+        for d in shp:
+            n *= d
+        assert n % 4 == 0
+        lay[k] = (off, shp)
+        off += n
+    return lay, off
+
+
+def pack_encoder_frames(sd, hp):
+    """One float32 blob with everything gcpx_encode_frames reads (encoder_frames_layout), on the device of `sd`: the conv weights in
+    the kernel's order, the biases, and per pyramid layer the BatchNorm's running statistics folded into an affine the way gcpx_bn_fold
+    folds them, in float32: scale = weight / sqrt(running_var + bn_eps), shift = bias - running_mean * scale."""
+    from .params import encoder_layers
+    lay, total = encoder_frames_layout(hp)
+    layers, c_top = encoder_layers(hp)
+    w0 = sd["encoder.net.input.conv.weight"]
+    blob = torch.zeros(total, dtype=torch.float32, device=w0.device)
+
+    def put(key, t):
+        off, shp = lay[key]
+        blob[off:off + t.numel()] = t.to(torch.float32).reshape(-1)
+        assert tuple(t.shape) == tuple(shp), (key, tuple(t.shape), shp)
+
+    put("input.w", w0.reshape(hp.ngf, 48).t().contiguous())
+    put("input.b", sd["encoder.net.input.conv.bias"])
+    for name, cin, cout, norm in layers[1:]:
+        p = f"encoder.net.{name}"
+        put(f"{name}.w", pack_conv4x4(sd[f"{p}.conv.weight"]))
+        put(f"{name}.b", sd[f"{p}.conv.bias"])
+        scale = sd[f"{p}.norm.weight"].float() / torch.sqrt(sd[f"{p}.norm.running_var"].float() + torch.tensor(hp.bn_eps, dtype=torch.float32))
+        put(f"{name}.scale", scale)
+        put(f"{name}.shift", sd[f"{p}.norm.bias"].float() - sd[f"{p}.norm.running_mean"].float() * scale)
+    put("head.w", sd["encoder.net.head.weight"].permute(0, 2, 3, 1).reshape(hp.nz_enc, 16 * c_top))
+    put("head.b", sd["encoder.net.head.bias"])
+    return blob
+
+
+def unpack_encoder_frames(blob, hp):
+    """the mirror of pack_encoder_frames: {state-dict key: tensor} of the conv weights and biases in their canonical layouts, and
+    `encoder.net.<name>.norm.scale` / `.shift`, the folded affine of every pyramid layer"""
+    from .params import encoder_layers
+    lay, total = encoder_frames_layout(hp)
+    assert blob.numel() == total, (blob.numel(), total)
+    layers, c_top = encoder_layers(hp)
+    ends = sorted(off for off, _ in lay.values()) + [total]
+    get = lambda key: blob[lay[key][0]:ends[ends.index(lay[key][0]) + 1]].reshape(lay[key][1])
+    out = {"encoder.net.input.conv.weight": get("input.w").t().reshape(hp.ngf, 3, 4, 4).contiguous(),
+           "encoder.net.input.conv.bias": get("input.b").clone()}
+    for name, cin, cout, norm in layers[1:]:
+        p = f"encoder.net.{name}"
+        out[f"{p}.conv.weight"] = unpack_conv4x4(get(f"{name}.w"), cin, cout)
+        out[f"{p}.conv.bias"] = get(f"{name}.b").clone()
+        out[f"{p}.norm.scale"], out[f"{p}.norm.shift"] = get(f"{name}.scale").clone(), get(f"{name}.shift").clone()
+    out["encoder.net.head.weight"] = get("head.w").reshape(hp.nz_enc, 4, 4, c_top).permute(0, 3, 1, 2).contiguous()
+    out["encoder.net.head.bias"] = get("head.b").clone()
+    return out

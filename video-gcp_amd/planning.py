@@ -997,11 +997,15 @@ class ImageCEMPolicy:
     """ImageCEMPolicy / CEMPolicy / PlannerPolicy (planner_policy.py:13-241) without the agent infrastructure: plan with the CEM
     planner when there is no plan, the plan is used up, or the re-planning interval comes round (`act`, :89-113); follow the plan
     open loop through its inverse-model actions or closed loop by re-inferring each action from the current image and the next
-    planned latent (`_infer_action`, :222-227: `model.encoder(img)[0][:, :, 0, 0]` -> `model.inv_mdl.run_single`)."""
+    planned latent (`_infer_action`, :222-227: `model.encoder(img)[0][:, :, 0, 0]` -> `model.inv_mdl.run_single`).
+    batch_encode: `_infer_action` encodes with `model.encode_frames`, the frame-independent encoder (csrc/enc_frames.hip), in place of
+    `model.encoder`: the actions a control.ControlRunner(batch_encode=True) computes for all its episodes in one launch, bit for bit
+    (not the bits of the default path: exact f32 against split-f16, both within the oracle's tolerance)."""
 
-    def __init__(self, model, planner, replan_interval=1, num_max_replans=10, closed_loop_execution=False):
+    def __init__(self, model, planner, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_encode=False):
         self.planner_model, self._cem_planner = model, planner
         self.replan_interval, self.num_max_replans, self.closed_loop_execution = replan_interval, num_max_replans, closed_loop_execution
+        self.batch_encode = bool(batch_encode)
         self.reset()
 
     def reset(self):
@@ -1038,6 +1042,6 @@ class ImageCEMPolicy:
     def _infer_action(self, current_img, target_latent):
         m = self.planner_model
         img = env2planner(np.asarray(current_img)[None]).to(m.device)
-        enc_img0 = m.encoder(img)[0][:, :, 0, 0]
+        enc_img0 = m.encode_frames(img) if self.batch_encode else m.encoder(img)[0][:, :, 0, 0]
         tl = torch.as_tensor(np.asarray(target_latent)[None], dtype=torch.float32, device=m.device)
         return m.inv_mdl.run_single(enc_img0, tl)[0].cpu().numpy()

@@ -290,6 +290,7 @@ SYMBOLS = [
     ("gcpx_cem_population", C.c_int, [vp, vp, vp, C.c_float, vp, i32, i32, i32, vp]),
     ("gcpx_cem_elites", C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     ("gcpx_cem_refit", C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    ("gcpx_encode_frames", C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, C.c_float, vp]),
 ]
 
 _lib = None

@@ -352,6 +352,7 @@ class WeightsMixin:
         slice of the flat vector ("rest" also re-splits the split-f16 tensors, which all gather from it), in launches of at most
         max_blocks workgroups (0: no limit)."""
         st = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        self._enc_frames_pack = None                 # (model.encode_frames builds it again from the new parameters)
         if bucket is not None:
             for off, cnt, two in self._arena_runs[bucket]:
                 rt.check(self.lib.gcpx_repack_blocks(self.theta.data_ptr(), self._arena_idx0.data_ptr() + 4 * off,
