@@ -140,12 +140,19 @@ typedef struct gcpx_conv_args {
 /* GCPX_SPLIT_ROWFOLD16: the row-folded weights of a 16 -> 16 channel upsampling block, two horizontal taps per k-step
    (packing.pack_conv3x3_fold16 / conv3x3_fold16_index over the [24][16][Cin] scratch of gcpx_fold_upsample_weights): the node half / the
    skip half of additional_conv_layer once the skip half is hoisted (gcpx_conv_args.addend) */
-typedef enum gcpx_split_layout { GCPX_SPLIT_PLAIN = 0, GCPX_SPLIT_ROWFOLD = 1, GCPX_SPLIT_HEAD32 = 2, GCPX_SPLIT_ROWFOLD16 = 3 } gcpx_split_layout;
+/* GCPX_SPLIT_LOWRES: the PLAIN pack of a 32 / 64-output-channel upsampling block (byte-identical: packing.pack_conv3x3_split32), run by
+   csrc/conv3x3_lowres.hip — the nine tap products on the SOURCE grid, bilinear x2 and 3x3 shift-sum behind them in f32.  Same contract
+   as the PLAIN launch (sources, bias, addend, raw store, stats_partial rows); only for problems gcpx_conv3x3_lowres_supported accepts */
+typedef enum gcpx_split_layout { GCPX_SPLIT_PLAIN = 0, GCPX_SPLIT_ROWFOLD = 1, GCPX_SPLIT_HEAD32 = 2, GCPX_SPLIT_ROWFOLD16 = 3,
+                                 GCPX_SPLIT_LOWRES = 4 } gcpx_split_layout;
 
 /* decoder block: (bilinear x2 upsample +) 3x3 conv, pad 1.  gcpx_conv3x3_grid(a) = number of workgroups that launch
    will use = rows of a->stats_partial (a->stats_partial must already be non-NULL in the query if it will be). */
 int gcpx_conv3x3(const gcpx_conv_args* a, void* stream);
 int gcpx_conv3x3_grid(const gcpx_conv_args* a);
+/* 1 when the block has a GCPX_SPLIT_LOWRES form (upsampling, split-f16 PLAIN-compatible pack, raw store at pitch Cout, and one of
+   128 -> 64 @4x4, 64 -> 32 @8x8, 128 -> 32 @8x8, 128 -> 32 @4x4), else 0.  split_layout may be PLAIN or LOWRES in the query */
+int gcpx_conv3x3_lowres_supported(const gcpx_conv_args* a);
 /* encoder block: 4x4 conv, stride 2, pad 1 (NHWC sources); its stats_partial has gcpx_conv4x4s2_grid() rows */
 int gcpx_conv4x4s2(const gcpx_conv_args* a, void* stream);
 int gcpx_conv4x4s2_grid(void);

@@ -1544,7 +1544,10 @@ extern "C" int gcpx_split_pack(const float* theta, const int32_t* idx, int32_t n
 
 // 32 / 64-output-channel upsampling blocks (Cin % 32 == 0) with split-f16 weights (packing.pack_conv3x3_split32): which = 0 for the
 // 16x16 tile with 2 channel tiles, 1 for 8x8x4 with 2, 2 for 8x8x4 with 4; grid as conv3x3.hip's launch<> computes it
+int gcpx_launch_lowres(const gcpx_conv_args* a, hipStream_t stream, int rows);      // conv3x3_lowres.hip
+
 int gcpx_launch_up32_split(const gcpx_conv_args* a, hipStream_t stream, int which, int grid) {
+    if (a->split_layout == GCPX_SPLIT_LOWRES) return gcpx_launch_lowres(a, stream, grid);
     if (which == 0) return launch_up32_split<2, 1>(a, stream, grid);
     if (which == 1) return launch_up32_split<2, 2>(a, stream, grid);
     return launch_up32_split<4, 2>(a, stream, grid);

@@ -311,6 +311,43 @@ def pack_conv3x3_split32(w):
     return torch.stack([w1, w2], 3).contiguous().view(torch.int16), e
 
 
+def bilinear_x2_matrix(n, dtype=torch.float64):
+    """[2 n, n]: bilinear x2 (align_corners=False, replicate clamp) along one axis as a matrix — output 2 s takes 0.25 / 0.75 of sources
+    s - 1, s; output 2 s + 1 takes 0.75 / 0.25 of s, s + 1"""
+    U = torch.zeros(2 * n, n, dtype=dtype)
+    for h in range(2 * n):
+        s = h // 2
+        s0, s1, w0 = (s, min(s + 1, n - 1), 0.75) if h % 2 else (max(s - 1, 0), s, 0.25)
+        U[h, s0] += w0
+        U[h, s1] += 1.0 - w0
+    return U
+
+
+def lowres_up_reference(x, w, b):
+    """conv3x3(bilinear_x2(x)) the way csrc/conv3x3_lowres.hip computes it (GCPX_SPLIT_LOWRES), in float64: the nine tap products
+    Y_t = W_t x on the SOURCE grid, then the separable interpolate + shift-sum — horizontal Z_ty = sum_tx shift_tx(Y_(ty,tx) Ux^T),
+    vertical out = b + sum_ty shift_ty(Uy Z_ty); a shifted-in row / column is the conv's zero padding.  x [F, Cin, H, W],
+    w [Cout, Cin, 3, 3], b [Cout] or None -> [F, Cout, 2 H, 2 W]"""
+    x, w = x.double(), w.double()
+    Fr, _, H, W = x.shape
+    cout = w.shape[0]
+    Uy, Ux = bilinear_x2_matrix(H), bilinear_x2_matrix(W)
+    out = torch.zeros(Fr, cout, 2 * H, 2 * W, dtype=torch.float64)
+    for ty in range(3):
+        z = torch.zeros(Fr, cout, H, 2 * W, dtype=torch.float64)
+        for tx in range(3):
+            y = torch.einsum("oc,fchw->fohw", w[:, :, ty, tx], x)            # Y_t: a 1x1 conv at source resolution
+            yx = torch.einsum("fohw,pw->fohp", y, Ux)                        # Up along x
+            lo, hi = max(0, 1 - tx), min(2 * W, 2 * W + 1 - tx)              # output columns px with px + tx - 1 inside
+            z[..., lo:hi] += yx[..., lo + tx - 1:hi + tx - 1]
+        zy = torch.einsum("qh,fohp->foqp", Uy, z)                            # Up along y
+        lo, hi = max(0, 1 - ty), min(2 * H, 2 * H + 1 - ty)
+        out[:, :, lo:hi] += zy[:, :, lo + ty - 1:hi + ty - 1]
+    if b is not None:
+        out += b.double()[None, :, None, None]
+    return out
+
+
 def conv3x3_split32_index(shape, offset):
     n = 1
     for d in shape:

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libgcpx.so")
 
 ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
 HEAD_RAW, HEAD_DLM_MEAN, HEAD_DLM_BOTH, HEAD_TANH_NCHW, HEAD_DLM_NLL, HEAD_DLM_NLL_GRAD = 0, 1, 2, 3, 4, 5
-SPLIT_PLAIN, SPLIT_ROWFOLD, SPLIT_HEAD32, SPLIT_ROWFOLD16 = 0, 1, 2, 3
+SPLIT_PLAIN, SPLIT_ROWFOLD, SPLIT_HEAD32, SPLIT_ROWFOLD16, SPLIT_LOWRES = 0, 1, 2, 3, 4
 EPI_NONE, EPI_LRELU, EPI_LSTM, EPI_GAUSS_SAMPLE = 0, 1, 2, 3
 MLP_PLAIN, MLP_GAUSS, MLP_TANH = 0, 1, 2
 
@@ -140,6 +140,7 @@ SYMBOLS = [
     ("gcpx_conv_grid", C.c_int, []),
     ("gcpx_conv3x3", C.c_int, [C.POINTER(ConvArgs), vp]),
     ("gcpx_conv3x3_grid", C.c_int, [C.POINTER(ConvArgs)]),
+    ("gcpx_conv3x3_lowres_supported", C.c_int, [C.POINTER(ConvArgs)]),
     ("gcpx_conv4x4s2", C.c_int, [C.POINTER(ConvArgs), vp]),
     ("gcpx_conv4x4s2_grid", C.c_int, []),
     ("gcpx_conv4x4s2_image", C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

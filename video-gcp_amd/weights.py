@@ -189,6 +189,14 @@ class WeightsMixin:
             if layout is None:
                 layout = rt.SPLIT_ROWFOLD16 if d.get("fold16") else (rt.SPLIT_ROWFOLD if "fold" in d else rt.SPLIT_PLAIN)
             a.split_layout = layout
+            # Low-resolution up-blocks take their tap products before the bilinear x2 (csrc/conv3x3_lowres.hip: a quarter of the MFMAs, the
+            # same PLAIN pack) where that measured faster (profiles/lowres_up.txt): the 64-output-channel block (pyramid-2: 78 -> 42 us) and,
+            # of the 32-channel ones, launches of at most one frame per CU (pyramid-1's hoisted skip half: 19 -> 13 us).  With several
+            # frames per CU the 32-channel form is bound by its LDS traffic (89 against 90 us for pyramid-1's node half): those keep the
+            # up32 kernel.  GCPX_NO_LOWRES=1 keeps it everywhere
+            if layout == rt.SPLIT_PLAIN and os.environ.get("GCPX_NO_LOWRES") is None and \
+                    (a.Cout == 64 or a.F <= self.lib.gcpx_conv_grid() // 2) and self.lib.gcpx_conv3x3_lowres_supported(C.byref(a)):
+                a.split_layout = rt.SPLIT_LOWRES
 
     def _pack_fused_embed(self):
         """Inference only: the input embedding Linear and LSTM layer 0's input projection are two Linears with nothing in between
