@@ -796,19 +796,25 @@ int gcpx_split_pack_group2(const gcpx_split_pack_desc* tab, int32_t nprob, uint3
    and -W2 (on the clamped row below).  w: dev [Cout][Cin][3][3]; out: dev f32 [24][Cout][Cin], set t = py 9 + dyl 3 + tx for
    t < 18, 18 + tx = -W0[tx], 21 + tx = -W2[tx]; sums formed in float64 in tap-row order (bit-identical to packing.fold_up_weights). */
 int gcpx_fold_upsample_weights(const float* w, int32_t Cout, int32_t Cin, float* out, void* stream);
-/* The optimizer state is four floats: state[0] = step counter, state[1] = this step's gradient-clipping coefficient (0 = unset = 1),
+/* The optimizer state is four floats: state[0] = step counter (a float: exact to 2^24 steps, where it stays), state[1] = this step's
+   gradient-clipping coefficient: > 0 the coefficient, 0 = unset = 1 (a zeroed state means "no clipping"), < 0 = the coefficient is
+   ZERO (gcpx_grad_clip_coef writes -1 when the norm overflowed to inf or max_norm / norm underflowed: the gradient does not enter the
+   step, as clip_grad_norm_ scales it to 0; stored as 0 it would read as unset and the exploded gradient would be applied whole),
    state[2] = the norm gcpx_grad_clip_coef measured, state[3] = the GATE.  With state[3] != 0 every step entry point below
    (gcpx_radam_step, gcpx_optim_step, gcpx_optim_range, whatever kind and tick) returns at kernel entry: theta, m, v and state[0] keep
    their bits.  gcpx_grad_health writes the gate (1 = this step's gradient or loss is not finite, 0 = clean) on every call; a caller
-   without a guard leaves it 0, and every result is then what it was before the slot had a meaning. */
+   without a guard leaves it 0, and every result is then what it was before the slot had a meaning.
+   The scalar coefficients of a step (beta1^t, beta2^t, RAdam's sma_max, sma and rectification term, Adam's bias corrections) are
+   formed in double from the float hyperparameters and the counter and rounded to float once: they are correct to float32 rounding for
+   every beta2 < 1 and t <= 2^24, and RAdam's sma >= 5 switch is the double-precision decision.  The element-wise arithmetic is float32. */
 /* RAdam (Liu et al. 2019; blox.torch.radam.RAdam as used by gcp_builder.py:178-179): state[0] = step counter (float),
    incremented by this call; rectified update when the variance is tractable (rho_t > 5), momentum SGD otherwise */
 int gcpx_radam_step(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, float* state, int64_t n, float lr,
                     float beta1, float beta2, float eps, float grad_scale, void* stream);
 /* The trainer's other optimizers (gcp_builder.py:174-186; torch.optim.Adam / RMSprop / SGD formulas): kind 1 = adam (p1, p2 = betas),
    2 = rmsprop (p1 = momentum, p2 = alpha), 3 = sgd (p1 = momentum).  m / v: the optimizer's two state vectors; state[0] = step
-   counter (incremented), state[1] = gradient-clipping coefficient applied to the (scaled) gradient (0 = unset = 1; set per step by
-   gcpx_grad_clip_coef; gcpx_radam_step applies it too). */
+   counter (incremented), state[1] = gradient-clipping coefficient applied to the (scaled) gradient (0 = unset = 1, < 0 = zero; set per
+   step by gcpx_grad_clip_coef; gcpx_radam_step applies it too). */
 int gcpx_optim_step(float* theta, const float* grad, float* m, float* v, float* state, int64_t n, int32_t kind, float lr, float p1,
                     float p2, float eps, float grad_scale, void* stream);
 /* One slice of an optimizer step: kind 0 = RAdam (p1, p2 = betas), 1 .. 3 as gcpx_optim_step, over n elements of the four vectors;
@@ -821,8 +827,10 @@ int gcpx_optim_step(float* theta, const float* grad, float* m, float* v, float* 
 int gcpx_optim_range(float* theta, const float* grad, float* m, float* v, float* state, int64_t n, int32_t kind, float lr, float p1,
                      float p2, float eps, float grad_scale, int32_t tick, int32_t max_blocks, void* stream);
 /* gradient_clip (gcp_builder.py:186 -> blox get_clipped_optimizer; spec here: torch.nn.utils.clip_grad_norm_ over all parameters):
-   state[2] = || grad_scale * grad ||_2, state[1] = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0).  partial: [n_partial]
-   scratch (deterministic two-stage sum). */
+   state[2] = || grad_scale * grad ||_2, state[1] = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0; -1 when that coefficient
+   is exactly 0, see the state above: a float32 sum of squares that overflows gives norm = inf).  partial: [n_partial] scratch
+   (deterministic two-stage sum: workgroup b adds the squares of elements b 256 + i + k 256 n_partial per thread i, then a tree;
+   one workgroup adds the partials the same way). */
 int gcpx_grad_clip_coef(const float* grad, int64_t n, float grad_scale, float max_norm, float* partial, int32_t n_partial, float* state,
                         void* stream);
 
@@ -1147,7 +1155,7 @@ int gcpx_topdown_bottlenecks(const float* match_dist_df, int32_t B, int32_t N, i
  *   tables live on the device and are built once per model (scalar_log.grad_tables).  Only the elements the chunks name are read, and
  *   a chunk outside [0, n) or longer than GCPX_GRAD_NORM_CHUNK is skipped.
  *   seg_norm[s] = |grad_scale| * coef * || segment s ||_2, with grad_scale as gcpx_grad_clip_coef takes it (1 / world when the buffer
- *   holds the ranks' sum) and coef = *clip_coef (NULL or a value of 0: 1) -- the clipping coefficient the step kernels apply to the
+ *   holds the ranks' sum) and coef = *clip_coef (NULL or a value of 0: 1; a negative value: 0) -- the clipping coefficient the step kernels apply to the
  *   gradient they read, where the reference's clip_grad_norm_ has scaled p.grad itself before it is logged.
  *   A segment whose elements are all exactly zero is NOT counted (this build's `p.grad is None`: a parameter off the graph gets no
  *   gradient write and keeps the zeros of the step's clear).  stats[0..3] = mean of the counted norms, their maximum (a NaN stays, as in

@@ -74,6 +74,9 @@ def test_segment_norms_on_a_synthetic_vector(gcpx_lib):
     assert np.all(np.abs(norm_c - 0.25 * ref) <= bound * 0.25 * ref)
     norm_0, _, _ = _launch_norms(gcpx_lib, g, chunks, seg0, scale=0.5, coef=torch.zeros(1, device="cuda"))
     assert np.array_equal(norm_0, norm)
+    # a negative slot = a coefficient of ZERO (gcpx_grad_clip_coef after an overflowed norm): the step applies no gradient, the log says 0
+    norm_n, stats_n, _ = _launch_norms(gcpx_lib, g, chunks, seg0, scale=0.5, coef=torch.full((1,), -1.0, device="cuda"))
+    assert np.all(norm_n == 0) and not np.signbit(norm_n).any() and stats_n[0] == 0 and stats_n[1] == 0 and stats_n[2] == stats[2]
     g[poff["p13.weight"][0] + 3] = float("inf")
     norm_i, stats_i, _ = _launch_norms(gcpx_lib, g, chunks, seg0, scale=0.5)
     keep = np.arange(len(lengths)) != 13

@@ -7,8 +7,9 @@ INDIRECT used to list the entry points whose only cover was a model-level test (
 tensor's max-abs).  It is empty and asserted to stay empty: the backward kernels have their kernel-level tests in
 tests/test_gpu_backward_kernels.py and tests/test_gpu_kernels.py, the forward / planner glue in tests/test_gpu_glue_kernels.py, the
 adaptive-binding kernels in tests/test_gpu_adaptive_kernels.py, the loss, KL and BatchNorm-statistics kernels in
-tests/test_gpu_loss_kernels.py (references and bounds: tests/loss_refs.py, pinned by tests/test_loss_refs_cpu.py).  A new entry point
-needs a direct test or an INFRASTRUCTURE reason."""
+tests/test_gpu_loss_kernels.py (references and bounds: tests/loss_refs.py, pinned by tests/test_loss_refs_cpu.py), the optimizer and
+gradient-clip kernels in tests/test_gpu_optim_kernels.py (tests/optim_refs.py, pinned by tests/test_optim_refs_cpu.py).  A new entry
+point needs a direct test or an INFRASTRUCTURE reason."""
 import glob
 import os
 import re

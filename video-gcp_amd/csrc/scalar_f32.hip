@@ -285,16 +285,34 @@ __global__ void __launch_bounds__(256) dlm_mean_bwd_kernel(const float* __restri
 }
 
 struct RadamCoef { float step, gsc; bool rect; };
+// b^t for the step counter t (an integer, 1 .. 2^24) by squaring in double: at most 48 products of 2^-53 each, so the result is exact to
+// float32 rounding with 2^23 to spare, and the same bits under every math library (powf is good to 1 - 2 ulp, and 1 - powf(b, t)
+// keeps that as an ABSOLUTE error: for b = 0.9999 and small t the difference had three good digits).
+__device__ __forceinline__ double pow_step(const float b, const float t) {
+    double r = 1.0, s = (double)b;
+    for (unsigned e = (unsigned)t; e; e >>= 1) {
+        if (e & 1u) r *= s;
+        s *= s;
+    }
+    return r;
+}
+// state[1], the step's clipping coefficient: > 0 = the coefficient, 0 = unset (no clipping: 1), < 0 = the coefficient is zero (the norm
+// overflowed, or max_norm / norm underflowed: clip_grad_norm_ scales such a gradient to 0)
+__device__ __forceinline__ float clip_factor(const float c) { return c > 0.f ? c : (c < 0.f ? 0.f : 1.f); }
+// The scalar coefficients of a step in double, rounded to float once: sma = sma_max - 2 t b2^t / (1 - b2^t) subtracts two numbers near
+// 2 / (1 - beta2) to get one near t, and in float32 that cancellation moved the sma >= 5 switch and cost the step coefficient up to a
+// third of its value (beta2 = 0.9999).  A few dozen double operations per thread beside 28 bytes of traffic per element.
 __device__ __forceinline__ RadamCoef radam_coef(const float* __restrict__ state, const float beta1, const float beta2, const float grad_scale) {
     const float t = state[0] + 1.f;
-    const float b2t = powf(beta2, t), b1t = powf(beta1, t);
-    const float sma_max = 2.f / (1.f - beta2) - 1.f;
-    const float sma = sma_max - 2.f * t * b2t / (1.f - b2t);
+    const double b2t = pow_step(beta2, t), b1t = pow_step(beta1, t);
+    const double sma_max = 2.0 / (1.0 - (double)beta2) - 1.0;
+    const double sma = sma_max - 2.0 * (double)t * b2t / (1.0 - b2t);
     RadamCoef c;
-    c.rect = sma >= 5.f;
-    if (c.rect) c.step = sqrtf((1.f - b2t) * (sma - 4.f) / (sma_max - 4.f) * (sma - 2.f) / sma * sma_max / (sma_max - 2.f)) / (1.f - b1t);
-    else c.step = 1.f / (1.f - b1t);
-    c.gsc = grad_scale * (state[1] > 0.f ? state[1] : 1.f);     // state[1]: this step's clipping coefficient (gcpx_grad_clip_coef), 0 = unset
+    c.rect = sma >= 5.0;
+    if (c.rect)
+        c.step = (float)(sqrt((1.0 - b2t) * (sma - 4.0) / (sma_max - 4.0) * (sma - 2.0) / sma * sma_max / (sma_max - 2.0)) / (1.0 - b1t));
+    else c.step = (float)(1.0 / (1.0 - b1t));
+    c.gsc = grad_scale * clip_factor(state[1]);
     return c;
 }
 __device__ __forceinline__ void radam_one(float& th, const float gr, float& m, float& v, const RadamCoef& c, const float lr, const float beta1,
@@ -359,8 +377,8 @@ __global__ void radam_tick_kernel(float* state) {
 }
 
 // The trainer's other optimizers (gcp_builder.py:174-186: 'adam', 'rmsprop', 'sgd' as torch.optim defines them) and the optional
-// gradient clipping by global norm.  state[0] = step counter, state[1] = clip coefficient of this step (1 when clipping is off),
-// state[2] = the clipped norm, state[3] = the gate.
+// gradient clipping by global norm.  state[0] = step counter, state[1] = clip coefficient of this step (clip_factor: 0 = unset, < 0 =
+// zero), state[2] = the norm that was measured, state[3] = the gate.
 //   adam:    m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  theta -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //   rmsprop: v = alpha v + (1 - alpha) g^2;  d = g / (sqrt(v) + eps);  momentum > 0: m = momentum m + d, theta -= lr m;  else theta -= lr d
 //   sgd:     momentum > 0: m = momentum m + g (m = g at the first step), theta -= lr m;  else theta -= lr g
@@ -370,8 +388,12 @@ __global__ void __launch_bounds__(256) optim_kernel(float* __restrict__ theta, c
                                                     const float grad_scale) {
     if (state[3] != 0.f) return;                    // the gate, as in radam_kernel
     const float t = state[0] + 1.f;
-    const float gs = grad_scale * (state[1] > 0.f ? state[1] : 1.f);
-    const float bc1 = 1.f - powf(p1, t), bc2s = sqrtf(1.f - powf(p2, t));
+    const float gs = grad_scale * clip_factor(state[1]);
+    float bc1 = 1.f, bc2s = 1.f;                    // Adam's bias corrections, in double as radam_coef's and rounded once
+    if (kind == 1) {
+        bc1 = (float)(1.0 - pow_step(p1, t));
+        bc2s = (float)sqrt(1.0 - pow_step(p2, t));
+    }
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float g = grad[i] * gs;
         if (kind == 1) {
@@ -406,7 +428,9 @@ __global__ void __launch_bounds__(256) sqnorm_partial_kernel(const float* __rest
     if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 
-// clip_grad_norm_: coefficient = min(1, max_norm / (||grad_scale * g|| + 1e-6)) -> state[1]; the norm itself -> state[2]
+// clip_grad_norm_: coefficient = min(1, max_norm / (||grad_scale * g|| + 1e-6)) -> state[1]; the norm itself -> state[2].  A coefficient
+// of exactly 0 (the f32 sum of squares overflowed: norm = inf; or the quotient underflowed) is stored as -1: 0 means "unset" to the step
+// kernels, and torch applies the 0 -- an exploded but finite gradient must not be applied at full size.
 __global__ void __launch_bounds__(256) clip_coef_kernel(const float* __restrict__ part, const int nb, const float grad_scale,
                                                         const float max_norm, float* __restrict__ state) {
     __shared__ float red[256];
@@ -421,7 +445,8 @@ __global__ void __launch_bounds__(256) clip_coef_kernel(const float* __restrict_
     if (threadIdx.x == 0) {
         const float norm = fabsf(grad_scale) * sqrtf(red[0]);
         state[2] = norm;
-        state[1] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+        const float coef = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+        state[1] = coef == 0.f ? -1.f : coef;
     }
 }
 

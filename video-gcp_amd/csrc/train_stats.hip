@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(kThreads2) segment_norm_kernel(const float* __
     __shared__ int counted[kThreads2];
     const int tid = threadIdx.x;
     float coef = clip_coef ? clip_coef[0] : 1.f;
-    if (coef == 0.f) coef = 1.f;
+    coef = coef > 0.f ? coef : (coef < 0.f ? 0.f : 1.f);        // the optimizer state's slot: 0 = unset, < 0 = a coefficient of zero
     const double mul = (double)fabsf(grad_scale) * (double)coef;
     // thread 0 walks the segments in index order: these are its running values
     double sum = 0.0;

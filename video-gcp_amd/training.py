@@ -299,12 +299,14 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         n = m.theta.numel()
         if self.gradient_clip:
             # clip_grad_norm_ over all parameters of the (averaged) gradient: its coefficient lands in opt_state[1], which the step reads
+            # (-1 for a coefficient of exactly 0 -- an overflowed norm -- since 0 means "unset": the step then applies no gradient)
             if self._clip_part is None:
                 self._clip_part = torch.empty(1024, device=m.device)
             rt.check(m.lib.gcpx_grad_clip_coef(self.grad.data_ptr(), n, scale, float(self.gradient_clip), self._clip_part.data_ptr(), 1024,
                                                self.opt_state.data_ptr(), st), "grad_clip")
         elif self._clip_state_dirty:
-            # opt_state[1] is the clip coefficient the step kernels apply whenever it is > 0: without clipping it must be 0 — also after
+            # opt_state[1] is the clip coefficient the step kernels apply whenever it is not 0 (> 0: the coefficient, < 0: a coefficient
+            # of zero, written when the norm overflowed): without clipping it must be 0 = unset — also after
             # resuming a checkpoint that was trained WITH clipping (the whole opt_state is restored)
             self.opt_state[1:2].zero_()
             self._clip_state_dirty = False
@@ -389,7 +391,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         and maximum -- one gcpx_grad_segment_norms on the caller's stream, no sync.  Returns device tensors:
         Outputs(names, seg_norm [len(names)], stats [4] = mean, max, number counted, number of non-finite norms).  The gradient buffer
         still holds the step's gradient (the optimizer kernels read it, the next backward clears it); under a process group it holds
-        the ranks' sum and is scaled by 1 / world here; the step's clipping coefficient (opt_state[1], 0 = none) is applied as the
+        the ranks' sum and is scaled by 1 / world here; the step's clipping coefficient (opt_state[1], 0 = none, < 0 = zero) is applied as the
         step kernels apply it.  A parameter whose gradient is zero everywhere is not counted (`p.grad is None`)."""
         from .plan_ops import Outputs
         from .scalar_log import GradStats
