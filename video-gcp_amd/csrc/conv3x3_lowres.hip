@@ -9,6 +9,12 @@
 //     Z_ty[sy, px] = sum_tx 1[px + tx inside] sum_sx ux(px + tx, sx) Y_(ty,tx)[sy, sx]          (6 FMA per value)
 //     out[py, px]  = b + sum_ty 1[py + ty inside] sum_sy uy(py + ty, sy) Z_ty[sy, px]          (6 FMA per value)
 //
+// Both stages are register-tiled in half-runs (half_run below): a thread reads the Hin / 2 + 1 source samples that one half of an output
+// row (column) depends on, for the three taps, ONCE — 3 (Hin / 2 + 1) - 1 float4 from LDS — and forms the Hin adjacent outputs of that
+// half from registers: 14 reads for 8 values at Hin = 8, 8 for 4 at Hin = 4, where one value at a time took 6 reads each.  The second
+// half of a row is the mirror image of the first (x -> W - 1 - x, tx -> 2 - tx), so both run the same code with the border rules and
+// bilinear weights folded at compile time; only the base address and the sign of the stride differ per thread.
+//
 // One unit of work = one frame (two at 4x4: 32 source pixels).  A workgroup has 3 CT wavefronts; wavefront (tx, ct) owns the three (ty, tx) taps of channel tile ct
 // and keeps their A fragments — the PLAIN up32 pack, [chunk][tap][CT][2][64] x 16 B — in registers for the whole persistent loop: no
 // weight traffic after the prologue.  The B fragments (the frame's activations, two f16 planes per 32-channel chunk) come from LDS and
@@ -35,11 +41,12 @@ struct LowresCfg {
     static constexpr int LDS_BYTES = PZ_BYTES + Y_BYTES + 64 + TAB_BYTES + STAT_BYTES;      // (64: the chunk maxima)
     static constexpr int NSLOT = UPIX * Q4;                                    // float4 staging slots of a unit
     static constexpr int NS = (NSLOT + NT - 1) / NT;
-    static constexpr int NHZ = FPU * 3 * HIN * WOUT * C4;                      // float4 items of the horizontal stage
-    static constexpr int NOUT = FPU * HOUT * WOUT * C4;                        // float4 items of the vertical stage = of the output
-    static constexpr int NO = (NOUT + NT - 1) / NT;
+    // half-runs: a row of Z is two runs of HIN output columns, a column of the output two runs of HIN output rows
+    static constexpr int NH = 2 * FPU * 3 * HIN * C4;                          // half-runs of the horizontal stage: one per thread
+    static constexpr int NV = 2 * FPU * WOUT * C4;                             // half-runs of the vertical stage: the first 2/3 of the threads
     static_assert(NT % C4 == 0 && NT % Q4 == 0, "a thread keeps one channel quad of the input and one of the output");
-    static_assert(NOUT * 16 <= Y_BYTES, "the finished output waits in the Y buffer");
+    static_assert(NH == NT && NV <= NT && NV % 64 == 0, "one horizontal half-run per thread; whole wavefronts in the vertical stage");
+    static_assert(NV * HIN * 16 <= Y_BYTES, "a finished unit may wait in the Y buffer");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
@@ -53,12 +60,51 @@ __device__ __forceinline__ void up_taps(const int h, const int n, int& s0, int& 
     w1 = 1.f - w0;
 }
 
+// One half-run of either interpolation stage, in the half's own coordinates (outputs r = 0 .. HIN - 1 from its border inwards):
+//     o[r] = sum_k 1[r + k - 1 >= 0] (w0 L_k[s0] + w1 L_k[s1]),   (s0, s1, w0, w1) = up_taps(r + k - 1)
+// p[k] points at sample 0 of tap k (the mirrored half passes tap 2 - k and its last sample), ss is the stride between samples in
+// floats (negative in the mirrored half).  r + k - 1 <= HIN stays inside the axis, so only the near border clamps; sample HIN / 2 of
+// tap 0 is never used.  Everything but the addresses folds at compile time.
+// TAPWISE (the instances with 96 registers of resident weights): one tap's samples in registers at a time, not all three.
+template <int HIN, bool TAPWISE>
+__device__ __forceinline__ void half_run(const float* const (&p)[3], const int ss, float4 (&o)[HIN]) {
+    constexpr int NS1 = HIN / 2 + 1;
+    int dep = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // (TAPWISE: the tap's addresses are made to depend on the previous tap's sums, which keeps its reads behind that arithmetic)
+        if (TAPWISE && k > 0) {
+#pragma unroll
+            for (int r = k > 1 ? 0 : 1; r < HIN; ++r) asm volatile("" : "+v"(dep) : "v"(o[r].x), "v"(o[r].w));
+        }
+        const float* pk = p[k] + dep;
+        float4 L[NS1];
+#pragma unroll
+        for (int s = 0; s < NS1; ++s)
+            if (k > 0 || s < NS1 - 1) L[s] = *reinterpret_cast<const float4*>(pk + s * ss);
+#pragma unroll
+        for (int r = 0; r < HIN; ++r) {
+            const int h = r + k - 1;
+            if (h >= 0) {
+                int s0, s1; float w0, w1;
+                up_taps(h, HIN, s0, s1, w0, w1);
+                const float4 A = L[s0], B = L[s1];
+                const float4 t = make_float4(w0 * A.x + w1 * B.x, w0 * A.y + w1 * B.y, w0 * A.z + w1 * B.z, w0 * A.w + w1 * B.w);
+                if (k == 0 || (k == 1 && r == 0)) o[r] = t;                  // (the first tap inside the axis)
+                else { o[r].x += t.x; o[r].y += t.y; o[r].z += t.z; o[r].w += t.w; }
+            }
+        }
+    }
+}
+
 template <int CT, int HIN, int NCHUNK, int FPU>
 __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gcpx_conv_args a, const int stat_rows) {
     using Cfg = LowresCfg<CT, HIN, NCHUNK, FPU>;
     constexpr int NT = Cfg::NT, NPIX = Cfg::NPIX, UPIX = Cfg::UPIX, NPG = Cfg::NPG, WOUT = Cfg::WOUT, HOUT = Cfg::HOUT, COUT = Cfg::COUT;
-    constexpr int C4 = Cfg::C4, Q4 = Cfg::Q4, NS = Cfg::NS, NSLOT = Cfg::NSLOT, NO = Cfg::NO, NOUT = Cfg::NOUT, NHZ = Cfg::NHZ;
+    constexpr int C4 = Cfg::C4, Q4 = Cfg::Q4, NS = Cfg::NS, NSLOT = Cfg::NSLOT, NV = Cfg::NV;
     constexpr int PLANE = Cfg::PLANE_BYTES, YS = Cfg::YS, FS = HOUT * WOUT * COUT;
+    // 48 registers of resident weights leave room to hold a finished half-run and its addend in registers; 96 do not
+    constexpr bool REG_RICH = CT * NCHUNK <= 4, AB_EARLY = REG_RICH;
     extern __shared__ float4 smem4[];
     char* planes = reinterpret_cast<char*>(smem4);                               // [chunk][piece][unit pixel][32] f16
     float* Z = reinterpret_cast<float*>(smem4);                                  // (the same bytes, one phase later)
@@ -93,17 +139,10 @@ __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gc
     }
     if (tid < NCHUNK) smax[tid] = 0u;
 
-    // a thread stages the same input channel quad in every slot (NT % Q4 == 0): its source, BatchNorm affine and activation are fixed
-    const int cgq = (tid % Q4) * 4, chq = cgq >> 5;
+    // a thread stages the same input channel quad in every slot (NT % Q4 == 0): its source, BatchNorm affine and activation are fixed,
+    // and it keeps one output channel quad through both interpolation stages (NT % C4 == 0).  Like the stages' index algebra these are
+    // derived again in every unit from an opaque copy of the thread index, not carried in registers beside the resident weights
     const int c0 = a.src[0].C;
-    const bool first = cgq < c0;
-    const int clq = first ? cgq : cgq - c0;
-    const float* sptr = (first ? a.src[0].ptr : a.src[1].ptr) + clq;
-    const int srcC = first ? a.src[0].C : a.src[1].C;
-    const int fdiv = first ? a.src[0].frame_div : a.src[1].frame_div;
-    const float slope = (first ? a.src[0].act : a.src[1].act) == GCPX_ACT_LRELU ? 0.2f : 1.f;
-    // ... and one output channel quad through both interpolation loops (NT % C4 == 0)
-    const int c4q = tid % C4;
     for (int c = tid; c < Cfg::CIN; c += NT) {
         const gcpx_conv_src& sr = c < c0 ? a.src[0] : a.src[1];
         const int cl = c < c0 ? c : c - c0;
@@ -115,29 +154,48 @@ __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gc
 
     float4 pre[NS];
     auto issue_loads = [&](const int f0, const int t) {
+        const int cgq = (t % Q4) * 4;
+        const bool first = cgq < c0;
+        const float* sptr = (first ? a.src[0].ptr : a.src[1].ptr) + (first ? cgq : cgq - c0);
+        const int srcC = first ? a.src[0].C : a.src[1].C;
+        // (frame -> source frame on the scalar unit: a unit has FPU frames and two sources, a thread picks)
+        int sf[FPU];
+#pragma unroll
+        for (int fl = 0; fl < FPU; ++fl) {
+            const int f = min(f0 + fl, F - 1);                            // (a unit's frames behind the last repeat it: computed, never stored)
+            const int q0 = f / a.src[0].frame_div, q1 = a.nsrc > 1 ? f / a.src[1].frame_div : 0;
+            sf[fl] = first ? q0 : q1;
+        }
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             const int idx = t + NT * k;
             pre[k] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (NSLOT % NT == 0 || idx < NSLOT) {
                 const int up = idx / Q4;
-                const int f = min(f0 + up / NPIX, F - 1);                 // (a unit's frames behind the last repeat it: computed, never stored)
-                pre[k] = *reinterpret_cast<const float4*>(sptr + ((size_t)(f / fdiv) * NPIX + up % NPIX) * srcC);
+                int fs = sf[0];
+#pragma unroll
+                for (int fl = 1; fl < FPU; ++fl) fs = up / NPIX == fl ? sf[fl] : fs;
+                pre[k] = *reinterpret_cast<const float4*>(sptr + ((size_t)fs * NPIX + up % NPIX) * srcC);
             }
         }
     };
     // A unit's output is stored one iteration late, behind the NEXT unit's staging: the memory counter is in order, so stores issued
     // right before the loop's back-edge would have to complete before the staging may touch the prefetched input; issued behind the
     // staging they are older than the next prefetch and long complete when it is waited for (conv3x3_up16_fold_kernel does the same)
-    // Until then it waits in LDS, in the Y buffer (dead behind the horizontal stage; every thread reads back what it wrote itself).
+    // Until then a half-run waits where the vertical stage left it, in its thread's registers, or (the instances with 96 registers
+    // of resident weights) in LDS, in the Y buffer: dead behind the horizontal stage, and every thread reads back what it wrote itself.
+    float4 keep[HIN];
     float4* O = reinterpret_cast<float4*>(Y);
     int pf0 = -1;
     auto store_out = [&](const int t) __attribute__((always_inline)) {
-        float* outu = a.out + (size_t)pf0 * FS;
+        if (t < NV) {
+            const int px = (t / C4) % WOUT, fl = (t / (C4 * WOUT)) % FPU, hv = t / (C4 * WOUT * FPU);
+            if (pf0 + fl < F) {
+                float* op = a.out + (size_t)(pf0 + fl) * FS + ((hv ? HOUT - 1 : 0) * WOUT + px) * COUT + (t % C4) * 4;
+                const int os = hv ? -WOUT * COUT : WOUT * COUT;
 #pragma unroll
-        for (int k = 0; k < NO; ++k) {
-            const int i = t + NT * k;
-            if ((NOUT % NT == 0 || i < NOUT) && pf0 + i / (HOUT * WOUT * C4) < F) *reinterpret_cast<float4*>(outu + i * 4) = O[i];
+                for (int r = 0; r < HIN; ++r) *reinterpret_cast<float4*>(op + r * os) = REG_RICH ? keep[r] : O[r * NV + t];
+            }
         }
     };
 
@@ -153,6 +211,8 @@ __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gc
         int tl = tid;
         asm volatile("" : "+v"(tl));
         // ---- registers -> BatchNorm affine + LeakyReLU of the producer; largest magnitude of every chunk over the unit ----
+        const int cgq = (tl % Q4) * 4, chq = cgq >> 5;
+        const float slope = (cgq < c0 ? a.src[0].act : a.src[1].act) == GCPX_ACT_LRELU ? 0.2f : 1.f;
         float4 v[NS];
         float m = 0.f;
         const float4 bn_s = *reinterpret_cast<const float4*>(bnS + cgq), bn_t = *reinterpret_cast<const float4*>(bnT + cgq);
@@ -167,9 +227,10 @@ __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gc
             m = fmaxf(m, fmaxf(fmaxf(fabsf(t.x), fabsf(t.y)), fmaxf(fabsf(t.z), fabsf(t.w))));
         }
         // (lanes l, l ^ 1, l ^ 2, l ^ 4 stage quads of the same 32-channel chunk: one LDS atomic per 8 lanes)
-        m = fmaxf(m, __shfl_xor(m, 1));
-        m = fmaxf(m, __shfl_xor(m, 2));
-        m = fmaxf(m, __shfl_xor(m, 4));
+        // (ds_swizzle in bit mode, lane ^ 1, 2, 4: no lane-address registers to carry)
+        m = fmaxf(m, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(m), 0x041f)));
+        m = fmaxf(m, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(m), 0x081f)));
+        m = fmaxf(m, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(m), 0x101f)));
         if ((lane & 7) == 0) atomicMax(&smax[chq], __float_as_uint(m));         // non-negative floats order like their bit patterns
         if (pf0 >= 0) store_out(tl);
         __syncthreads();                                                    // maxima complete; the previous unit's Z reads are done
@@ -206,8 +267,45 @@ __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gc
             }
         }
         __syncthreads();                                                    // planes complete, every thread has read the maxima
-        if (tid < NCHUNK) smax[tid] = 0u;
-        if (u + (int)gridDim.x < nunits) issue_loads((u + gridDim.x) * FPU, tl);    // the next unit arrives behind this one's arithmetic
+        if (tl < NCHUNK) smax[tl] = 0u;
+        // bias + the sequence's share of the conv (its skip channels, convolved once per sequence: gcpx_conv_args.addend) for this
+        // thread's vertical half-run.  Where the registers allow it (AB_EARLY: 48 registers of resident weights) it is requested here,
+        // BEFORE the next unit's input, so that the in-order memory counter lets the vertical stage wait for the addend alone; for the
+        // same reason the prefetch below is issued on every path (a workgroup's last unit fetches itself again, from L2: never used).
+        // The other instances fetch it in the vertical stage's epilogue, one output row at a time
+        // (frame -> addend frame on the scalar unit, as in issue_loads)
+        auto addend_frame = [&](const int fl) __attribute__((always_inline)) {
+            int q = 0;
+            if (a.addend) {
+#pragma unroll
+                for (int g = 0; g < FPU; ++g) {
+                    const int qg = min(f0 + g, F - 1) / a.addend_frame_div;
+                    q = fl == g ? qg : q;
+                }
+            }
+            return q;
+        };
+        float4 ab[HIN];
+        auto issue_addend = [&](const int t) __attribute__((always_inline)) {
+            if (t < NV) {
+                const float4 bq = *reinterpret_cast<const float4*>(biasT + (t % C4) * 4);
+#pragma unroll
+                for (int r = 0; r < HIN; ++r) ab[r] = bq;
+                if (a.addend) {
+                    const int px = (t / C4) % WOUT, fl = (t / (C4 * WOUT)) % FPU, hv = t / (C4 * WOUT * FPU);
+                    const float* ap = a.addend + (size_t)addend_frame(fl) * FS + ((hv ? HOUT - 1 : 0) * WOUT + px) * COUT + (t % C4) * 4;
+                    const int os = hv ? -WOUT * COUT : WOUT * COUT;
+#pragma unroll
+                    for (int r = 0; r < HIN; ++r) {
+                        const float4 ad = *reinterpret_cast<const float4*>(ap + r * os);
+                        ab[r].x += ad.x; ab[r].y += ad.y; ab[r].z += ad.z; ab[r].w += ad.w;
+                    }
+                }
+            }
+        };
+        if (AB_EARLY) issue_addend(tl);
+        // the next unit arrives behind this one's arithmetic
+        issue_loads((u + (int)gridDim.x < nunits ? u + (int)gridDim.x : u) * FPU, tl);
 
         // ---- Y_(ty,tx) = W_(ty,tx) x on the source grid: NCHUNK x NPG x 3 taps x 3 MFMAs, small terms first ----
         f32x4 acc[3][NPG];
@@ -252,82 +350,61 @@ __global__ void __launch_bounds__(3 * CT * 64, 1) conv3x3_lowres_kernel(const gc
         __syncthreads();                                                    // Y complete, the planes are free
         int tv = tid;
         asm volatile("" : "+v"(tv));
-        // bias + the sequence's share of the conv (its skip channels, convolved once per sequence: gcpx_conv_args.addend), requested
-        // here and used behind the horizontal stage
-        float4 ab[NO];
-#pragma unroll
-        for (int k = 0; k < NO; ++k) ab[k] = *reinterpret_cast<const float4*>(biasT + c4q * 4);
-        if (a.addend) {
-#pragma unroll
-            for (int k = 0; k < NO; ++k) {
-                const int i = tv + NT * k;
-                if (NOUT % NT == 0 || i < NOUT) {
-                    const int f = min(f0 + i / (HOUT * WOUT * C4), F - 1);
-                    const float4 ad = *reinterpret_cast<const float4*>(a.addend + (size_t)(f / a.addend_frame_div) * FS + (i % (HOUT * WOUT * C4)) * 4);
-                    ab[k].x += ad.x; ab[k].y += ad.y; ab[k].z += ad.z; ab[k].w += ad.w;
-                }
-            }
-        }
+        const int c4o = (tv % C4) * 4;
 
         // ---- horizontal: interpolate + shift-sum over tx.  A column outside the image is the conv's zero padding ----
-#pragma unroll 1
-        for (int i = tv; i < NHZ; i += NT) {
-            int t = i / C4;
-            const int px = t % WOUT; t /= WOUT;
+        // thread = (half, frame, ty, source row, channel quad): HIN output columns of Z_ty[sy, .] from the half's border inwards
+        {
+            int t = tv / C4;
             const int sy = t % HIN; t /= HIN;
-            const int ty = t % 3, fl = t / 3;
-            float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int ty = t % 3; t /= 3;
+            const int fl = t % FPU, h = t / FPU;
+            const float* yb = Y + ((ty * 3 + (h ? 2 : 0)) * UPIX + fl * NPIX + sy * HIN + (h ? HIN - 1 : 0)) * YS + c4o;
+            const int ts = h ? -UPIX * YS : UPIX * YS;
+            const float* const yp[3] = {yb, yb + ts, yb + 2 * ts};
+            float4 z[HIN];
+            half_run<HIN, !REG_RICH>(yp, h ? -YS : YS, z);
+            float* zp = Z + (((fl * 3 + ty) * HIN + sy) * WOUT + (h ? WOUT - 1 : 0)) * COUT + c4o;
+            const int zs = h ? -COUT : COUT;
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int hx = px + kx - 1;
-                if (hx >= 0 && hx < WOUT) {
-                    int s0, s1; float w0, w1;
-                    up_taps(hx, HIN, s0, s1, w0, w1);
-                    const float* yp = Y + ((ty * 3 + kx) * UPIX + fl * NPIX + sy * HIN) * YS + c4q * 4;
-                    const float4 A = *reinterpret_cast<const float4*>(yp + s0 * YS);
-                    const float4 B = *reinterpret_cast<const float4*>(yp + s1 * YS);
-                    z.x += w0 * A.x + w1 * B.x; z.y += w0 * A.y + w1 * B.y; z.z += w0 * A.z + w1 * B.z; z.w += w0 * A.w + w1 * B.w;
-                }
-            }
-            *reinterpret_cast<float4*>(Z + i * 4) = z;
+            for (int r = 0; r < HIN; ++r) *reinterpret_cast<float4*>(zp + r * zs) = z[r];
         }
         __syncthreads();                                                    // Z complete
 
-        f32x4 st1 = f32x4{0, 0, 0, 0}, st2 = f32x4{0, 0, 0, 0};
-        // ---- vertical: interpolate + shift-sum over ty, bias + addend, BatchNorm partial sums; the result waits in LDS for the next staging ----
+        // ---- vertical: interpolate + shift-sum over ty, bias + addend, BatchNorm partial sums; the result waits in registers for the next staging ----
+        // thread = (half, frame, output column, channel quad): HIN output rows of that column from the half's border inwards
+        if (tv < NV) {
+            int t = tv / C4;
+            const int px = t % WOUT; t /= WOUT;
+            const int fl = t % FPU, hv = t / FPU;
+            const float* zb = Z + (((fl * 3 + (hv ? 2 : 0)) * HIN + (hv ? HIN - 1 : 0)) * WOUT + px) * COUT + c4o;
+            const int ts = hv ? -HIN * WOUT * COUT : HIN * WOUT * COUT;
+            const float* const zq[3] = {zb, zb + ts, zb + 2 * ts};
+            float4 o[HIN];
+            half_run<HIN, !REG_RICH>(zq, hv ? -WOUT * COUT : WOUT * COUT, o);
+            const float4 bq = *reinterpret_cast<const float4*>(biasT + c4o);
+            const float* ap = a.addend + (size_t)addend_frame(fl) * FS + ((hv ? HOUT - 1 : 0) * WOUT + px) * COUT + c4o;
+            const int os = hv ? -WOUT * COUT : WOUT * COUT;
+            f32x4 st1, st2;
 #pragma unroll
-        for (int k = 0; k < NO; ++k) {
-            const int i = tv + NT * k;
-            __builtin_amdgcn_sched_barrier(0);                              // (one item's six LDS reads in flight, not all NO x 6)
-            if (NOUT % NT == 0 || i < NOUT) {
-                int t = i / C4;
-                const int px = t % WOUT; t /= WOUT;
-                const int py = t % HOUT, fl = t / HOUT;
-                float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    const int hy = py + ky - 1;
-                    if (hy >= 0 && hy < HOUT) {
-                        int s0, s1; float w0, w1;
-                        up_taps(hy, HIN, s0, s1, w0, w1);
-                        const float* zp = Z + (((fl * 3 + ky) * HIN) * WOUT + px) * COUT + c4q * 4;
-                        const float4 A = *reinterpret_cast<const float4*>(zp + s0 * WOUT * COUT);
-                        const float4 B = *reinterpret_cast<const float4*>(zp + s1 * WOUT * COUT);
-                        o.x += w0 * A.x + w1 * B.x; o.y += w0 * A.y + w1 * B.y; o.z += w0 * A.z + w1 * B.z; o.w += w0 * A.w + w1 * B.w;
-                    }
+            for (int r = 0; r < HIN; ++r) {
+                float4 b = AB_EARLY ? ab[r] : bq;
+                if (!AB_EARLY && a.addend) {
+                    __builtin_amdgcn_sched_barrier(0);                      // (one row's addend in registers, not all HIN)
+                    const float4 ad = *reinterpret_cast<const float4*>(ap + r * os);
+                    b.x += ad.x; b.y += ad.y; b.z += ad.z; b.w += ad.w;
                 }
-                const f32x4 r = f32x4{o.x + ab[k].x, o.y + ab[k].y, o.z + ab[k].z, o.w + ab[k].w};
-                O[i] = make_float4(r[0], r[1], r[2], r[3]);
-                if (f0 + fl < F) {
-                    st1 += r;
-                    st2 += r * r;
-                }
+                const f32x4 v4 = f32x4{o[r].x + b.x, o[r].y + b.y, o[r].z + b.z, o[r].w + b.w};
+                if (REG_RICH) keep[r] = make_float4(v4[0], v4[1], v4[2], v4[3]);
+                else O[r * NV + tv] = make_float4(v4[0], v4[1], v4[2], v4[3]);
+                st1 = r == 0 ? v4 : st1 + v4;
+                st2 = r == 0 ? v4 * v4 : st2 + v4 * v4;
             }
-        }
-        {
-            const float4 s1 = stat[tid * 2], s2 = stat[tid * 2 + 1];
-            stat[tid * 2] = make_float4(s1.x + st1[0], s1.y + st1[1], s1.z + st1[2], s1.w + st1[3]);
-            stat[tid * 2 + 1] = make_float4(s2.x + st2[0], s2.y + st2[1], s2.z + st2[2], s2.w + st2[3]);
+            if (f0 + fl < F) {                                              // (a frame behind the last repeats it: computed, never counted or stored)
+                const float4 s1 = stat[tv * 2], s2 = stat[tv * 2 + 1];
+                stat[tv * 2] = make_float4(s1.x + st1[0], s1.y + st1[1], s1.z + st1[2], s1.w + st1[3]);
+                stat[tv * 2 + 1] = make_float4(s2.x + st2[0], s2.y + st2[1], s2.z + st2[2], s2.w + st2[3]);
+            }
         }
         pf0 = f0;
     }

@@ -190,12 +190,12 @@ class WeightsMixin:
                 layout = rt.SPLIT_ROWFOLD16 if d.get("fold16") else (rt.SPLIT_ROWFOLD if "fold" in d else rt.SPLIT_PLAIN)
             a.split_layout = layout
             # Low-resolution up-blocks take their tap products before the bilinear x2 (csrc/conv3x3_lowres.hip: a quarter of the MFMAs, the
-            # same PLAIN pack) where that measured faster (profiles/lowres_up.txt): the 64-output-channel block (pyramid-2: 78 -> 42 us) and,
-            # of the 32-channel ones, launches of at most one frame per CU (pyramid-1's hoisted skip half: 19 -> 13 us).  With several
-            # frames per CU the 32-channel form is bound by its LDS traffic (89 against 90 us for pyramid-1's node half): those keep the
-            # up32 kernel.  GCPX_NO_LOWRES=1 keeps it everywhere
+            # same PLAIN pack) on every launch the kernel accepts.  With its interpolation stages register-tiled each of them measured
+            # faster than the up32 kernel by more than the spread (profiles/lowres_tiled.txt): pyramid-2 42 -> 33 us (up32: 78), pyramid-1's
+            # hoisted skip half 13 -> 9 us (up32: 19), and pyramid-1's node half, which kept the up32 kernel while the untiled form was
+            # bound by its LDS round trips (89 against 90 us), 92 -> 47 us.  GCPX_NO_LOWRES=1 keeps the up32 kernel everywhere
             if layout == rt.SPLIT_PLAIN and os.environ.get("GCPX_NO_LOWRES") is None and \
-                    (a.Cout == 64 or a.F <= self.lib.gcpx_conv_grid() // 2) and self.lib.gcpx_conv3x3_lowres_supported(C.byref(a)):
+                    self.lib.gcpx_conv3x3_lowres_supported(C.byref(a)):
                 a.split_layout = rt.SPLIT_LOWRES
 
     def _pack_fused_embed(self):
