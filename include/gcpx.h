@@ -261,6 +261,19 @@ int gcpx_gemm_group_dims(const gcpx_gemm_args* host_table, int32_t n, int32_t* d
 int gcpx_gemm_group(const gcpx_gemm_args* dev_table, const int32_t* dev_dims, int32_t n, int32_t total_blocks, void* stream);
 /* number of row blocks gcpx_gemm uses for an M x N problem (first dim of stats_partial) */
 int gcpx_gemm_row_blocks(int32_t M, int32_t N);
+/* Dispatch query: what gcpx_gemm would launch for these arguments, without launching anything (no HIP call besides the one-time
+   read of the device's CU count; 256 CUs are assumed without a device).  out6 = {form, PR, CR, grid x, grid y, grid z}: PR x CR
+   is the block of 16 x 16 tiles a wavefront (GCPX_GEMM_FORM_TILE) or a split-K workgroup (GCPX_GEMM_FORM_SPLIT_K) owns; PR, CR and
+   the grid's x, y are 0 for the split-f16 and planes kernels, which tile on their own.  gcpx_gemm takes its launch from the same
+   host function, under the same environment switches (GCPX_GEMM_TILE, GCPX_GEMM_NOKS, GCPX_GEMM_NO_KS_BLOCKS).  Returns the argument
+   errors gcpx_gemm would. */
+typedef enum gcpx_gemm_form_id {
+    GCPX_GEMM_FORM_TILE = 0,      /* one-wavefront blocks: csrc/gemm_tile.h, KS = false */
+    GCPX_GEMM_FORM_SPLIT_K = 1,   /* four wavefronts split K over one block: csrc/gemm_tile.h, KS = true */
+    GCPX_GEMM_FORM_SPLIT_F16 = 2, /* csrc/gemm_split.hip */
+    GCPX_GEMM_FORM_PLANES = 3     /* csrc/gemm_planes.hip */
+} gcpx_gemm_form_id;
+int gcpx_gemm_form(const gcpx_gemm_args* a, int32_t* out6);
 
 /* ---------------------------------------------------------------------------------------------------
  * Fused Predictor MLP:  input(in->mid, LReLU), n_mid x (mid->mid, GroupNorm(8), LReLU), head(mid->out).

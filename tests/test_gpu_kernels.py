@@ -437,12 +437,22 @@ def test_mlp(env, mid, in_dims, out_dim, M, gauss):
         assert_close(z, want[:, :nz] + torch.exp(want[:, nz:]) * eps, atol=5e-5, rtol=1e-5, name="z")
 
 
-@pytest.mark.parametrize("Mg,Ng,nb", [(32, 512, 6), (64, 512, 6), (128, 512, 6), (256, 512, 2), (64, 128, 1)])
-def test_mlp_group_with_gemm(env, Mg, Ng, nb):
+@pytest.mark.parametrize("Mg,Ng,nb,form", [
+    pytest.param(32, 512, 6, (1, 1, 1), id="32-512-6"), pytest.param(64, 512, 6, (1, 2, 2), id="64-512-6"),
+    pytest.param(128, 512, 6, (1, 4, 2), id="128-512-6"), pytest.param(256, 512, 2, (1, 2, 2), id="256-512-2"),
+    pytest.param(64, 128, 1, (1, 1, 1), id="64-128-1"), pytest.param(70, 832, 1, (1, 1, 2), id="KS12"),
+    pytest.param(70, 4160, 1, (1, 2, 4), id="KS24"), pytest.param(37, 160, 1, (0, 2, 2), id="W22"),
+    pytest.param(69, 160, 2, (0, 4, 2), id="W42")])
+def test_mlp_group_with_gemm(env, monkeypatch, Mg, Ng, nb, form):
     """gcpx_mlp_group_gemm (level_pre_kernel): two Predictors and one batched row GEMM as ONE launch — prior + posterior + the
-    split_linear merge of a tree level — equals gcpx_mlp_group followed by gcpx_gemm bit for bit (same workgroup bodies), for every
-    GEMM tiling the tree levels use (split-K single tiles, split-K blocks, one-wavefront blocks)."""
+    split_linear merge of a tree level — equals gcpx_mlp_group followed by gcpx_gemm bit for bit (same workgroup bodies), for all
+    seven level_pre_kernel variants: the GEMM as split-K <1,1>, <1,2>, <2,2>, <4,2>, <2,4> blocks (chosen by gcpx_gemm's cost models on
+    256 CUs) and as one-wavefront <2,2> and <4,2> blocks (forced through GCPX_GEMM_TILE, as tests/test_gpu_gemm_forms.py does).
+    form = (split-K, PR, CR): what gcpx_gemm_form must answer for the set's GEMM, asserted before anything runs."""
     rt, pk, lib, dev = env
+    if not form[0]:
+        for k_, v_ in (("GCPX_GEMM_TILE", f"{form[1]},{form[2]},0"), ("GCPX_GEMM_NO_KS_BLOCKS", "1"), ("GCPX_GEMM_NOKS", "1")):
+            monkeypatch.setenv(k_, v_)
     torch.manual_seed(Mg + Ng)
     mid, n_mid, M = 128, 3, Mg
     keep = []
@@ -503,6 +513,9 @@ def test_mlp_group_with_gemm(env, Mg, Ng, nb):
         keep.extend([raw, dd, tab])
         return raw, dd, total.value
 
+    out6 = (C.c_int32 * 6)()
+    rt.check(lib.gcpx_gemm_form(C.byref(gargs[1]), out6), "gemm_form")
+    assert tuple(out6[:3]) == form and out6[5] == nb, f"the merge GEMM runs as {list(out6)}, not as {form}"
     raw, dd, total = group(0)
     rt.check(lib.gcpx_mlp_group(raw.data_ptr(), dd.data_ptr(), 2, total, mid, _stream()), "mlp_group")
     rt.check(lib.gcpx_gemm(C.byref(gargs[0]), _stream()), "gemm")

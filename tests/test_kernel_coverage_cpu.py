@@ -9,7 +9,10 @@ tests/test_gpu_backward_kernels.py and tests/test_gpu_kernels.py, the forward / 
 adaptive-binding kernels in tests/test_gpu_adaptive_kernels.py, the loss, KL and BatchNorm-statistics kernels in
 tests/test_gpu_loss_kernels.py (references and bounds: tests/loss_refs.py, pinned by tests/test_loss_refs_cpu.py), the optimizer and
 gradient-clip kernels in tests/test_gpu_optim_kernels.py (tests/optim_refs.py, pinned by tests/test_optim_refs_cpu.py).  A new entry
-point needs a direct test or an INFRASTRUCTURE reason."""
+point needs a direct test or an INFRASTRUCTURE reason.
+Being called is no cover for an entry point that dispatches to many device bodies: the exact row GEMM behind gcpx_gemm (28 gemm_tile
+bodies, csrc/gemm_tile.h) has every one of them asserted through gcpx_gemm_form and held to float64 in tests/test_gpu_gemm_forms.py
+(tests/gemm_refs.py, pinned by tests/test_gemm_refs_cpu.py)."""
 import glob
 import os
 import re
@@ -19,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INFRASTRUCTURE = {
     "gcpx_version": "ABI version query (checked by build())",
     "gcpx_conv_grid": "grid-size query",
+    "gcpx_gemm_form": "dispatch query",
     "gcpx_graph_begin": "hipGraph capture", "gcpx_graph_end": "hipGraph capture", "gcpx_graph_launch": "hipGraph replay",
     "gcpx_graph_destroy": "hipGraph handle",
     "gcpx_stream_create": "stream handle", "gcpx_stream_create_priority": "stream handle", "gcpx_stream_destroy": "stream handle",

@@ -104,17 +104,6 @@ TileChoice choose_tile(int M, int N, int nb = 1) {
     return best;
 }
 
-template <int PR, int CR>
-void launch_t(const gcpx_gemm_args* a, hipStream_t stream) {
-    const int rbk = (a->M + 16 * PR - 1) / (16 * PR);
-    const int cbk = (a->N / 16 + 4 * CR - 1) / (4 * CR);
-    const int nb = a->nbatch > 1 ? a->nbatch : 1;
-    if (a->epi == GCPX_EPI_LSTM)
-        hipLaunchKernelGGL((gemm_kernel<PR, CR, true>), dim3(rbk, cbk, nb), dim3(256), 0, stream, *a);
-    else
-        hipLaunchKernelGGL((gemm_kernel<PR, CR, false>), dim3(rbk, cbk, nb), dim3(256), 0, stream, *a);
-}
-
 }  // namespace
 
 extern "C" int gcpx_gemm_row_blocks(int32_t M, int32_t N) {
@@ -232,84 +221,86 @@ static int gemm_check(const gcpx_gemm_args* a) {
     return GCPX_OK;
 }
 
+// THE dispatch of a checked problem: which kernel family, which block shape, which grid.  gcpx_gemm launches what this returns,
+// gcpx_gemm_form reports it and gcpx_gemm_tile_plan hands it to the combined launches — they cannot disagree.  Order: a multi-tile
+// split-K block when its cost model takes the problem; else the planes and split-f16 kernels; else split-K single tiles for few
+// rows (K >= 256, at most 1024 workgroups); else one-wavefront blocks.  planes_ok = false: the answer without the planes form.
+struct GemmForm { int form, pr, cr, gx, gy, gz; };
+
+static GemmForm gemm_form(const gcpx_gemm_args* a, const bool planes_ok) {
+    const int nb = a->nbatch > 1 ? a->nbatch : 1;
+    int pr = 1, cr = 1;
+    if (ks_block_choice(a, &pr, &cr))
+        return GemmForm{GCPX_GEMM_FORM_SPLIT_K, pr, cr, (a->M + 16 * pr - 1) / (16 * pr), a->N / (16 * cr), nb};
+    if (planes_ok && gcpx_gemm_planes_applies(a)) return GemmForm{GCPX_GEMM_FORM_PLANES, 0, 0, 0, 0, nb};
+    if (gcpx_gemm_split_applies(a)) return GemmForm{GCPX_GEMM_FORM_SPLIT_F16, 0, 0, 0, 0, nb};
+    TileChoice t = choose_tile(a->M, a->N, nb);
+    const long rbk = (a->M + 15) / 16, nt = a->N / 16;
+    // few rows: split K over the wavefronts of a workgroup when that still leaves the launch small
+    if (t.pr == 1 && t.cr == 1 && a->K >= 256 && !getenv("GCPX_GEMM_NOKS") && rbk * nt * nb <= 1024)
+        return GemmForm{GCPX_GEMM_FORM_SPLIT_K, 1, 1, (int)rbk, (int)nt, nb};
+    const bool known = (t.pr == 1 || t.pr == 2 || t.pr == 4) && (t.cr == 1 || t.cr == 2 || t.cr == 4);
+    if (!known) t = TileChoice{1, 1};                            // (a GCPX_GEMM_TILE shape without a kernel runs as <1,1>)
+    return GemmForm{GCPX_GEMM_FORM_TILE, t.pr, t.cr, (a->M + 16 * t.pr - 1) / (16 * t.pr), (a->N / 16 + 4 * t.cr - 1) / (4 * t.cr), nb};
+}
+
 // How gcpx_gemm would tile this problem, for launches that carry its workgroups next to other work (mlp.hip: level_pre_kernel):
 // block shape, split-K or one-wavefront blocks, grid.  false: bad arguments, or the problem runs on the split-f16 kernel.
 bool gcpx_gemm_tile_plan(const gcpx_gemm_args* a, int* pr, int* cr, int* ks, int* gx, int* gy, int* gz) {
     if (gemm_check(a) != GCPX_OK || a->stats_partial) return false;
-    const int nb = a->nbatch > 1 ? a->nbatch : 1;
-    *gz = nb;
-    if (ks_block_choice(a, pr, cr)) {
-        *ks = 1; *gx = (a->M + 16 * *pr - 1) / (16 * *pr); *gy = a->N / (16 * *cr);
-        return true;
-    }
-    if (gcpx_gemm_split_applies(a)) return false;
-    const TileChoice t = choose_tile(a->M, a->N, nb);
-    const long rbk = (a->M + 15) / 16, nt = a->N / 16;
-    if (t.pr == 1 && t.cr == 1 && a->K >= 256 && !getenv("GCPX_GEMM_NOKS") && rbk * nt * nb <= 1024) {
-        *pr = 1; *cr = 1; *ks = 1; *gx = (int)rbk; *gy = (int)nt;
-        return true;
-    }
-    *pr = t.pr; *cr = t.cr; *ks = 0;
-    *gx = (a->M + 16 * t.pr - 1) / (16 * t.pr); *gy = (a->N / 16 + 4 * t.cr - 1) / (4 * t.cr);
+    // (the planes form needs a launch of its own in front: a combined launch looks past it, as it always did)
+    const GemmForm f = gemm_form(a, false);
+    if (f.form != GCPX_GEMM_FORM_TILE && f.form != GCPX_GEMM_FORM_SPLIT_K) return false;
+    *pr = f.pr; *cr = f.cr; *ks = f.form == GCPX_GEMM_FORM_SPLIT_K;
+    *gx = f.gx; *gy = f.gy; *gz = f.gz;
     return true;
+}
+
+extern "C" int gcpx_gemm_form(const gcpx_gemm_args* a, int32_t* out6) {
+    const int st = gemm_check(a);
+    if (st != GCPX_OK) return st;
+    GCPX_CHECK_ARG(out6 != nullptr, "out6 is NULL");
+    const GemmForm f = gemm_form(a, true);
+    out6[0] = f.form; out6[1] = f.pr; out6[2] = f.cr; out6[3] = f.gx; out6[4] = f.gy; out6[5] = f.gz;
+    return GCPX_OK;
 }
 
 extern "C" int gcpx_gemm(const gcpx_gemm_args* a, void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const int st = gemm_check(a);
     if (st != GCPX_OK) return st;
-    {
-        int pr_ = 1, cr_ = 1;
-        if (!ks_block_choice(a, &pr_, &cr_)) {
-            if (gcpx_gemm_planes_applies(a)) return gcpx_launch_gemm_planes(a, stream);
-            if (gcpx_gemm_split_applies(a)) return gcpx_launch_gemm_split(a, stream);
+    const GemmForm f = gemm_form(a, true);
+    if (f.form == GCPX_GEMM_FORM_PLANES) return gcpx_launch_gemm_planes(a, stream);
+    if (f.form == GCPX_GEMM_FORM_SPLIT_F16) return gcpx_launch_gemm_split(a, stream);
+    const dim3 grid(f.gx, f.gy, f.gz);
+    const bool lstm = a->epi == GCPX_EPI_LSTM;
+#define GCPX_GEMM_LAUNCH(PR_, CR_, KS_)                                                                                       \
+    do {                                                                                                                      \
+        if (lstm) hipLaunchKernelGGL((gemm_kernel<PR_, CR_, true, KS_>), grid, dim3(256), 0, stream, *a);                     \
+        else hipLaunchKernelGGL((gemm_kernel<PR_, CR_, false, KS_>), grid, dim3(256), 0, stream, *a);                         \
+    } while (0)
+    if (f.form == GCPX_GEMM_FORM_SPLIT_K) {
+        switch (f.pr * 10 + f.cr) {
+            case 12: GCPX_GEMM_LAUNCH(1, 2, true); break;
+            case 22: GCPX_GEMM_LAUNCH(2, 2, true); break;
+            case 42: GCPX_GEMM_LAUNCH(4, 2, true); break;
+            case 24: GCPX_GEMM_LAUNCH(2, 4, true); break;
+            default: GCPX_GEMM_LAUNCH(1, 1, true); break;
+        }
+    } else {
+        switch (f.pr * 10 + f.cr) {
+            case 44: GCPX_GEMM_LAUNCH(4, 4, false); break;
+            case 42: GCPX_GEMM_LAUNCH(4, 2, false); break;
+            case 41: GCPX_GEMM_LAUNCH(4, 1, false); break;
+            case 24: GCPX_GEMM_LAUNCH(2, 4, false); break;
+            case 22: GCPX_GEMM_LAUNCH(2, 2, false); break;
+            case 21: GCPX_GEMM_LAUNCH(2, 1, false); break;
+            case 14: GCPX_GEMM_LAUNCH(1, 4, false); break;
+            case 12: GCPX_GEMM_LAUNCH(1, 2, false); break;
+            default: GCPX_GEMM_LAUNCH(1, 1, false); break;
         }
     }
-    const TileChoice t = choose_tile(a->M, a->N, a->nbatch > 1 ? a->nbatch : 1);
-    {
-        int pr = 1, cr = 1;
-        if (ks_block_choice(a, &pr, &cr)) {
-            const long nb = a->nbatch > 1 ? a->nbatch : 1;
-            const dim3 grid((a->M + 16 * pr - 1) / (16 * pr), a->N / (16 * cr), nb);
-            const bool lstm = a->epi == GCPX_EPI_LSTM;
-#define GCPX_KS_LAUNCH(PR_, CR_)                                                                                              \
-            do {                                                                                                              \
-                if (lstm) hipLaunchKernelGGL((gemm_kernel<PR_, CR_, true, true>), grid, dim3(256), 0, stream, *a);            \
-                else hipLaunchKernelGGL((gemm_kernel<PR_, CR_, false, true>), grid, dim3(256), 0, stream, *a);                \
-            } while (0)
-            if (pr == 1 && cr == 2) GCPX_KS_LAUNCH(1, 2);
-            else if (pr == 2 && cr == 2) GCPX_KS_LAUNCH(2, 2);
-            else if (pr == 4 && cr == 2) GCPX_KS_LAUNCH(4, 2);
-            else GCPX_KS_LAUNCH(2, 4);
-#undef GCPX_KS_LAUNCH
-            GCPX_CHECK_LAUNCH();
-            return GCPX_OK;
-        }
-    }
-    if (t.pr == 1 && t.cr == 1 && a->K >= 256 && !getenv("GCPX_GEMM_NOKS")) {
-        // few rows: split K over the wavefronts of a workgroup when that still leaves the launch small
-        const long nb = a->nbatch > 1 ? a->nbatch : 1;
-        const long rbk = (a->M + 15) / 16, nt = a->N / 16;
-        if (rbk * nt * nb <= 1024) {
-            if (a->epi == GCPX_EPI_LSTM)
-                hipLaunchKernelGGL((gemm_kernel<1, 1, true, true>), dim3(rbk, nt, nb), dim3(256), 0, stream, *a);
-            else
-                hipLaunchKernelGGL((gemm_kernel<1, 1, false, true>), dim3(rbk, nt, nb), dim3(256), 0, stream, *a);
-            GCPX_CHECK_LAUNCH();
-            return GCPX_OK;
-        }
-    }
-    switch (t.pr * 10 + t.cr) {
-        case 44: launch_t<4, 4>(a, stream); break;
-        case 42: launch_t<4, 2>(a, stream); break;
-        case 41: launch_t<4, 1>(a, stream); break;
-        case 24: launch_t<2, 4>(a, stream); break;
-        case 22: launch_t<2, 2>(a, stream); break;
-        case 21: launch_t<2, 1>(a, stream); break;
-        case 14: launch_t<1, 4>(a, stream); break;
-        case 12: launch_t<1, 2>(a, stream); break;
-        default: launch_t<1, 1>(a, stream); break;
-    }
+#undef GCPX_GEMM_LAUNCH
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

@@ -13,6 +13,7 @@ ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
 HEAD_RAW, HEAD_DLM_MEAN, HEAD_DLM_BOTH, HEAD_TANH_NCHW, HEAD_DLM_NLL, HEAD_DLM_NLL_GRAD = 0, 1, 2, 3, 4, 5
 SPLIT_PLAIN, SPLIT_ROWFOLD, SPLIT_HEAD32, SPLIT_ROWFOLD16, SPLIT_LOWRES = 0, 1, 2, 3, 4
 EPI_NONE, EPI_LRELU, EPI_LSTM, EPI_GAUSS_SAMPLE = 0, 1, 2, 3
+GEMM_FORM_TILE, GEMM_FORM_SPLIT_K, GEMM_FORM_SPLIT_F16, GEMM_FORM_PLANES = 0, 1, 2, 3
 MLP_PLAIN, MLP_GAUSS, MLP_TANH = 0, 1, 2
 
 vp = C.c_void_p
@@ -149,6 +150,7 @@ SYMBOLS = [
     ("gcpx_randn", C.c_int, [vp, i64, vp, vp]),
     ("gcpx_gemm", C.c_int, [C.POINTER(GemmArgs), vp]),
     ("gcpx_gemm_row_blocks", C.c_int, [i32, i32]),
+    ("gcpx_gemm_form", C.c_int, [C.POINTER(GemmArgs), vp]),
     ("gcpx_gemm_planes_workspace", C.c_int, [i32, i32, i32, vp, vp]),
     ("gcpx_mlp", C.c_int, [C.POINTER(MlpArgs), vp]),
     ("gcpx_balanced_binding", C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
