@@ -15,6 +15,10 @@ forward of plan_batch (one value: used by the loop; several: the t = 0 call alon
 --batch_encode: instead of the serial loop, the batched loop with the closed-loop encoder one frame per call and with one
 encode_frames launch per step (ControlRunner(batch_encode=True), csrc/enc_frames.hip), taking turns over the same tasks, --repeats times
 each: wall and planner seconds, executed steps per second and microseconds per episode-step with the planner time taken out.
+--planner vmpc / seq_latent (with --batch_plans): the same template over the flat predictor (model_cls = SequentialModel), re-planned at
+every step -- visual MPC (base_configs.vmpc, act_cond, action sequences scored by L2ImageCost, the best sample executed) and CEM in the
+latents of gcp_sequential (learned cost, closed loop); --keep_plans 0 leaves the plans of the plans-per-step loop on the device,
+--decode_candidates 1 decodes every candidate while scoring.  The population (MPC_CEM) is written into the line.
 Prints one JSON line per shape; --out appends them to a file under profiles/.
 """
 import argparse
@@ -37,7 +41,8 @@ CONF = textwrap.dedent('''
     from gcp.planning.cem.sampler import {sampler}
     from gcp.planning.cem.cem_planner import HierarchicalImageCEMPlanner
     from gcp.planning.cem.cost_fcn import {cost}
-    from experiments.prediction.base_configs import gcp_tree as base_conf
+    from gcp.prediction.models.sequential import SequentialModel
+    from experiments.prediction.base_configs import {base} as base_conf
 
     agent = AttrDict(type=BenchmarkAgent, env=(TopdownMultiroom3dEnv, dict(init_pos=None, goal_pos=None, n_rooms={n_rooms},
                      heading_smoothing=0.1, crop_window=40)), T={T}, image_height=32, image_width=32)
@@ -46,18 +51,34 @@ CONF = textwrap.dedent('''
                          nz_enc=128, nz_vae=256, regress_length=True, attach_state_regressor=True, attach_inv_mdl=True,
                          inv_mdl_params=AttrDict(n_actions=2, use_convs=False, build_encoder=False),
                          decoder_distribution='discrete_logistic_mixture'))
+    h_config.update(dict({model_extra}))
     h_config.pop("add_weighted_pixel_copy")
-    cem_params = AttrDict(prune_final=True, horizon={seq}, action_dim=256, verbose=False, {cem_extra},
+    cem_params = AttrDict(prune_final=True, horizon={horizon}, action_dim={action_dim}, verbose=False, {cem_extra},
                           n_level_hierarchy={levels}, sampler={sampler},
                           cost_fcn={cost}, cost_config=AttrDict(checkpt_path='none'))
     policy = AttrDict(type=ImageCEMPolicy, params=h_config, checkpt_path='none', cem_planner=HierarchicalImageCEMPlanner,
-                      cem_params=cem_params, replan_interval=agent.T + 2, closed_loop_execution=True)
+                      cem_params=cem_params, replan_interval={replan}, closed_loop_execution={closed_loop}{policy_extra})
     config = AttrDict(start_index=0, end_index=99, agent=agent, policy=policy)
 ''')
 # cem_params of .../gcp_tree/mod_hyper.py (the hierarchical planner) and of .../gcp_sequential/mod_hyper.py (the flat planner, same model)
-PLANNERS = {"tree": dict(sampler="ImageHierarchicalTreeCEMSampler", cost="ImageLearnedCostEstimate",
+TREE_MODEL = dict(base="gcp_tree", model_extra="", action_dim=256, horizon=None, replan="agent.T + 2", closed_loop=True, policy_extra="")
+# the flat predictor (model_cls = SequentialModel), re-planned at every step.  No shipped conf fixes these populations: MPC_CEM is this
+# tool's choice, written into every line it prints
+MPC_CEM = dict(batch_size=10, n_iters=2, elite_frac=0.3, horizon=10)
+MPC_EXTRA = "n_iters={n_iters}, batch_size={batch_size}, elite_frac={elite_frac}".format(**MPC_CEM)
+MPC_POLICY = ", model_cls=SequentialModel, num_max_replans=agent.T"
+PLANNERS = {"tree": dict(TREE_MODEL, sampler="ImageHierarchicalTreeCEMSampler", cost="ImageLearnedCostEstimate",
                          cem_extra="n_iters=3, batch_size=10, sampling_rates_per_layer=[10, 10]"),
-            "flat": dict(sampler="SimpleTreeCEMSampler", cost="ImageWrappedLearnedCostFcn", cem_extra="n_iters=1, batch_size=5, elite_frac=1.0")}
+            "flat": dict(TREE_MODEL, sampler="SimpleTreeCEMSampler", cost="ImageWrappedLearnedCostFcn",
+                         cem_extra="n_iters=1, batch_size=5, elite_frac=1.0"),
+            # visual MPC: base_configs.vmpc + act_cond, action sequences scored in pixel space, the best sample executed open loop
+            "vmpc": dict(base="vmpc", model_extra="nz_vae=0, attach_inv_mdl=False, lstm_init='zero'", action_dim=2, horizon=MPC_CEM["horizon"], replan=1,
+                         closed_loop=False, policy_extra=MPC_POLICY + ", act_cond=True", sampler="FlatCEMSampler", cost="L2ImageCost",
+                         cem_extra=MPC_EXTRA + ", use_inferred_actions=False, dense_cost=True"),
+            # CEM in the latents of the goal-conditioned flat predictor, the learned cost, closed-loop execution
+            "seq_latent": dict(base="gcp_sequential", model_extra="lstm_init='zero'", action_dim=256, horizon=MPC_CEM["horizon"], replan=1,
+                               closed_loop=True, policy_extra=MPC_POLICY, sampler="FlatCEMSampler", cost="ImageLearnedCostEstimate",
+                               cem_extra=MPC_EXTRA)}
 SHAPES = {9: dict(n_rooms=9, T=200, seq=100, levels=7), 25: dict(n_rooms=25, T=400, seq=200, levels=8)}
 
 
@@ -68,10 +89,14 @@ class TimedPlanner:
         self.planner, self.torch, self.seconds, self.calls = planner, torch, 0.0, 0
         self.tasks_per_call, self.first_call_s, self.max_rows = [], None, None
 
-    def plan_batch(self, states, goals):
+    @property
+    def device_plans(self):
+        return getattr(self.planner, "device_plans", False)
+
+    def plan_batch(self, states, goals, **kw):
         self.torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = self.planner.plan_batch(states, goals, max_rows=self.max_rows)
+        out = self.planner.plan_batch(states, goals, max_rows=self.max_rows, **kw)
         self.torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         self.seconds += dt
@@ -116,7 +141,7 @@ def time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T)
     for flag in (False, True):
         timed = TimedPlanner(planner, torch)
         timed.max_rows = best
-        runner = CT.ControlRunner(model, timed, env, batch_plans=flag, **desc.policy_args)
+        runner = CT.ControlRunner(model, timed, env, batch_plans=flag, keep_plans=bool(a.keep_plans) or not flag, **desc.policy_args)
         runner.run({k: v[:2] for k, v in tasks.items()})            # warm-up: plans and buffers of both kinds of call
         for _ in range(a.repeats):
             timed.seconds, timed.calls, timed.tasks_per_call, timed.first_call_s = 0.0, 0, [], None
@@ -136,7 +161,11 @@ def time_batch_plans(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T)
                tasks_per_call_mean=r3([float(np.mean(r["tasks"])) for r in bat]), tasks_per_call_max=[int(max(r["tasks"])) for r in bat],
                batched_ms_per_plan=r3([1e3 * r["planner"] / max(r["plans"], 1) for r in bat]),
                t0_call_s=r3([r["first"] for r in bat]),
-               t0_call_ms_per_plan=r3([1e3 * r["first"] / r["tasks"][0] for r in bat]))
+               t0_call_ms_per_plan=r3([1e3 * r["first"] / r["tasks"][0] for r in bat]),
+               per_episode_steps_per_s=[round(a.E * T / r["wall"], 1) for r in per], batched_steps_per_s=[round(a.E * T / r["wall"], 1) for r in bat],
+               batched_keep_plans=bool(a.keep_plans))
+    if a.planner in ("vmpc", "seq_latent"):
+        row.update(cem=dict(MPC_CEM), replan_interval=1, candidates_decoded=bool(planner.decode_candidates))
     return row
 
 
@@ -178,7 +207,12 @@ def main():
     ap.add_argument("--rooms", type=int, nargs="+", default=[9, 25])
     ap.add_argument("--out", default=None)
     ap.add_argument("--planner", choices=sorted(PLANNERS), default="tree", help="the conf's planner: tree = gcp_tree (hierarchical), "
-                    "flat = gcp_sequential (CEMPlanner over all tree latents)")
+                    "flat = gcp_sequential (CEMPlanner over all tree latents); over the flat predictor, re-planned at every step "
+                    "(with --batch_plans): vmpc = visual MPC (action sequences, L2ImageCost), seq_latent = CEM in its latents")
+    ap.add_argument("--decode_candidates", type=int, default=0, help="1 = the flat planner decodes the images of every candidate while it scores "
+                    "(CEMPlanner.decode_candidates; a hand-written cost always does)")
+    ap.add_argument("--keep_plans", type=int, default=1, help="--batch_plans: 0 = the plans-per-step loop keeps its plans on the device "
+                    "(ControlRunner(keep_plans=False))")
     ap.add_argument("--batch_plans", action="store_true", help="time planning per step (plan_batch) beside planning per episode")
     ap.add_argument("--repeats", type=int, default=3, help="--batch_plans: runs of each loop")
     ap.add_argument("--max_rows", type=int, nargs="+", default=None, help="--batch_plans: candidate rows per forward of plan_batch")
@@ -201,21 +235,27 @@ def main():
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "mod_hyper.py")
             with open(path, "w") as f:
-                f.write(CONF.format(**SHAPES[n_rooms], **PLANNERS[a.planner]))
+                kw = dict(SHAPES[n_rooms], **PLANNERS[a.planner])
+                kw["horizon"] = kw["horizon"] or kw["seq"]
+                f.write(CONF.format(**kw))
             conf = CL.exec_control_conf(path, {})
         desc, env_desc = CL.planner_from_control_conf(conf), CL.environment_from_control_conf(conf)
         model, planner, _ = CL.build_policy(desc, dev, seed=0, random_weights=True, verbose=False)
+        if a.decode_candidates:
+            planner.decode_candidates = True
         T = min(a.steps or env_desc.T, env_desc.T)
         tasks = NE.draw_tasks(n_rooms, 0, range(a.E))
         env = NE.NavEnvBatch(n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev)
 
         # one frame alone against the same frame in a batch of 3: encoder + inverse model
-        obs = NE.NavEnvBatch(n_rooms, env_desc.crop_window, 1, env_desc.img_sz, dev).reset({k: v[:3] for k, v in tasks.items()})
-        target = torch.randn(3, model._hp.nz_enc, generator=torch.Generator().manual_seed(0)).to(dev)
-        together = model.inv_mdl.run_single(model.encode(obs), target)
-        alone = torch.cat([model.inv_mdl.run_single(model.encode(obs[e:e + 1]), target[e:e + 1]) for e in range(3)])
-        row_diff = float((together - alone).abs().max())
-        enc_diff = float((model.encode(obs) - torch.cat([model.encode(obs[e:e + 1]) for e in range(3)])).abs().max())
+        row_diff = enc_diff = None
+        if model._hp.attach_inv_mdl and not (a.batch_plans or a.batch_encode):
+            obs = NE.NavEnvBatch(n_rooms, env_desc.crop_window, 1, env_desc.img_sz, dev).reset({k: v[:3] for k, v in tasks.items()})
+            target = torch.randn(3, model._hp.nz_enc, generator=torch.Generator().manual_seed(0)).to(dev)
+            together = model.inv_mdl.run_single(model.encode(obs), target)
+            alone = torch.cat([model.inv_mdl.run_single(model.encode(obs[e:e + 1]), target[e:e + 1]) for e in range(3)])
+            row_diff = float((together - alone).abs().max())
+            enc_diff = float((model.encode(obs) - torch.cat([model.encode(obs[e:e + 1]) for e in range(3)])).abs().max())
 
         if a.batch_encode:
             lines.append(time_batch_encode(a, torch, CT, model, planner, env, tasks, desc, n_rooms, T))

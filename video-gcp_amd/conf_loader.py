@@ -199,19 +199,19 @@ KEY_TABLE = {
         unbuilt={}),
     "policy": dict(
         mapped={"type", "params", "model_cls", "checkpt_path", "load_epoch", "cem_params", "replan_interval", "num_max_replans",
-                "closed_loop_execution"},
+                "closed_loop_execution", "act_cond"},
         checked=dict(cem_planner=_PLANNER_CLASSES),
         inert=dict(logger="logging", verbose="logging", max_dump_rollouts="logging", ncam="cameras"),
-        unbuilt=dict(act_cond=False)),
+        unbuilt={}),
     "cem": dict(
         mapped={"horizon", "action_dim", "n_iters", "batch_size", "elite_frac", "cost_fcn", "cost_config", "dense_cost",
                 "final_step_cost_weight", "sampler", "sampler_clip_val", "initial_std", "verbose", "max_seq_len", "n_level_hierarchy",
-                "sampling_rates_per_layer", "n_ll_samples"},
+                "sampling_rates_per_layer", "n_ll_samples", "use_inferred_actions"},
         checked={},
         # prune_final: set by every shipped control conf, read nowhere in the reference.  max_rollout_bs: how the reference chunks a
         # population; this build evaluates every candidate (planning.py, deviation D2)
         inert=dict(prune_final="unread", max_rollout_bs="chunking", dump_planning_data="logging"),
-        unbuilt=dict(LL_cost_fcn=None, use_delta_state_actions=False, use_inferred_actions=True)),
+        unbuilt=dict(LL_cost_fcn=None, use_delta_state_actions=False)),
 }
 # trainer keys (gcp_builder.py:_default_hparams) that the device trainer reads
 _TRAINER_KEYS = ("batch_size", "lr", "num_epochs", "adam_beta", "epoch_cycles_train", "seed", "gradient_clip", "top_of_100_eval",
@@ -402,7 +402,11 @@ def planner_from_control_conf(config, **over):
         hp           GCPHParams of the planner's model (policy.params through hparams_from_conf; `over` overrides fields)
         model_kind   'tree' / 'sequential' (policy.model_cls, else the tree model: planner_policy.py:36)
         planner      'hierarchical' (planning.HierarchicalCEMPlanner) or 'flat' (planning.CEMPlanner), decided by cem_params.sampler
-        planner_args keyword arguments of that planner; sampler / sampler_args (flat); cost / cost_args; verbose; horizon
+        planner_args keyword arguments of that planner; sampler / sampler_args (flat); cost / cost_args; verbose
+        horizon      cem_params.horizon (default: max_seq_len); below max_seq_len the flat planner caps its rollouts to it
+        act_cond     policy.act_cond: the samples are action sequences for the action-conditioned flat predictor (visual MPC)
+        action_source  'inverse_model' (the plan's actions are the final rollout's inverse-model actions) or 'samples'
+                     (cem_params.use_inferred_actions = False: the action plan is the best sample itself)
         policy_args  replan_interval, num_max_replans, closed_loop_execution of planning.ImageCEMPolicy
         weights      dict(path, epoch, file, cost_path, cost_file): `file` / `cost_file` are None where nothing resolves
         pairs        (start_index, end_index)
@@ -441,16 +445,49 @@ def planner_from_control_conf(config, **over):
     cem = dict(policy.get("cem_params") or {})
     unused = screen_keys("cem", cem, "cem_params")
     ignored += [f"cem_params.{k}:{KEY_TABLE['cem']['inert'].get(k, 'default')}" for k in unused]
-    if cem.get("action_dim") != hp.nz_vae:
-        raise ValueError(f"cem_params.action_dim = {cem.get('action_dim')}: the planner samples the model's latents, nz_vae = {hp.nz_vae}")
+    planner_cls = class_name(policy.get("cem_planner"))
+    sampler = class_name(cem.get("sampler", "HierarchicalTreeCEMSampler"))
+    # what the planner samples (planner_policy.py:231, cem_simulator.py:99-104): the model's latents, or, under act_cond, action sequences
+    # for the action-conditioned flat predictor
+    act_cond = bool(policy.get("act_cond", False))
+    flat_only = tuple(s_ for s_ in _FLAT_SAMPLERS if s_ != "SimpleTreeCEMSampler")
+    if act_cond:
+        if kind != "sequential":
+            raise ValueError(f"policy.act_cond = True with policy.model_cls = {class_name(policy.get('model_cls'))}: action sequences are "
+                             "rolled out by the flat predictor, model_cls = SequentialModel (cem_simulator.py:99-104)")
+        if not hp.action_conditioned_pred:
+            raise ValueError("policy.act_cond = True but policy.params has action_conditioned_pred = False: the predictor takes no actions "
+                             "(base_configs/vmpc.py sets it)")
+        if sampler not in flat_only:
+            raise ValueError(f"cem_params.sampler = {sampler} with policy.act_cond: action sequences are drawn by a flat sampler {flat_only}")
+        if cem.get("action_dim") != hp.n_actions:
+            raise ValueError(f"cem_params.action_dim = {cem.get('action_dim')}: under policy.act_cond the planner samples the model's "
+                             f"actions, n_actions = {hp.n_actions}")
+    else:
+        if kind == "sequential" and hp.action_conditioned_pred:
+            raise ValueError("policy.act_cond = False but policy.params has action_conditioned_pred = True: the predictor needs the "
+                             "planner's samples as actions (set act_cond)")
+        if kind == "sequential" and sampler not in flat_only:
+            raise ValueError(f"cem_params.sampler = {sampler} with policy.model_cls = SequentialModel: the flat predictor has no tree; its "
+                             f"latents are drawn by a flat sampler {flat_only}")
+        if cem.get("action_dim") != hp.nz_vae:
+            raise ValueError(f"cem_params.action_dim = {cem.get('action_dim')}: the planner samples the model's latents, nz_vae = {hp.nz_vae}")
+    use_inferred = bool(cem.get("use_inferred_actions", True))
+    if not use_inferred and not act_cond:
+        raise ValueError("cem_params.use_inferred_actions = False without policy.act_cond: the best sample is a latent sequence, not an "
+                         "action plan (cem_planner.py:143-149)")
+    closed_loop = bool(policy.get("closed_loop_execution", False))
+    if closed_loop and not hp.attach_inv_mdl:
+        raise ValueError("policy.closed_loop_execution = True but policy.params has attach_inv_mdl = False: closed-loop execution infers "
+                         "every action with the inverse model (planner_policy.py:222-227)")
     if cem.get("max_seq_len") not in (None, hp.max_seq_len):        # planner_policy.py:132 overwrites it with the model's
         raise ValueError(f"cem_params.max_seq_len = {cem['max_seq_len']}: the policy sets it to the model's, {hp.max_seq_len}")
     horizon = cem.get("horizon")
-    if horizon is not None and horizon < hp.max_seq_len:
-        raise ValueError(f"cem_params.horizon = {horizon} < max_seq_len = {hp.max_seq_len}: capping rollouts to a horizon "
-                         "(cem_planner.py:151-155) is not built; at or above max_seq_len it caps nothing")
-    planner_cls = class_name(policy.get("cem_planner"))
-    sampler = class_name(cem.get("sampler", "HierarchicalTreeCEMSampler"))
+    if horizon is not None and horizon < hp.max_seq_len and sampler in _HIERARCHICAL_SAMPLERS:
+        raise ValueError(f"cem_params.horizon = {horizon} < max_seq_len = {hp.max_seq_len}: the hierarchical planner optimises whole "
+                         "trees and does not cap them to a horizon (cem_planner.py:151-155 is built for the flat planner)")
+    if horizon is not None and horizon < 1:
+        raise ValueError(f"cem_params.horizon = {horizon}: a plan has at least one step")
     cost = class_name(cem.get("cost_fcn", "LearnedCostEstimate"))
     if cost not in _LEARNED_COSTS + _HAND_COSTS:
         raise ValueError(f"cem_params.cost_fcn = {cost}: no counterpart in planning.py ({_LEARNED_COSTS + _HAND_COSTS})")
@@ -490,7 +527,10 @@ def planner_from_control_conf(config, **over):
         planner = "flat"
         planner_args = dict(n_iters=int(n_iters), batch_size=int(cem.get("batch_size", 64)), elite_frac=float(cem.get("elite_frac", 0.1)),
                             max_seq_len=hp.max_seq_len)
-        sampler_args = dict(clip_val=clip, n_steps=hp.max_seq_len, action_dim=hp.nz_vae, initial_std=float(cem.get("initial_std", 3e-1)))
+        # the flat predictor takes one latent / action per predicted frame: sample t leads from frame t to frame t + 1 (sequential.py:50).
+        # The reference draws max_seq_len steps (cem_planner.py:109-113) and its model never reads the last one
+        sampler_args = dict(clip_val=clip, n_steps=hp.max_seq_len - 1 if kind == "sequential" else hp.max_seq_len,
+                            action_dim=hp.n_actions if act_cond else hp.nz_vae, initial_std=float(cem.get("initial_std", 3e-1)))
         if sampler == "SimpleTreeCEMSampler":
             sampler_args["n_level_hierarchy"] = int(levels)
     else:
@@ -511,9 +551,10 @@ def planner_from_control_conf(config, **over):
     if not ckpt and cost_ckpt:
         weights.update(path=cost_ckpt, file=_resolve_weights(cost_ckpt, cost_config.get("load_epoch")))
     policy_args = dict(replan_interval=int(policy.get("replan_interval", 1)), num_max_replans=int(policy.get("num_max_replans", 10)),
-                       closed_loop_execution=bool(policy.get("closed_loop_execution", False)))
+                       closed_loop_execution=closed_loop)
     return AttrDict(hp=hp, model_kind=kind, planner=planner, planner_args=planner_args, sampler=sampler, sampler_args=sampler_args,
-                    cost=cost, cost_args=cost_args, verbose=bool(cem.get("verbose", False)),
+                    cost=cost, cost_args=cost_args, verbose=bool(cem.get("verbose", False)), act_cond=act_cond,
+                    action_source="inverse_model" if use_inferred else "samples",
                     horizon=int(horizon) if horizon is not None else hp.max_seq_len, policy_args=policy_args, weights=weights,
                     pairs=(config.get("start_index"), config.get("end_index")), ignored=ignored)
 
@@ -521,6 +562,8 @@ def planner_from_control_conf(config, **over):
 def build_policy(description, device, weights=None, seed=0, random_weights=False, reference_rng=False, verbose=None):
     """(model, planner, policy) of a planner_from_control_conf description on `device`: the planning.* objects a user who owns an
     environment loop drives through `policy.act(t=..., images=..., goal_image=...)`.
+    The model is GCPTreeModel, or GCPSequentialModel for policy.model_cls = SequentialModel: then the simulator is
+    ActCondGCPImageSimulator under act_cond (visual MPC) and GCPImageSimulator without drawn lengths otherwise (CEM in its latents).
     weights: a checkpoint file instead of the conf's; random_weights: run on the seeded initialisation when no checkpoint resolves
     (otherwise that raises); seed: of the initialisation, and seed + 1 of the planner's draws; reference_rng: the hierarchical
     planner replays the reference's np.random sequence; verbose: keep the per-iteration elites (default: the conf's `verbose`)."""
@@ -529,10 +572,13 @@ def build_policy(description, device, weights=None, seed=0, random_weights=False
     from .model import GCPTreeModel
     from .params import init_params
     d = description
-    if d.model_kind != "tree":
-        raise ValueError("policy.model_cls names the flat predictor: the image CEM policy is built for the tree model")
     hp = d.hp
-    model = GCPTreeModel(hp, params=init_params(hp, seed=seed), device=device)
+    if d.model_kind == "sequential":                                 # policy.model_cls = SequentialModel (planner_policy.py:36)
+        from .params import init_params_sequential
+        from .sequential import GCPSequentialModel
+        model = GCPSequentialModel(hp, params=init_params_sequential(hp, seed=seed), device=device)
+    else:
+        model = GCPTreeModel(hp, params=init_params(hp, seed=seed), device=device)
     main = weights or d.weights["file"]
     if main:
         load_weights(main, model)
@@ -544,7 +590,10 @@ def build_policy(description, device, weights=None, seed=0, random_weights=False
         raise ValueError(f"no checkpoint at policy.checkpt_path = {d.weights['path']!r} (load_epoch = {d.weights['epoch'] or 'latest'}): "
                          "give a weights file, or ask for random weights")
     model.eval()                                                     # planner_policy.py:51
-    sim = P.GCPImageSimulator(model)
+    if d.get("act_cond"):                                            # planner_policy.py:231
+        sim = P.ActCondGCPImageSimulator(model)
+    else:                                                            # (the flat predictor has no length predictor)
+        sim = P.GCPImageSimulator(model, pred_length=d.model_kind != "sequential")
     cost = P.LearnedCostEstimate(model) if d.cost in _LEARNED_COSTS else getattr(P, d.cost)(d.cost_args["dense_cost"],
                                                                                              d.cost_args["final_step_weight"])
     verbose = d.verbose if verbose is None else bool(verbose)
@@ -554,7 +603,8 @@ def build_policy(description, device, weights=None, seed=0, random_weights=False
         a = dict(d.sampler_args)
         sampler = getattr(P, d.sampler)(a.pop("clip_val"), a.pop("n_steps"), a.pop("action_dim"), a.pop("initial_std"), device=device,
                                         seed=seed + 1, **a)
-        planner = P.CEMPlanner(sim, cost, sampler, verbose=verbose, **d.planner_args)
+        planner = P.CEMPlanner(sim, cost, sampler, verbose=verbose, horizon=d.horizon if d.horizon < hp.max_seq_len else None,
+                               use_inferred_actions=d.get("action_source", "inverse_model") != "samples", **d.planner_args)
     return model, planner, P.ImageCEMPolicy(model, planner, **d.policy_args)
 
 

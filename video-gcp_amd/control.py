@@ -20,6 +20,9 @@ executed steps of all E tasks advance together on the device (nav_env.NavEnvBatc
               and the weights only), the call ImageCEMPolicy(batch_encode=True)._infer_action makes for one frame.  Not the bits of the
               default path (split-f16 with shared scales); both are within the oracle's latent tolerance.  It combines
               with --batch_plans and --reference_rng and changes nothing without closed_loop_execution.
+  the model   the tree model, or the flat predictor of a conf with policy.model_cls = SequentialModel: visual MPC (act_cond: the best sample's
+              actions, no inverse model needed) and CEM in its latents (conf_loader.build_policy); --keep_plans 0 for loops
+              that re-plan at every step.
 The loop runs agent.T steps, as GeneralAgent.rollout does: no early stop."""
 import argparse
 import json
@@ -35,12 +38,17 @@ class ControlRunner:
     HierarchicalCEMPlanner, CEMPlanner) and one read-back
     of their frames per step; off (the default), every episode plans through its own planner call.
     batch_encode: closed-loop acting encodes the current frames of all episodes in one `model.encode_frames` launch; off (the default),
-    one `model.encode` call per frame.  An error if the model's encoder shape is not one `encode_frames` takes."""
+    one `model.encode` call per frame.  An error if the model's encoder shape is not one `encode_frames` takes.
+    keep_plans: `plans` holds a host copy of every plan made (the default); off, `dict(t, cost)` per plan, and with batch_plans and a
+    planner that hands its plans over on the device (CEMPlanner.plan_batch(device=True)) neither frames nor plans visit the host: what
+    a loop that re-plans at every step (visual MPC, replan_interval = 1) needs."""
 
     def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_plans=False,
-                 batch_encode=False):
+                 batch_encode=False, keep_plans=True):
         self.model, self.planner, self.env = model, planner, env
-        self.batch_plans, self.batch_encode = bool(batch_plans), bool(batch_encode)
+        self.batch_plans, self.batch_encode, self.keep_plans = bool(batch_plans), bool(batch_encode), bool(keep_plans)
+        if closed_loop_execution and not model._hp.attach_inv_mdl:
+            raise ValueError("closed_loop_execution needs the model's inverse model (attach_inv_mdl)")
         if self.batch_encode:
             from .packing import encoder_frames_unsupported
             why = encoder_frames_unsupported(model._hp)
@@ -48,7 +56,8 @@ class ControlRunner:
                 raise ValueError(f"batch_encode needs an encoder shape model.encode_frames takes ({why})")
         self.replan_interval, self.num_max_replans = int(replan_interval), int(num_max_replans)
         self.closed_loop_execution = bool(closed_loop_execution)
-        self.plans = []               # per episode: [(t, image_plan, action_plan, latent_plan, cost)] of every plan made (host copies)
+        # per episode, every plan made: dict(t, image_plan, action_plan, latent_plan, cost) (host copies); keep_plans=False: dict(t, cost)
+        self.plans = []
 
     # -- planning: ImageCEMPolicy.act's condition and _plan, per episode --
     def _needs_plan(self, e, t):
@@ -77,17 +86,47 @@ class ControlRunner:
 
     def _plan_batch(self, due, t):
         """the episodes `due` at step t through one planner.plan_batch call; their frames come back in one copy"""
+        if self._device_plans:
+            return self._plan_batch_device(due, t)
         frames = self.env.frames[torch.as_tensor(due, device=self.env.device), t].cpu().numpy()
         for e, r in zip(due, self.planner.plan_batch(frames, self.goal_frames_np[due])):
             self._record(e, t, r.predictions, r.actions, r.latents, r.cost)
+
+    def _plan_batch_device(self, due, t):
+        """keep_plans=False: frames and plans stay on the device (CEMPlanner.plan_batch(device=True)): the frames of the due episodes go
+        from env.frames to the planner as they are, the plans into `act` / `lat` with one indexed copy each; what comes back are the
+        plans' costs and lengths (2 numbers per episode: the execution counters are host integers)"""
+        dev = self.env.device
+        idx = torch.as_tensor(due, device=dev)
+        r = self.planner.plan_batch(self.env.frames[idx, t], self.env.goal_frames[idx], device=True, latents=self.closed_loop_execution)
+        K, A = len(due), r.actions.shape[1]
+        L = r.latents.shape[1] if r.latents is not None else 0
+        if self.act is None or self.act.shape[1] < max(A, L):
+            n, E = max(A, L, self._lmax), self.env.E
+            grow = lambda old, width: torch.zeros(E, n, width, device=dev) if old is None else \
+                torch.cat([old, torch.zeros(E, n - old.shape[1], width, device=dev)], dim=1)
+            self.act = grow(self.act, self.model._hp.n_actions)
+            self.lat = grow(self.lat, self.model._hp.nz_enc)
+        self.act[idx, :A] = r.actions.reshape(K, A, -1).to(torch.float32)
+        if r.latents is not None:
+            self.lat[idx, :L] = r.latents
+        host = torch.stack([r.costs.to(torch.float64), r.lengths.to(torch.float64), r.n_actions.to(torch.float64)]).cpu().numpy()
+        for j, e in enumerate(due):
+            self.plan_len[e], self.exec_step[e] = int(host[1, j]), 0
+            self.lat_len[e], self.act_len[e] = (int(host[1, j]) if r.latents is not None else 0), int(host[2, j])
+            self.num_replans[e] += 1
+            self.plans[e].append(dict(t=t, cost=float(host[0, j])))
 
     def _record(self, e, t, image_plan, action_plan, latent_plan, cost):
         actions = np.zeros((0, 2), dtype=np.float32) if action_plan is None else np.asarray(action_plan)
         self._store(e, actions, np.asarray(latent_plan))
         self.plan_len[e], self.exec_step[e] = int(np.asarray(image_plan).shape[0]), 0
         self.num_replans[e] += 1
-        self.plans[e].append(dict(t=t, image_plan=np.asarray(image_plan), action_plan=actions, latent_plan=np.asarray(latent_plan),
-                                  cost=cost))
+        if self.keep_plans:
+            self.plans[e].append(dict(t=t, image_plan=np.asarray(image_plan), action_plan=actions, latent_plan=np.asarray(latent_plan),
+                                      cost=cost))
+        else:
+            self.plans[e].append(dict(t=t, cost=cost))
 
     # -- acting: ImageCEMPolicy.get_action for all rows --
     def _encode(self, obs):
@@ -123,6 +162,8 @@ class ControlRunner:
         self.lat_len, self.act_len = [0] * E, [0] * E
         self.plans = [[] for _ in range(E)]
         self.goal_frames_np = env.goal_frames.cpu().numpy()
+        # plans per step that nobody keeps stay on the device, with a planner that can hand them over there
+        self._device_plans = self.batch_plans and not self.keep_plans and bool(getattr(self.planner, "device_plans", False))
         for t in range(T):
             if self.batch_plans:
                 due = [e for e in range(E) if self._needs_plan(e, t)]
@@ -171,6 +212,8 @@ def get_args(argv=None):
     p.add_argument("--batch_encode", type=int, default=0, help="1 = closed-loop acting encodes the frames of all episodes in one launch of the "
                    "frame-independent encoder (model.encode_frames): not the default encoder's bits, see DESIGN.md 5.7; no effect without "
                    "closed_loop_execution; an error if the model's encoder shape is unsupported")
+    p.add_argument("--keep_plans", type=int, default=1, help="0 = keep only the step and the cost of every plan (ControlRunner.plans); with "
+                   "--batch_plans 1 and a flat planner the plans then stay on the device: no image plan is decoded or copied to the host")
     return p.parse_args(argv)
 
 
@@ -190,8 +233,10 @@ def main(argv=None):
         print(f"[control] not used from {os.path.basename(args.experiment)}: {k}", flush=True)
     model, planner, _ = CL.build_policy(desc, dev, weights=args.weights or None, seed=args.seed, random_weights=bool(args.random_weights),
                                         reference_rng=args.reference_rng, verbose=False)
-    if not model._hp.attach_inv_mdl:
-        raise ValueError("the control loop needs the inverse model (attach_inv_mdl) for its actions")
+    needs_inv = [k for k, v in (("policy.closed_loop_execution = True", desc.policy_args["closed_loop_execution"]),
+                                ("cem_params.use_inferred_actions = True", desc.get("action_source", "inverse_model") == "inverse_model")) if v]
+    if needs_inv and not model._hp.attach_inv_mdl:
+        raise ValueError(f"{' and '.join(needs_inv)}: the control loop needs the inverse model (attach_inv_mdl) for its actions")
     assets = None
     if args.topdown_assets:
         from .dataset import load_topdown_assets
@@ -218,7 +263,8 @@ def main(argv=None):
     env = NE.NavEnvBatch(env_desc.n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev, assets=assets)
     if args.batch_plans and not hasattr(planner, "plan_batch"):
         raise ValueError(f"--batch_plans 1 needs a planner with plan_batch; the conf builds {type(planner).__name__}, which has none")
-    runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), batch_encode=bool(args.batch_encode), **desc.policy_args)
+    runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), batch_encode=bool(args.batch_encode),
+                           keep_plans=bool(args.keep_plans), **desc.policy_args)
     parts = []
     for s in range(0, len(idx), max(args.batch, 1)):
         parts.append(runner.run({k: v[s:s + max(args.batch, 1)] for k, v in tasks.items()}))

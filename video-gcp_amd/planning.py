@@ -28,7 +28,17 @@ from .model import Outputs
 
 
 def env2planner(img):
-    """GCPImageSimulator._env2planner (cem_simulator.py:87-96): env image(s) -> NCHW in [-1, 1]."""
+    """GCPImageSimulator._env2planner (cem_simulator.py:87-96): env image(s) -> NCHW in [-1, 1].
+    Bytes that are already on a device are converted there through the 256 values the host conversion gives (a device division by a
+    scalar may multiply by its reciprocal): the same bits as converting on the host and uploading, without the round trip."""
+    if torch.is_tensor(img) and img.dtype == torch.uint8 and img.device.type != "cpu":
+        table = torch.arange(256, dtype=torch.float32)
+        if int(img.max()) > 1:
+            table = table / 255.0
+        out = (table * 2 - 1.0).to(img.device)[img.long()]
+        if out.dim() == 5:
+            out = out[0]
+        return out.permute(0, 3, 1, 2) if out.dim() == 4 else out
     img = torch.as_tensor(img, dtype=torch.float32)
     if img.max() > 1.0:
         img = img / 255.0
@@ -88,6 +98,11 @@ class GCPImageSimulator:
         with m.val_mode(pred_length=self.pred_length, decode=decode):
             out = m(inp, "train")                    # cem_simulator.py:29-31 (phase defaults to 'train')
         raw = out.raw
+        if "E" not in raw:
+            # the flat predictor (GCPSequentialModel, samples [n, max_seq_len - 1, nz_vae]) has no tree: its frames are `images`, its
+            # goal latent `e_g`, what ActCondGCPImageSimulator reads
+            return Outputs(images=raw.get("images"), latents=raw["model_enc_seq_padded"], lengths=raw["seq_len"],
+                           actions=raw.get("actions_padded"), states=raw.get("regressed_state_padded"), e_goal=raw["e_g"], out=out)
         return Outputs(images=raw.get("pruned_padded"), latents=raw["model_enc_seq_padded"], lengths=raw["seq_len"],
                        actions=raw.get("actions_padded"), states=raw.get("regressed_state_padded"),
                        e_goal=raw["E"][:, -1], out=out)
@@ -125,7 +140,7 @@ class ActCondGCPImageSimulator(GCPImageSimulator):
     `GCPSequentialModel`.  Selected by the policy's `act_cond` flag (planner_policy.py:197,231).  Such a model never draws its length
     (base_gcp.py:224-226): every rollout has `rollout_len` frames, frame 0 being the start image (sequential.py:57)."""
 
-    supports_latent_only = False     # the flat predictor's plan always decodes
+    supports_latent_only = True      # rollout_device(..., decode=False): the flat predictor's plan without decoder and head launches
 
     def __init__(self, model, append_latent=True, pred_length=False):
         assert model._hp.action_conditioned_pred, "the action-conditioned simulator needs an action-conditioned predictor"
@@ -142,10 +157,10 @@ class ActCondGCPImageSimulator(GCPImageSimulator):
         assert tuple(a.shape[1:]) == (hp.max_seq_len - 1, hp.n_actions), "one action per predicted frame"
         inp = dict(I_0=self._bcast(state, n), I_g=self._bcast(goal_state, n), actions=a,
                    end_ind=torch.full((n,), rollout_len - 1, dtype=torch.long, device=m.device))
-        with m.val_mode(pred_length=False):
+        with m.val_mode(pred_length=False, decode=decode):
             out = m(inp, "train")
         raw = out.raw
-        return Outputs(images=raw["images"], latents=raw["model_enc_seq_padded"], lengths=raw["seq_len"],
+        return Outputs(images=raw.get("images"), latents=raw["model_enc_seq_padded"], lengths=raw["seq_len"],
                        actions=raw.get("actions_padded"), states=raw.get("regressed_state_padded"), e_goal=raw["e_g"], out=out)
 
 
@@ -332,7 +347,10 @@ class L2ImageCost(CostFcn, ImageCost):
 
     @staticmethod
     def _goal_planes(goal_raw, dtype=None):
-        g = np.asarray(goal_raw, dtype=dtype)
+        g = np.asarray(goal_raw)
+        if g.dtype == np.uint8:                                   # a recorded frame (control.ControlRunner's goals): bytes, as env2planner
+            g = g.astype(np.float32) / np.float32(255.0)
+        g = g.astype(dtype) if dtype is not None else g
         return np.moveaxis(g, 3, 1) * 2 - 1.0                     # HWC in [0, 1] -> CHW in [-1, 1]
 
     def _prepare_goal(self, goal_raw):
@@ -591,11 +609,19 @@ class CEMPlanner:
     """Flat CEM over tree latents with device-resident rollouts and sharded candidates (cem_planner.py:55-135)."""
 
     def __init__(self, simulator, cost, sampler, n_iters=3, batch_size=512, elite_frac=0.1, max_seq_len=80,
-                 goal_in_cost=True, decode_candidates=False, verbose=False):
+                 goal_in_cost=True, decode_candidates=False, verbose=False, horizon=None, use_inferred_actions=True):
         # decode_candidates: also decode the images of every candidate while scoring (what the reference's simulator does,
         # cem_simulator.py:29-59).  The learned cost reads latents only, so by default the images are decoded once, for the
         # plan that is returned; scores, elites and the returned plan are the same either way.
         self.decode_candidates = decode_candidates or not hasattr(cost, "sequence_cost_device")     # hand-written costs read the images
+        # horizon (cem_planner.py:115-122,151-155: _cap_to_horizon): every rollout's predictions, actions, states and latents are cut to
+        # their first `horizon` entries before they are scored, and the returned plan likewise.  On the device: the rollout still runs
+        # max_seq_len steps, its lengths are clamped in front of the cost (which reads the first `length` steps only), and the final
+        # rollout is sliced.  None: nothing is cut.
+        # use_inferred_actions (cem_planner.py:143-149): True, the plan's actions are the final rollout's (inverse-model) actions; False,
+        # the action plan is the best sample itself, uncut -- meaningful when the samples are actions (ActCondGCPImageSimulator).
+        assert horizon is None or horizon >= 1
+        self.horizon, self.use_inferred_actions = horizon, bool(use_inferred_actions)
         self._sim, self._cost, self._sampler = simulator, cost, sampler
         self.n_iters, self.batch_size, self.elite_frac, self.max_seq_len = n_iters, batch_size, elite_frac, max_seq_len
         self.goal_in_cost = goal_in_cost
@@ -610,6 +636,25 @@ class CEMPlanner:
         assert n % world == 0, "candidate population must divide evenly over ranks"
         per = n // world
         return rank * per, per
+
+    def _cap(self, r):
+        """_cap_to_horizon on a padded device rollout: the cost and the logs read the first min(length, horizon) steps"""
+        if self.horizon is not None:
+            r.lengths = r.lengths.clamp(max=self.horizon)
+        return r
+
+    def _cap_list(self, seqs):
+        """_cap_to_horizon (cem_planner.py:151-155) on the host lists of the final rollout"""
+        if self.horizon is None or seqs is None:
+            return seqs
+        return [x[:self.horizon] for x in seqs]
+
+    def _action_plan(self, final_actions, best_sample):
+        """_get_action_plan (cem_planner.py:143-149) for one plan: the final rollout's actions, or the best sample itself (numpy)"""
+        if self.use_inferred_actions:
+            return final_actions
+        b = best_sample.detach().cpu().numpy() if torch.is_tensor(best_sample) else np.asarray(best_sample)
+        return b
 
     def evaluate(self, state, goal_state, samples):
         """costs [n] of all candidates given the WHOLE population: this rank rolls out its slice, one all-gather assembles the vector."""
@@ -626,6 +671,7 @@ class CEMPlanner:
             r = self._sim.rollout_device(state, goal_state, local, self.max_seq_len, decode=self.decode_candidates, **kw)
         else:                                            # any simulator with the reference's interface
             r = self._sim.rollout_device(state, goal_state, local, self.max_seq_len)
+        self._cap(r)
         if hasattr(self._cost, "sequence_cost_device"):
             cost = self._cost.sequence_cost_device(r.latents, r.lengths, r.e_goal if self.goal_in_cost else None)
         else:
@@ -697,7 +743,9 @@ class CEMPlanner:
         if getattr(self._sim, "pred_length", False) and hasattr(self._sampler, "sample_uniform"):
             kw["len_u"] = self._sampler.sample_uniform(1)             # the plan's own length draw, from the rank-shared stream
         final = self._sim.rollout(state, goal_state, best_samples[:1].cpu().numpy(), self.max_seq_len, **kw)
-        actions = final.actions[0] if final.actions is not None else None
+        if self.horizon is not None:
+            final = Outputs({k: self._cap_list(v) for k, v in final.items()})
+        actions = self._action_plan(final.actions[0] if final.actions is not None else None, best_samples[0])
         states = final.get("states")
         if self.verbose:
             vlog.append(final_log_entry(final, goal_state, best_scores, final.latents[0].shape[-1] if self._sim._append_latent else 0))
@@ -707,9 +755,12 @@ class CEMPlanner:
 
     # K tasks per forward: at most this many candidate rows in one scoring forward (HierarchicalCEMPlanner.MAX_ROWS)
     MAX_ROWS = 1000
+    device_plans = True           # plan_batch(device=True) hands the plans over on the device (control.ControlRunner(keep_plans=False))
 
-    def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None):
+    def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None, device=False, latents=True):
         """K tasks planned together: states, goals [K, H, W, 3] env images -> a list of K Outputs with the fields of `plan`.
+        device: the plans stay on the device (`_device_plans`: no decoded final rollout, no host lists; states and goals may be device
+        tensors, which then never visit the host); latents: whether the caller reads the plans' latents (closed-loop acting).
         The K Gaussians mean, std [K, n_steps, dim] live in this call, initialised as `sampler.init()` does; the sampler's own mean / std
         are not touched.  Every iteration is one noise draw [K, n, n_steps, dim] from the sampler's rank-shared generator, one launch
         for the K populations (gcpx_cem_population), the scoring rollout of the K * n rows -- task k's rows with its own start and goal
@@ -738,9 +789,12 @@ class CEMPlanner:
             raise ValueError(f"plan_batch does not shard its populations ({s.n_shards()} sampler shards / ranks): use plan()")
         if s._dtype != torch.float32:
             raise ValueError("plan_batch keeps its distributions in float32")
-        states, goals = np.asarray(states), np.asarray(goals)
+        if not (device and torch.is_tensor(states) and torch.is_tensor(goals)):
+            states, goals = np.asarray(states), np.asarray(goals)
         if states.ndim != 4 or states.shape != goals.shape:
             raise ValueError("plan_batch takes states and goals [K, H, W, 3]")
+        # (a hand-written cost takes its goal on the host, cost_fcn.py's contract: the goal frames, not the start frames, come back once)
+        cost_goals = goals.cpu().numpy() if torch.is_tensor(goals) and not hasattr(self._cost, "sequence_cost_device") else goals
         K, n = states.shape[0], self.batch_size
         n_elite = max(int(n * self.elite_frac), 1)
         max_rows = self.MAX_ROWS if max_rows is None else int(max_rows)
@@ -753,14 +807,18 @@ class CEMPlanner:
         mean = torch.zeros(K, s._n_steps, s._action_dim, device=dev)
         std = s._initial_std * torch.ones(K, s._n_steps, s._action_dim, device=dev)
         rec = Outputs(noise=[], populations=[], scores=[], elite_idx=[], means=[], stds=[], rollouts=[], goal_latents=[], best_samples=None)
-        kept = []
+        kept, task0 = [], [0]
 
         def score(r, chunk_goals):
+            lo = task0[0]                                    # the forwards of an iteration take the tasks in order
+            task0[0] = (lo + len(chunk_goals)) % K
+            self._cap(r)
             if record:
                 kept.append((r.latents.clone(), r.lengths.clone(), r.e_goal.clone()))
             if learned:
                 return self._cost.sequence_cost_device(r.latents, r.lengths, r.e_goal if self.goal_in_cost else None)
-            return self._cost.rollout_cost_rows_device(sim.predictions_device(r), r.lengths, [g[None] for g in chunk_goals], repeat=n)
+            return self._cost.rollout_cost_rows_device(sim.predictions_device(r), r.lengths,
+                                                       [g[None] for g in cost_goals[lo:lo + len(chunk_goals)]], repeat=n)
 
         self.logs, best, elite_scores = [], None, None
         for _ in range(self.n_iters):
@@ -780,14 +838,48 @@ class CEMPlanner:
                 kept.clear()
         rec.best_samples = best
         self.batch_record = rec if record else None
+        if device:
+            return self._device_plans(states, goals, best, elite_scores[:, 0], max_rows, len_u, latents)
         costs = elite_scores[:, 0].cpu().numpy()
         out = []
         for k0, final in zip(range(0, K, max(max_rows, 1)), rollout_chunks(sim, self.max_seq_len, states, goals, best, 1, max_rows, True, len_u)):
+            if self.horizon is not None:
+                final = Outputs({k: self._cap_list(v) for k, v in final.items()})
             st = final.get("states")
             for j in range(len(final.predictions)):
-                out.append(Outputs(predictions=final.predictions[j], actions=final.actions[j] if final.actions is not None else None,
+                out.append(Outputs(predictions=final.predictions[j],
+                                   actions=self._action_plan(final.actions[j] if final.actions is not None else None, best[k0 + j]),
                                    latents=final.latents[j], cost=float(costs[k0 + j]), states=st[j] if st is not None else None))
         return out
+
+    def _device_plans(self, states, goals, best, costs, max_rows, len_u, latents):
+        """plan_batch(device=True): the K plans as device tensors, nothing decoded and nothing copied to the host.
+        Outputs(best [K, n_steps, dim], costs [K], lengths int32 [K] (frames of each plan, the horizon applied), actions [K, A, n_actions]
+        with n_actions [K] valid rows each (the final rollout's inverse-model actions, or the best samples themselves), and latents
+        [K, T, nz_enc] or None).  The final rollout of the K best candidates runs only when something reads it: the caller's `latents`,
+        the inverse-model actions, or a simulator that draws its lengths (whose draws are then consumed as the host path consumes them)."""
+        sim, K, dev = self._sim, best.shape[0], best.device
+        pred_length = bool(getattr(sim, "pred_length", False))
+        lat = act = lens = None
+        if latents or self.use_inferred_actions or pred_length:
+            keep = lambda r, _goals: (r.latents.clone(), r.lengths.clone(), None if r.actions is None else r.actions.clone())
+            parts = rollout_chunks(sim, self.max_seq_len, states, goals, best, 1, max_rows, False, len_u, each=keep, decode_device=False)
+            lat, lens = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+            if parts[0][2] is not None:
+                act = torch.cat([p[2] for p in parts])
+        else:
+            lens = torch.full((K,), self.max_seq_len, dtype=torch.int32, device=dev)
+        # the host contract: one action per frame transition (GCPImageSimulator.rollout: actions[:length - 1]), then frames, latents and
+        # actions alike cut to their first `horizon` entries
+        n_act = (lens - 1).clamp(min=0)
+        if self.horizon is not None:
+            lens, n_act = lens.clamp(max=self.horizon), n_act.clamp(max=self.horizon)
+        if self.use_inferred_actions:
+            if act is None:                                  # no inverse model: an empty action plan (ImageCEMPolicy.get_action)
+                act, n_act = torch.zeros(K, 1, 2, device=dev), torch.zeros_like(lens)
+        else:
+            act, n_act = best, torch.full((K,), best.shape[1], dtype=torch.int32, device=dev)
+        return Outputs(best=best, costs=costs, lengths=lens, actions=act, n_actions=n_act, latents=lat if latents else None)
 
 
 class ImageHierarchicalTreeCEMSampler:
@@ -1006,6 +1098,9 @@ class ImageCEMPolicy:
         self.planner_model, self._cem_planner = model, planner
         self.replan_interval, self.num_max_replans, self.closed_loop_execution = replan_interval, num_max_replans, closed_loop_execution
         self.batch_encode = bool(batch_encode)
+        if closed_loop_execution and not getattr(getattr(model, "_hp", None), "attach_inv_mdl", True):
+            raise ValueError("closed_loop_execution = True needs the model's inverse model (attach_inv_mdl): every action is inferred from "
+                             "the current image and the next planned latent (planner_policy.py:222-227)")
         self.reset()
 
     def reset(self):

@@ -463,6 +463,16 @@ class GCPSequentialModel(GCPTreeModel):
                 self._mlp(plan, "cost_mdl", P["cost_mdl"], [gather(mes, 2), gather(mes, 3)], B, B, out=cost.data_ptr(), ob=0, orow=1)
                 outs["cost_pred"], outs["cost_target"] = cost, self._buf("cost_target", (B,))
         plan.lane = 0
+        if not key.decode:
+            # val_mode(decode=False), the planner's scoring rollout under a learned cost: the recurrence and the latent-space heads above
+            # are the launches of the decoding plan, the decoder and the head are not launched, and `images` is absent from the outputs
+            # (no ground truth and no loss on this path: forward() refuses them).  The plan key holds `decode`: a plan of its own.
+            plan.join([1])
+            outs.update(X=X, PZ=PZ, QZ=QZ, Z=Z, seq_len=seq_len, matched_distr_kernel_order=None, e_g=EG)
+            outs["enc_traj_seq"] = enc_traj
+            plan.rec.update(head_src=None, tin=tin, seq_row_map=None)
+            plan.outs = outs
+            return plan
 
         # ---- decoder over the T-1 predicted latents of every sequence (sequential.py:56) ----
         F = B * (T - 1)
@@ -592,7 +602,7 @@ class GCPSequentialModel(GCPTreeModel):
     def _wrap_outputs(self, o, tin, phase):
         out = Outputs()
         out.end_ind, out.raw = tin["end_ind"], o
-        out.dense_rec = Outputs(images=o["images"], encodings=o["X"][:, 1:], p_z=o["PZ"], q_z=o["QZ"], z=o["Z"])
+        out.dense_rec = Outputs(images=o.get("images"), encodings=o["X"][:, 1:], p_z=o["PZ"], q_z=o["QZ"], z=o["Z"])   # (no images: decode=False)
         if "seq_len_logits" in o:
             out.seq_len_logits = o["seq_len_logits"]
         return out
