@@ -1026,6 +1026,39 @@ int gcpx_resize_assemble_batch(const uint8_t* frames, const int32_t* info, const
                                float* I_g, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states, float* actions,
                                void* stream);
 
+/* The same two assemblies over a split whose frames stay on the device (video-gcp_amd/dataset_resident.py: ResidentStore holds them,
+ *   ResidentLoader._assemble calls these where HostFedLoader._assemble calls gcpx_assemble_batch / gcpx_resize_assemble_batch on a
+ *   freshly uploaded slot).  No frame, state or action bytes are uploaded per batch: a sequence is a window of the store.
+ *   store   uint8, store_bytes of them: every trajectory's frames [n_i][H][W][3] ([n_i][Hs][Ws][3] in the resize form) back to back,
+ *           no padding between trajectories; 16-byte aligned (the plain form with H * W % 4 != 0 takes any alignment);
+ *   states_store f32 [sum n_i][state_dim], actions_store f32 [sum (n_i - 1)][n_actions] (null when the size is 0);
+ *   info    int64 [B][8], 8-byte aligned, per sequence:
+ *             [0] index in the store (in frames) of the window's first frame, [1] n_frames the trajectory has from there on,
+ *             [2] first state row, [3] n_states from there on, [4] first action row, [5] n_actions from there on,
+ *             [6] chop, [7] zero_from | end_ind << 32 (both non-negative and below 2^31);
+ *   lut, pad_in, states_mean / states_den, the tables and every output: as in gcpx_assemble_batch / gcpx_resize_assemble_batch.
+ *   Output frame t reads frame [0] + s of the store, s = min(t + chop, T - 1), when t < zero_from and s < min(n_frames, T), else it
+ *   is lut[0] and nothing is read: the frames behind a short trajectory are another trajectory's and never stand in for padding.
+ *   States and actions read rows [2] + s and [4] + s under the same map (actions: T - 1 steps, s clamped to T - 2).  All addressing
+ *   into the store is 64-bit.  No byte outside [store, store + store_bytes) is read whatever info holds: a window that starts below
+ *   the store or reaches past its last whole frame is padding, and the 16-byte staging loads of the resize form stop at store_bytes.
+ *   The row bases of states and actions are the caller's to keep inside their arrays (a negative base reads nothing).
+ *   Limits (GCPX_ERR_INVALID_ARG otherwise, nothing launched): no null store / info / lut / pad_in / output, store_bytes at least one
+ *   frame, sides in [1, 512]; the resize form has the limits of gcpx_resize_assemble_batch (W % 4 == 0, Hs <= 8 H, Ws <= 8 W, ksx / ksy
+ *   the tap counts of the sizes, no null table). */
+int gcpx_assemble_batch_resident(const uint8_t* store, int64_t store_bytes, const int64_t* info, const float* lut, const float* pad_in,
+                                 const float* states_store, const float* actions_store, const float* states_mean, const float* states_den,
+                                 int32_t B, int32_t T, int32_t H, int32_t W, int32_t state_dim, int32_t n_actions, float* traj_seq,
+                                 float* I_0, float* I_g, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states,
+                                 float* actions, void* stream);
+int gcpx_resize_assemble_batch_resident(const uint8_t* store, int64_t store_bytes, const int64_t* info, const float* lut, const int32_t* kx,
+                                        const int32_t* bx, const int32_t* ky, const int32_t* by, const float* pad_in,
+                                        const float* states_store, const float* actions_store, const float* states_mean,
+                                        const float* states_den, int32_t B, int32_t T, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                                        int32_t ksx, int32_t ksy, int32_t state_dim, int32_t n_actions, float* traj_seq, float* I_0,
+                                        float* I_g, float* pad_mask, int64_t* end_ind, int64_t* start_ind, float* states, float* actions,
+                                        void* stream);
+
 /* The assembly for the nav datasets, whose frames are not recorded images but top-down pictures of the maze drawn from the states
  *   (MazeTopRenderedGlobalSplitVarLenVideoDataset.process_data_dict, /root/reference/gcp/datasets/data_loader.py:299-319, calling
  *   Multiroom3dEnv.render_pos_top_down, gcp/planning/infra/envs/miniworld_env/multiroom3d/multiroom3d_env.py:185-219).  Called by

@@ -41,34 +41,7 @@ __global__ void __launch_bounds__(kThreads) assemble_frames_kernel(const uint8_t
     const float pad = tab[0];
     const int p0 = (blockIdx.y * kThreads + threadIdx.x) * 4;
     if (p0 >= HW) return;
-    if ((HW & 3) == 0) {
-        float4 v[3];
-        if (valid) {
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(src + (size_t)p0 * 3);
-            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];        // RGBR GBRG BRGB
-            v[0] = make_float4(tab[w0 & 255], tab[(w0 >> 24) & 255], tab[(w1 >> 16) & 255], tab[(w2 >> 8) & 255]);
-            v[1] = make_float4(tab[(w0 >> 8) & 255], tab[w1 & 255], tab[(w1 >> 24) & 255], tab[(w2 >> 16) & 255]);
-            v[2] = make_float4(tab[(w0 >> 16) & 255], tab[(w1 >> 8) & 255], tab[w2 & 255], tab[(w2 >> 24) & 255]);
-        } else {
-            v[0] = v[1] = v[2] = make_float4(pad, pad, pad, pad);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            *reinterpret_cast<float4*>(dst + (size_t)c * HW + p0) = v[c];
-            if (d0) *reinterpret_cast<float4*>(d0 + (size_t)c * HW + p0) = v[c];
-            if (dg) *reinterpret_cast<float4*>(dg + (size_t)c * HW + p0) = v[c];
-        }
-    } else {
-        for (int p = p0; p < min(p0 + 4, HW); ++p) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float x = valid ? tab[src[(size_t)p * 3 + c]] : pad;
-                dst[(size_t)c * HW + p] = x;
-                if (d0) d0[(size_t)c * HW + p] = x;
-                if (dg) dg[(size_t)c * HW + p] = x;
-            }
-        }
-    }
+    lut_quad_store(src, valid, tab, pad, HW, p0, dst, d0, dg);
 }
 
 // one workgroup per sequence: pad mask, end / start index, states (standardised) and actions under the same time map as the frames
@@ -146,24 +119,7 @@ __global__ void __launch_bounds__(kThreads) resize_assemble_frames_kernel(
     const int nrows = min(min(max(by[2 * (r0 + nr - 1)] + by[2 * (r0 + nr - 1) + 1], y_lo + 1), Hs) - y_lo, cap);
     const int row_bytes = Ws * 3;
     const long long a0 = (((long long)b * T + s) * Hs + y_lo) * row_bytes;
-    const int shift = (int)(a0 & 15);
-    {
-        const long long abase = a0 - shift;
-        const int nvec = (shift + nrows * row_bytes + 15) >> 4;
-        for (int v = tid; v < nvec; v += kThreads) {
-            const long long g = abase + 16ll * v;
-            uint4 x;
-            if (g + 16 <= total_bytes) {
-                x = *reinterpret_cast<const uint4*>(frames + g);
-            } else {                              // the last bytes of the whole slot: no read past its end
-                uint32_t w[4] = {0, 0, 0, 0};
-                for (int j = 0; j < 16; ++j)
-                    if (g + j < total_bytes) w[j >> 2] |= (uint32_t)frames[g + j] << (8 * (j & 3));
-                x = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            *reinterpret_cast<uint4*>(raw + 16 * v) = x;
-        }
-    }
+    const int shift = stage_bytes(frames, a0, nrows * row_bytes, total_bytes, raw, tid);
     __syncthreads();
     // horizontal pass: hres[r][xx][c] for the nrows staged rows
     resize_rows_any(ksx, raw, shift, hres, skx, sbx, nrows, Ws, W, tid);

@@ -1,6 +1,8 @@
 // The two integer passes of the 8-bit bilinear resampler (Pillow's Image.resize, see video-gcp_amd/dataset.py) as device functions over a
 // band of source rows staged in LDS, and the host-side choice of the band.  Shared by the kernels that resize inside the batch assembly:
-// csrc/batch_assemble.hip (recorded frames) and csrc/topdown_assemble.hip (frames rendered from states), so that both do one arithmetic.
+// csrc/batch_assemble.hip (recorded frames), csrc/batch_assemble_resident.hip (recorded frames kept on the device; it also shares the
+// staging loads and the conversion of frames that need no resize) and csrc/topdown_assemble.hip (frames rendered from states), so that
+// all do one arithmetic.
 #pragma once
 #include <algorithm>
 
@@ -10,6 +12,7 @@ namespace gcpx_resize {
 
 constexpr int kThreads = 256;
 constexpr int kInfo = 8;     // int32 per sequence: n_frames, n_states, n_actions, chop, zero_from, end_ind, -, -
+constexpr int kInfoResident = 8;   // int64 per sequence of the resident forms (csrc/batch_assemble_resident.hip, include/gcpx.h)
 constexpr int kPrecisionBits = 22;            // Pillow's PRECISION_BITS for 8-bit channels
 constexpr int kResizeMaxSide = 512;
 constexpr int kResizeMaxScale = 8;
@@ -98,6 +101,66 @@ __device__ __forceinline__ void resize_rows_any(const int ksx, const uint8_t* __
         case 13: resize_rows<13>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
         case 15: resize_rows<15>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;
         default: resize_rows<17>(raw, shift, hres, skx, sbx, nrows, Ws, W, tid); break;   // 2 * kResizeMaxScale + 1
+    }
+}
+
+// Bytes [a0, a0 + nbytes) of `src` into LDS by 16-byte loads from the 16-byte boundary below a0 (src itself is 16-byte aligned); returns
+// a0 & 15, the offset of byte a0 in `raw`.  `total_bytes` is the size of what src points to: its last bytes are read one by one, nothing
+// at or past its end.
+__device__ __forceinline__ int stage_bytes(const uint8_t* __restrict__ src, const long long a0, const int nbytes,
+                                           const long long total_bytes, uint8_t* __restrict__ raw, const int tid) {
+    const int shift = (int)(a0 & 15);
+    const long long abase = a0 - shift;
+    const int nvec = (shift + nbytes + 15) >> 4;
+    for (int v = tid; v < nvec; v += kThreads) {
+        const long long g = abase + 16ll * v;
+        uint4 x;
+        if (g + 16 <= total_bytes) {
+            x = *reinterpret_cast<const uint4*>(src + g);
+        } else {                              // the last bytes of the whole slot: no read past its end
+            uint32_t w[4] = {0, 0, 0, 0};
+            for (int j = 0; j < 16; ++j)
+                if (g + j < total_bytes) w[j >> 2] |= (uint32_t)src[g + j] << (8 * (j & 3));
+            x = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        *reinterpret_cast<uint4*>(raw + 16 * v) = x;
+    }
+    return shift;
+}
+
+// Pixels [p0, p0 + 4) of one frame stored at the model's size: 12 bytes of `src` (read when `valid`, else the pixel is `pad`) through
+// the table to one float4 of each of the three channel planes of dst (and of d0 / dg when the frame is also I_0 / I_g).  H * W % 4 == 0
+// takes three dword loads (src is then 4-byte aligned), any other size single bytes.
+__device__ __forceinline__ void lut_quad_store(const uint8_t* __restrict__ src, const bool valid, const float* __restrict__ tab,
+                                               const float pad, const int HW, const int p0, float* __restrict__ dst,
+                                               float* __restrict__ d0, float* __restrict__ dg) {
+    if ((HW & 3) == 0) {
+        float4 v[3];
+        if (valid) {
+            const uint32_t* w = reinterpret_cast<const uint32_t*>(src + (size_t)p0 * 3);
+            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];        // RGBR GBRG BRGB
+            v[0] = make_float4(tab[w0 & 255], tab[(w0 >> 24) & 255], tab[(w1 >> 16) & 255], tab[(w2 >> 8) & 255]);
+            v[1] = make_float4(tab[(w0 >> 8) & 255], tab[w1 & 255], tab[(w1 >> 24) & 255], tab[(w2 >> 16) & 255]);
+            v[2] = make_float4(tab[(w0 >> 16) & 255], tab[(w1 >> 8) & 255], tab[w2 & 255], tab[(w2 >> 24) & 255]);
+        } else {
+            v[0] = v[1] = v[2] = make_float4(pad, pad, pad, pad);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            *reinterpret_cast<float4*>(dst + (size_t)c * HW + p0) = v[c];
+            if (d0) *reinterpret_cast<float4*>(d0 + (size_t)c * HW + p0) = v[c];
+            if (dg) *reinterpret_cast<float4*>(dg + (size_t)c * HW + p0) = v[c];
+        }
+    } else {
+        for (int p = p0; p < min(p0 + 4, HW); ++p) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float x = valid ? tab[src[(size_t)p * 3 + c]] : pad;
+                dst[(size_t)c * HW + p] = x;
+                if (d0) d0[(size_t)c * HW + p] = x;
+                if (dg) dg[(size_t)c * HW + p] = x;
+            }
+        }
     }
 }
 

@@ -33,6 +33,9 @@ the crop and the two dots.  Recorded images are neither read nor uploaded: an it
 goal's pixel, and gcpx_topdown_assemble_batch (csrc/topdown_assemble.hip) renders, resizes and converts in the launch that writes the
 model's inputs.  The model gets states[..., :2] (MazeGlobalSplit..., data_loader.py:292-296).
 
+Keeping a whole split on the device and assembling batches from it there, with the same draws and the same bits
+(`train.py --device_dataset 1`), is dataset_resident.py.
+
 Not here: reading `.h5` (h5py), building the top-down picture from textures (nav_gen.py writes an untextured one with a whole nav
 dataset: `python -m video_gcp_amd.gen_nav`), filters other than bilinear.
 """
@@ -291,6 +294,12 @@ class VideoDataset:
                              "resized on the device as Pillow's bilinear Image.resize would")
         raw["images"] = im
         return raw
+
+    def pad_mask(self, index):
+        """the pad mask of item `index` alone (f32 [T_raw]): all that `draw` reads of an item, and its length is the trajectory's
+        (dataset_resident.py sizes its store from these before it reads a frame)"""
+        F = self._cache.get(self.filenames[index // self.traj_per_file])
+        return F[f"traj{index % self.traj_per_file}/pad_mask"].astype(np.float32)
 
     def draw(self, raw, rs):
         """the reference's per-item draws (data_loader.py:144-156,175-211) from RandomState rs, in its order.  Returns the plan:

@@ -269,6 +269,10 @@ SYMBOLS = [
     ("gcpx_assemble_batch", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("gcpx_resize_assemble_batch", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                              vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    ("gcpx_assemble_batch_resident", C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                               vp, vp]),
+    ("gcpx_resize_assemble_batch_resident", C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
+                                                      i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("gcpx_topdown_assemble_batch", C.c_int, [vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                               i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     ("gcpx_panel_compose", C.c_int, [vp, i32, vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, vp, vp]),

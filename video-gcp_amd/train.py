@@ -23,6 +23,11 @@ Frame size: `--resize_frames 1` resizes recorded frames stored at another size t
 assembly, as Pillow's bilinear Image.resize does (dataset.py), for the train, validation and `--metric` test loaders alike.
 Deviation: the reference resizes every item (data_loader.py:213-220); here it defaults to 0, so that a dataset of the wrong size
 stops the run as it did before the option existed.
+Resident data: `--device_dataset 1` uploads every split it reads (train and val, or test under `--metric 1`) once and keeps it on the
+device as uint8; each batch then sends B * (64 + 4 T) bytes of indices and pad masks and is assembled from the store on the device
+(dataset_resident.py), bit-identical to the host-fed batches, also with `--resize_frames 1`.  `--device_dataset_gb G` bounds one split's
+store (default: half of the device's memory); a split that does not fit, or a top-rendered nav dataset, raises.  Every rank of a
+process group holds the whole split.  Defaults to 0, and the trainer then issues no launch, copy or allocation it did not issue before.
 On a nav dataset (Nav9Rooms, Nav25Rooms) the picture logs also hold `regressed_state_topdown` / `action_traj_topdown`, and `--metric 1`
 writes `<path>/metrics/trajectories/it_<step>/trajectories_<b>.png`: the maze with the state trajectories drawn on it (image_log.py).
 
@@ -80,6 +85,10 @@ def get_cmd_args(argv=None):
     p.add_argument("--top_of", default=100, type=int, help="prior samples per sequence of the top-of-N evaluation")
     p.add_argument("--resize_frames", default=0, type=int, help="if 1, frames stored at another size are resized to img_sz on the device "
                    "(bilinear, as the reference's loader always does)")
+    p.add_argument("--device_dataset", default=0, type=int, help="if 1, every split is uploaded once and kept on the device as uint8; "
+                   "batches are assembled from it there (dataset_resident.py). A split that does not fit raises")
+    p.add_argument("--device_dataset_gb", default=None, type=float, help="the most device memory one resident split may take, in GiB "
+                   "(default: half of the device's memory)")
     p.add_argument("--imepoch", default=4, type=int, help="number of times pictures are logged per epoch")
     p.add_argument("--log_images", default=0, type=int, help="if 1, writes prediction panels to <path>/images (the reference's "
                    "default is 1)")
@@ -133,12 +142,18 @@ def val_phase(args):
     return "test" if getattr(args, "metric", False) else "val"
 
 
-def make_loader(data_dir, spec, phase, hp, model, data_opts, n_repeat=1, seed=0, rank=0, world=1, resize=False):
+def make_loader(data_dir, spec, phase, hp, model, data_opts, n_repeat=1, seed=0, rank=0, world=1, resize=False, resident=False,
+                budget_bytes=None):
     """the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, shuffled in the train phase only;
-    `resize`: frames stored at another size are resized to hp.img_sz in the batch assembly (--resize_frames)"""
+    `resize`: frames stored at another size are resized to hp.img_sz in the batch assembly (--resize_frames);
+    `resident`: the split is uploaded once and the batches are assembled from it on the device (--device_dataset, dataset_resident.py;
+    at most `budget_bytes` of it, a top-rendered dataset raises)"""
     from .dataset import HostFedLoader, VideoDataset
-    return HostFedLoader(VideoDataset(data_dir, spec, phase, hp.img_sz, resize=resize, **data_opts), model, hp.batch_size,
-                         n_repeat=n_repeat, seed=seed, rank=rank, world=world)
+    ds = VideoDataset(data_dir, spec, phase, hp.img_sz, resize=resize, **data_opts)
+    if resident:
+        from .dataset_resident import ResidentLoader
+        return ResidentLoader(ds, model, hp.batch_size, n_repeat=n_repeat, seed=seed, rank=rank, world=world, budget_bytes=budget_bytes)
+    return HostFedLoader(ds, model, hp.batch_size, n_repeat=n_repeat, seed=seed, rank=rank, world=world)
 
 
 class SyntheticLoader:
@@ -218,8 +233,11 @@ class ModelTrainer:
         if self.data_dir and (train_loader is None or val_loader is None):
             # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val / test unshuffled
             reps = int(conf.get("epoch_cycles_train", 1))
+            gb = getattr(args, "device_dataset_gb", None)
             mk = lambda phase: make_loader(self.data_dir, spec, phase, hp, self.model, data_opts, n_repeat=reps, seed=seed, rank=self.rank,
-                                           world=max(self.world, 1), resize=bool(getattr(args, "resize_frames", 0)))
+                                           world=max(self.world, 1), resize=bool(getattr(args, "resize_frames", 0)),
+                                           resident=bool(getattr(args, "device_dataset", 0)),
+                                           budget_bytes=None if gb is None else int(gb * 2 ** 30))
             train_loader = train_loader or mk("train")
             val_loader = val_loader or mk(val_phase(args))
         if not args.feed_random_data and train_loader is None:
