@@ -160,6 +160,18 @@ int gcpx_conv4x4s2_grid(void);
    x: dev NCHW [F][3][Hin][Win]; out NHWC [F][Hin/2][Win/2][Cout] with bias + out_act applied. */
 int gcpx_conv4x4s2_image(const float* x, const float* wpk, const float* bias, float* out,
                          int32_t F, int32_t Hin, int32_t Win, int32_t Cout, int32_t out_act, void* stream);
+/* the first TWO encoder blocks of 64 x 64 frames in one launch (csrc/conv_enc_fused.hip): gcpx_conv4x4s2_image(x, w0pk, bias0, ., a->F,
+   64, 64, 16, act0) followed by gcpx_conv4x4s2(a) on its result, the 32 x 32 x 16 map between them kept in LDS.  `a` describes the
+   second block as for gcpx_conv4x4s2 (16 -> 32 channels, 32 x 32 -> 16 x 16, split-f16 weights in the PLAIN layout, one source without
+   affine or activation); a->src[0].ptr is not read.  a0_out: dev [F][32][32][16] or NULL — the map is stored there as well, for the
+   callers that have another reader of it.  a->out, a0_out and rows 0 .. F - 1 of a->stats_partial (row f = frame f; may be NULL) hold the
+   bits the two launches leave; rows F .. gcpx_conv4x4s2_grid() - 1 are zeroed.  Nothing at or beyond frame F is read or written.
+   _supported: 1 when (a, image size) is such a problem (and F <= gcpx_conv4x4s2_grid()), else 0 — the caller then makes the two
+   launches; _grid: workgroups of a launch with at least that many frames (a workgroup loops over frames blockIdx, blockIdx + grid, ...) */
+int gcpx_conv4x4s2_image_fused(const float* x, const float* w0pk, const float* bias0, int32_t act0, float* a0_out,
+                               const gcpx_conv_args* a, void* stream);
+int gcpx_conv4x4s2_image_fused_supported(const gcpx_conv_args* a, int32_t Himg, int32_t Wimg);
+int gcpx_conv4x4s2_image_fused_grid(void);
 
 /* BatchNorm statistics -> (scale, shift):  scale = gamma * rsqrt(var + eps), shift = beta - mean * scale.
    partial: dev [n_partial][2][pitch] (fp32 partial sums written by the conv / gemm epilogues); column n

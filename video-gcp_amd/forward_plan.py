@@ -20,32 +20,62 @@ class ForwardPlanMixin:
     # ------------------------------------------------------------------------------------------------
     # plan: encoder
     # ------------------------------------------------------------------------------------------------
-    def _plan_encoder(self, plan, tag, x_ptr, F, out_ptr, out_ob, out_orow, out_rpb):
+    def _plan_encoder(self, plan, tag, x_ptr, F, out_ptr, out_ob, out_orow, out_rpb, skips_read=True):
         """Encoder over F NCHW frames at x_ptr; writes the nz_enc latent of frame r=(b,j) to
-        out_ptr + b*out_ob + j*out_orow.  Returns the skip sources {module index: (tensor, C, scale, shift, act)}."""
+        out_ptr + b*out_ob + j*out_orow.  Returns the skip sources {module index: (tensor, C, scale, shift, act)}; a caller that
+        drops them says skips_read=False."""
         hp, P, lib = self._hp, self.pk, self.lib
         G = lib.gcpx_conv4x4s2_grid()
         S = hp.img_sz
         skip_idx = encoder_skip_layers(hp)
         skips = {}
-        a0 = self._buf(f"{tag}.a0", (F, S // 2, S // 2, hp.ngf))
-        enc_rec = dict(F=F, x_ptr=x_ptr, a0=a0, r={}, out=(out_ptr, out_ob, out_orow, out_rpb))
+        enc_rec = dict(F=F, x_ptr=x_ptr, a0=None, r={}, out=(out_ptr, out_ob, out_orow, out_rpb))
         plan.rec[f"enc:{tag}"] = enc_rec
-        plan.add(f"enc.input:{tag}", lib.gcpx_conv4x4s2_image, x_ptr, P["enc.input.w"].data_ptr(),
-                 P["enc.input.b"].data_ptr(), a0.data_ptr(), F, S, S, hp.ngf, rt.ACT_LRELU)
-        prev = (a0.data_ptr(), hp.ngf, 1, None, None, rt.ACT_NONE)
-        if 0 in skip_idx:
+        # The first layer has no norm, so the first two layers run as ONE launch where the library has that form (64 x 64 frames, split-f16
+        # 16 -> 32 block: csrc/conv_enc_fused.hip) and the 32 x 32 x 16 map `a0` between them stays in LDS.  It is stored to HBM as well
+        # only where it has a reader: skip 0 of the decoder, and the backward pass of a training step (the layer's dgrad and wgrad).
+        # Without one the buffer (84 MB for a c2 trajectory batch) is not allocated.  Per pass, by the keep rule of
+        # profiles/enc_fused.txt: the passes whose skips nobody reads (trajectory, I_g) take the fused launch; the I_0 pass keeps the two
+        # launches (its 16 one-frame workgroups of 139 KB LDS cannot share a CU with the trajectory pass's and wait for it: mean 44 us
+        # against 31 us).  GCPX_NO_ENC_FUSE=1: two launches everywhere; GCPX_ENC_FUSE_ALL=1: the I_0 pass fused too (measurement)
+        a0_read = (0 in skip_idx and skips_read) or self.save_for_backward
+        name1, _, cout1, _ = self._enc_layers[1]
+        r1 = self._buf(f"{tag}.r1", (F, S // 4, S // 4, cout1))
+        st1 = self._buf(f"{tag}.st1", (G, 2, cout1)) if self.training else None
+        a1 = self._conv_args([(None, hp.ngf, 1, None, None, rt.ACT_NONE)], F, S // 2, S // 2, S // 4, S // 4, cout1, cout1,
+                             P[f"enc.{name1}.w"], P[f"enc.{name1}.b"], r1, stats=st1)
+        self._set_split(a1, f"enc.{name1}")
+        plan.keep.append(a1)
+        fused = (os.environ.get("GCPX_NO_ENC_FUSE") is None and (not skips_read or os.environ.get("GCPX_ENC_FUSE_ALL") is not None) and
+                 bool(lib.gcpx_conv4x4s2_image_fused_supported(C.byref(a1), S, S)))
+        a0 = self._buf(f"{tag}.a0", (F, S // 2, S // 2, hp.ngf)) if a0_read or not fused else None
+        enc_rec["a0"] = a0
+        if a0 is not None:
+            a1.src[0].ptr = a0.data_ptr()
+        if fused:
+            plan.add(f"enc.input+{name1}:{tag}", lib.gcpx_conv4x4s2_image_fused, x_ptr, P["enc.input.w"].data_ptr(),
+                     P["enc.input.b"].data_ptr(), rt.ACT_LRELU, a0.data_ptr() if a0 is not None else None, C.byref(a1))
+        else:
+            plan.add(f"enc.input:{tag}", lib.gcpx_conv4x4s2_image, x_ptr, P["enc.input.w"].data_ptr(),
+                     P["enc.input.b"].data_ptr(), a0.data_ptr(), F, S, S, hp.ngf, rt.ACT_LRELU)
+        prev = None
+        if 0 in skip_idx and a0 is not None:
             skips[0] = (a0, hp.ngf, None, None, rt.ACT_NONE)
         res = S // 2
         for li, (name, cin, cout, norm) in enumerate(self._enc_layers[1:], start=1):
-            r = self._buf(f"{tag}.r{li}", (F, res // 2, res // 2, cout))
+            if li == 1:
+                r, stats = r1, st1
+                if not fused:
+                    plan.add(f"enc.{name}:{tag}", lib.gcpx_conv4x4s2, C.byref(a1))
+            else:
+                r = self._buf(f"{tag}.r{li}", (F, res // 2, res // 2, cout))
+                stats = self._buf(f"{tag}.st{li}", (G, 2, cout)) if self.training else None
+                a = self._conv_args([prev], F, res, res, res // 2, res // 2, cout, cout, P[f"enc.{name}.w"],
+                                    P[f"enc.{name}.b"], r, stats=stats)
+                self._set_split(a, f"enc.{name}")
+                plan.keep.append(a)
+                plan.add(f"enc.{name}:{tag}", lib.gcpx_conv4x4s2, C.byref(a))
             enc_rec["r"][li] = r
-            stats = self._buf(f"{tag}.st{li}", (G, 2, cout)) if self.training else None
-            a = self._conv_args([prev], F, res, res, res // 2, res // 2, cout, cout, P[f"enc.{name}.w"],
-                                P[f"enc.{name}.b"], r, stats=stats)
-            self._set_split(a, f"enc.{name}")
-            plan.keep.append(a)
-            plan.add(f"enc.{name}:{tag}", lib.gcpx_conv4x4s2, C.byref(a))
             res //= 2
             scale, shift = self._bn(plan, f"{tag}.bn{li}", f"encoder.net.{name}.norm", cout, stats, G, cout,
                                     F * res * res)
@@ -250,7 +280,7 @@ class ForwardPlanMixin:
             plan.lane = 0
             if has_traj:
                 enc_traj = self._buf("enc_traj", (B * T, nz))
-                self._plan_encoder(plan, "traj", tin["traj_seq"].data_ptr(), B * T, enc_traj.data_ptr(), T * nz, nz, T)
+                self._plan_encoder(plan, "traj", tin["traj_seq"].data_ptr(), B * T, enc_traj.data_ptr(), T * nz, nz, T, skips_read=False)
                 if hp.seq_enc == "none":                       # build_temporal_inf_encoder -> Identity (base_gcp.py:131-132)
                     inf_enc = enc_traj
                 else:
@@ -299,7 +329,7 @@ class ForwardPlanMixin:
             rows = hp.input_nc * hp.img_sz
             plan.add("path_cost", lib.gcpx_path_cost, tin["traj_seq"].data_ptr(), tin["cost_start_idx"].data_ptr(),
                      tin["cost_end_idx"].data_ptr(), B, T, rows, hp.img_sz, self._buf("cost_partial", (B, rows)).data_ptr(), gt.data_ptr())
-        self._plan_encoder(plan, "Ig", tin["I_g"].data_ptr(), B, _addr(E, 2 ** L * nz), PS * nz, 0, 1)
+        self._plan_encoder(plan, "Ig", tin["I_g"].data_ptr(), B, _addr(E, 2 ** L * nz), PS * nz, 0, 1, skips_read=False)
         outs = {}
         e0 = lambda: self._rowsrc(_addr(E), PS * nz, 0, nz)
         eg = lambda: self._rowsrc(_addr(E, 2 ** L * nz), PS * nz, 0, nz)

@@ -221,11 +221,11 @@ class GCPSequentialModel(GCPTreeModel):
             plan.add("path_cost", lib.gcpx_path_cost, tin["traj_seq"].data_ptr(), tin["cost_start_idx"].data_ptr(),
                      tin["cost_end_idx"].data_ptr(), B, T, rows, hp.img_sz, self._buf("cost_partial", (B, rows)).data_ptr(),
                      self._buf("cost_target", (B,)).data_ptr())
-        self._plan_encoder(plan, "Ig", tin["I_g"].data_ptr(), B, _addr(EG), nz, 0, 1)
+        self._plan_encoder(plan, "Ig", tin["I_g"].data_ptr(), B, _addr(EG), nz, 0, 1, skips_read=False)
         plan.lane = 0
         if has_traj:
             enc_traj = self._buf("enc_traj", (B * T, nz))
-            self._plan_encoder(plan, "traj", tin["traj_seq"].data_ptr(), B * T, enc_traj.data_ptr(), T * nz, nz, T)
+            self._plan_encoder(plan, "traj", tin["traj_seq"].data_ptr(), B * T, enc_traj.data_ptr(), T * nz, nz, T, skips_read=False)
         plan.join([1, 2])
         outs = {}
         e0 = lambda: self._rowsrc(_addr(X), T * nz, 0, nz)
