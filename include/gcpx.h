@@ -160,6 +160,23 @@ int gcpx_conv4x4s2_grid(void);
    x: dev NCHW [F][3][Hin][Win]; out NHWC [F][Hin/2][Win/2][Cout] with bias + out_act applied. */
 int gcpx_conv4x4s2_image(const float* x, const float* wpk, const float* bias, float* out,
                          int32_t F, int32_t Hin, int32_t Win, int32_t Cout, int32_t out_act, void* stream);
+/* Dispatch queries: what gcpx_conv4x4s2 / gcpx_conv4x4s2_image would launch for these arguments, without launching anything (no HIP
+   call besides the one-time read of the device's CU count; 256 CUs are assumed without a device).  Each entry point takes form,
+   frames per workgroup and grid from the same host function as its query, under the same environment switches, read on every call:
+   GCPX_ENC_NOSPLIT (ignore split weights), GCPX_ENC_DIRECT (no LDS form), GCPX_ENC_FPB (frames per workgroup of the LDS and split
+   forms, when in 1 .. the shape's maximum), GCPX_ENC_IMAGE_DIRECT.  Both return the argument errors the launch would.
+   out4 = {form, fpb, grid, nblk}: fpb = frames a workgroup of the LDS / split form stages (0 for the direct kernels); nblk = the blocks
+   the grid's workgroups loop over: groups of fpb frames, or for the direct kernels groups of 16 (Cout 32) / 8 pixel groups of 16
+   output pixels.  out2 = {form, grid}. */
+typedef enum gcpx_enc_form_id {
+    GCPX_ENC_FORM_DIRECT = 0,        /* conv4x4s2_kernel: operands straight from global memory, any frame shape */
+    GCPX_ENC_FORM_LDS = 1,           /* conv4x4s2_lds_kernel: exact f32, fpb frames staged in LDS */
+    GCPX_ENC_FORM_SPLIT = 2,         /* conv4x4s2_split_kernel (csrc/conv_enc_split.hip): split-f16, fpb frames staged in LDS */
+    GCPX_ENC_FORM_IMAGE_DIRECT = 3,  /* conv4x4s2_image_kernel */
+    GCPX_ENC_FORM_IMAGE_LDS = 4      /* conv4x4s2_image_lds_kernel: 32 x 32 and 64 x 64 images, one frame per workgroup and trip */
+} gcpx_enc_form_id;
+int gcpx_conv4x4s2_form(const gcpx_conv_args* a, int32_t* out4);
+int gcpx_conv4x4s2_image_form(int32_t F, int32_t Hin, int32_t Win, int32_t* out2);
 /* the first TWO encoder blocks of 64 x 64 frames in one launch (csrc/conv_enc_fused.hip): gcpx_conv4x4s2_image(x, w0pk, bias0, ., a->F,
    64, 64, 16, act0) followed by gcpx_conv4x4s2(a) on its result, the 32 x 32 x 16 map between them kept in LDS.  `a` describes the
    second block as for gcpx_conv4x4s2 (16 -> 32 channels, 32 x 32 -> 16 x 16, split-f16 weights in the PLAIN layout, one source without

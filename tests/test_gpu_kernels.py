@@ -1330,7 +1330,9 @@ def test_conv4x4s2(env, Hin, cin, cout, Fr, split):
 @pytest.mark.parametrize("Hin,cin,cout,Fr", [(32, 16, 32, 3), (16, 32, 64, 9), (8, 64, 128, 19)])
 def test_conv4x4s2_split_error_vs_float64(env, case, Hin, cin, cout, Fr):
     """The split-f16 encoder blocks against float64, next to the exact f32 kernel (one power-of-two scale per staged block of
-    frames): data of magnitude 1e-3, 300, with an outlier, all zero; frame counts that leave the last block partly empty."""
+    frames): data of magnitude 1e-3, 300, with an outlier, all zero.  At these frame counts the launch stages ONE frame per block, so
+    no block is partly empty and no scale spans frames: blocks of several frames, a last block short of frames and frames of
+    different magnitude under one scale are held to float64 in tests/test_gpu_enc_forms.py."""
     rt, pk, lib, dev = env
     torch.manual_seed(17)
     amp = {"unit": 1.0, "tiny": 1e-3, "large": 300.0, "outlier": 1.0, "zero": 0.0}[case]

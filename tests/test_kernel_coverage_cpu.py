@@ -12,7 +12,10 @@ gradient-clip kernels in tests/test_gpu_optim_kernels.py (tests/optim_refs.py, p
 point needs a direct test or an INFRASTRUCTURE reason.
 Being called is no cover for an entry point that dispatches to many device bodies: the exact row GEMM behind gcpx_gemm (28 gemm_tile
 bodies, csrc/gemm_tile.h) has every one of them asserted through gcpx_gemm_form and held to float64 in tests/test_gpu_gemm_forms.py
-(tests/gemm_refs.py, pinned by tests/test_gemm_refs_cpu.py)."""
+(tests/gemm_refs.py, pinned by tests/test_gemm_refs_cpu.py); the encoder convs behind gcpx_conv4x4s2 and gcpx_conv4x4s2_image (three
+direct, five LDS, five split-f16 and three image bodies, csrc/conv_enc.hip and csrc/conv_enc_split.hip, the LDS and split ones at every
+frames-per-block choice that changes a workgroup's work) are asserted through gcpx_conv4x4s2_form / gcpx_conv4x4s2_image_form and held
+to float64 in tests/test_gpu_enc_forms.py (tests/enc_refs.py, pinned by tests/test_enc_refs_cpu.py)."""
 import glob
 import os
 import re
@@ -23,6 +26,7 @@ INFRASTRUCTURE = {
     "gcpx_version": "ABI version query (checked by build())",
     "gcpx_conv_grid": "grid-size query",
     "gcpx_gemm_form": "dispatch query",
+    "gcpx_conv4x4s2_form": "dispatch query", "gcpx_conv4x4s2_image_form": "dispatch query",
     "gcpx_graph_begin": "hipGraph capture", "gcpx_graph_end": "hipGraph capture", "gcpx_graph_launch": "hipGraph replay",
     "gcpx_graph_destroy": "hipGraph handle",
     "gcpx_stream_create": "stream handle", "gcpx_stream_create_priority": "stream handle", "gcpx_stream_destroy": "stream handle",

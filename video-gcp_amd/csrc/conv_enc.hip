@@ -11,7 +11,8 @@
 
 #include <cstdlib>
 
-int gcpx_launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int cus);     // conv_enc_split.hip
+int gcpx_enc_split_fpb(const gcpx_conv_args* a, int cus);                                                             // conv_enc_split.hip
+int gcpx_launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int fpb, int nblk, int grid);     // conv_enc_split.hip
 
 namespace {
 
@@ -335,10 +336,30 @@ __global__ void __launch_bounds__(256) conv4x4s2_lds_kernel(const gcpx_conv_args
     }
 }
 
+// frames per workgroup: the most loaded CU should carry as few frames as possible (workgroups are dealt round-robin to the
+// CUs); among equals the larger group (weight fragments are fetched once per group; measured at 1280 frames: 4x4 layer
+// 62 us with 5 frames / workgroup, 97 us with 1).  FPB: the most the shape's kernel stages.
+int enc_lds_fpb(const int F, const int FPB, const int cus) {
+    int fpb = 1;
+    long best = -1;
+    for (int c = 1; c <= FPB; ++c) {
+        const int nb = (F + c - 1) / c;
+        const long cost = (long)((nb + cus - 1) / cus) * c;
+        if (best < 0 || cost <= best) { best = cost; fpb = c; }
+    }
+    if (const char* e = getenv("GCPX_ENC_FPB")) { const int v = atoi(e); if (v >= 1 && v <= FPB) fpb = v; }
+    return fpb;
+}
+
+// launches the plan of enc_form (below)
 template <int CIN, int COUT, int HIN, int FPB, int WP, int WC, bool ZP>
-int launch_enc_lds(const gcpx_conv_args* a, hipStream_t stream) {
+int launch_enc_lds(const gcpx_conv_args* a, hipStream_t stream, const int fpb, const int nblk, const int grid, const int nrows) {
     using Cfg = EncLdsCfg<CIN, COUT, HIN, FPB, WP, WC, ZP>;
     auto kern = conv4x4s2_lds_kernel<CIN, COUT, HIN, FPB, WP, WC, ZP>;
+    if (fpb < 1 || fpb > FPB || nblk != (a->F + fpb - 1) / fpb || grid < 1 || grid > nblk) {
+        gcpx_set_error("conv4x4s2 (LDS): plan fpb=%d nblk=%d grid=%d does not fit F=%d, at most %d frames", fpb, nblk, grid, a->F, FPB);
+        return GCPX_ERR_INVALID_ARG;
+    }
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
@@ -348,22 +369,6 @@ int launch_enc_lds(const gcpx_conv_args* a, hipStream_t stream) {
         }
         attr_set = true;
     }
-    // frames per workgroup: the most loaded CU should carry as few frames as possible (workgroups are dealt round-robin to the
-    // CUs); among equals the larger group (weight fragments are fetched once per group; measured at 1280 frames: 4x4 layer
-    // 62 us with 5 frames / workgroup, 97 us with 1)
-    const int cus = gcpx_conv_grid() / 2;
-    int fpb = 1;
-    long best = -1;
-    for (int c = 1; c <= FPB; ++c) {
-        const int nb = (a->F + c - 1) / c;
-        const long cost = (long)((nb + cus - 1) / cus) * c;
-        if (best < 0 || cost <= best) { best = cost; fpb = c; }
-    }
-    if (const char* e = getenv("GCPX_ENC_FPB")) { const int v = atoi(e); if (v >= 1 && v <= FPB) fpb = v; }
-    const int nblk = (a->F + fpb - 1) / fpb;
-    // stats_partial has gcpx_conv4x4s2_grid() rows and all of them must be written: the launched workgroups zero the others
-    const int nrows = gcpx_conv4x4s2_grid();
-    const int grid = nblk < nrows ? nblk : nrows;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), Cfg::lds_bytes(fpb), stream, *a, nblk, nrows, fpb);
     return GCPX_OK;
 }
@@ -516,7 +521,7 @@ __global__ void __launch_bounds__(256) conv4x4s2_image_lds_kernel(const float* _
 }
 
 template <int HIN>
-int launch_image_lds(const float* x, const float* wpk, const float* bias, float* out, int F, int out_act, hipStream_t stream) {
+int launch_image_lds(const float* x, const float* wpk, const float* bias, float* out, int F, int out_act, int grid, hipStream_t stream) {
     using Cfg = ImgLdsCfg<HIN>;
     auto kern = conv4x4s2_image_lds_kernel<HIN>;
     static bool attr_set = false;
@@ -528,64 +533,151 @@ int launch_image_lds(const float* x, const float* wpk, const float* bias, float*
         }
         attr_set = true;
     }
-    int grid = gcpx_conv_grid() / 2 * (160 * 1024 / Cfg::LDS_BYTES);      // as many workgroups as fit the CUs' LDS at once
-    if (grid > F) grid = F;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), Cfg::LDS_BYTES, stream, x, wpk, bias, out, F, out_act);
     return GCPX_OK;
 }
 
-}  // namespace
+// The shapes with an LDS form, once: X(CIN, COUT, HIN, FPB, WP, WC, ZP)
+#define GCPX_ENC_LDS_SHAPES(X)        \
+    X(16, 32, 32, 1, 4, 1, false)     \
+    X(32, 64, 16, 4, 4, 1, true)      \
+    X(64, 128, 8, 8, 1, 4, true)      \
+    X(16, 32, 16, 4, 4, 1, true)      \
+    X(32, 64, 8, 16, 4, 1, true)
 
-extern "C" int gcpx_conv4x4s2_grid(void) { return gcpx_conv_grid() * 4; }
-
-extern "C" int gcpx_conv4x4s2(const gcpx_conv_args* a, void* stream_) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+int conv4x4s2_check(const gcpx_conv_args* a) {
     GCPX_CHECK_ARG(a != nullptr, "null args");
     GCPX_CHECK_ARG(a->nsrc == 1 && a->src[0].frame_div == 1, "encoder conv takes one per-frame source");
     GCPX_CHECK_ARG(a->Cin == a->src[0].C && a->Cin % 16 == 0, "Cin must equal src C and be a multiple of 16");
     GCPX_CHECK_ARG(a->Hout * 2 == a->Hin && a->Wout * 2 == a->Win, "Hout must be Hin/2");
     GCPX_CHECK_ARG(a->Cout % 16 == 0 && a->out_pitch == a->Cout, "Cout % 16 and dense output");
     GCPX_CHECK_ARG(a->wpk && a->bias && a->out && a->F > 0, "null pointer / F <= 0");
-    const int npix = a->F * a->Hout * a->Wout;
-    const int ngroups = (npix + 15) / 16;
-    // these kernels hide their global-load latency with occupancy, not with LDS staging: 8 workgroups per CU
-    int grid = gcpx_conv4x4s2_grid();
-    const int CT = a->Cout / 16;
-    const int per_blk = (CT == 2) ? 16 : 8;      // pixel groups per workgroup (WP * PRW)
-    const int nblk = (ngroups + per_blk - 1) / per_blk;
-    // stats_partial has gcpx_conv4x4s2_grid() rows: all of them must be written
-    if (!a->stats_partial && grid > nblk) grid = nblk;
+    return GCPX_OK;
+}
+
+// What gcpx_conv4x4s2 launches for checked arguments: the ONE place where form, frames per workgroup and grid are decided —
+// gcpx_conv4x4s2 launches this plan and gcpx_conv4x4s2_form reports it, under the same environment switches (read on every call).
+// Order: the split-f16 form when the caller supplies PLAIN split weights and the shape has one; else the LDS form of the five square
+// shapes; else the direct kernel of the output width.
+struct EncForm { int form, fpb, grid, nblk; };
+
+int enc_form(const gcpx_conv_args* a, EncForm* f) {
+    const int nrows = gcpx_conv4x4s2_grid();              // rows of stats_partial
+    const int cus = gcpx_conv_grid() / 2;
     if (a->wpk_split && a->split_layout == GCPX_SPLIT_PLAIN && !getenv("GCPX_ENC_NOSPLIT")) {
-        const int st = gcpx_launch_enc_split(a, stream, gcpx_conv4x4s2_grid(), gcpx_conv_grid() / 2);
-        if (st < 0) return st;
-        if (st == 0) {
-            GCPX_CHECK_LAUNCH();
+        const int fpb = gcpx_enc_split_fpb(a, cus);
+        if (fpb > 0) {
+            const int nblk = (a->F + fpb - 1) / fpb;
+            *f = EncForm{GCPX_ENC_FORM_SPLIT, fpb, nblk < nrows ? nblk : nrows, nblk};
             return GCPX_OK;
         }
     }
     if (a->Hin == a->Win && !getenv("GCPX_ENC_DIRECT")) {
-        int st = 1;
-        if (a->Cin == 16 && a->Cout == 32 && a->Hin == 32) st = launch_enc_lds<16, 32, 32, 1, 4, 1, false>(a, stream);
-        else if (a->Cin == 32 && a->Cout == 64 && a->Hin == 16) st = launch_enc_lds<32, 64, 16, 4, 4, 1, true>(a, stream);
-        else if (a->Cin == 64 && a->Cout == 128 && a->Hin == 8) st = launch_enc_lds<64, 128, 8, 8, 1, 4, true>(a, stream);
-        else if (a->Cin == 16 && a->Cout == 32 && a->Hin == 16) st = launch_enc_lds<16, 32, 16, 4, 4, 1, true>(a, stream);
-        else if (a->Cin == 32 && a->Cout == 64 && a->Hin == 8) st = launch_enc_lds<32, 64, 8, 16, 4, 1, true>(a, stream);
-        if (st <= 0) {
-            if (st < 0) return st;
-            GCPX_CHECK_LAUNCH();
+        int FPB = 0;
+#define X(CIN, COUT, HIN, FPB_, WP, WC, ZP) if (a->Cin == CIN && a->Cout == COUT && a->Hin == HIN) FPB = FPB_;
+        GCPX_ENC_LDS_SHAPES(X)
+#undef X
+        if (FPB > 0) {
+            const int fpb = enc_lds_fpb(a->F, FPB, cus);
+            const int nblk = (a->F + fpb - 1) / fpb;
+            // stats_partial has gcpx_conv4x4s2_grid() rows and all of them must be written: the launched workgroups zero the others
+            *f = EncForm{GCPX_ENC_FORM_LDS, fpb, nblk < nrows ? nblk : nrows, nblk};
             return GCPX_OK;
         }
     }
-    switch (CT) {
-        case 2: hipLaunchKernelGGL((conv4x4s2_kernel<1, 8, 2, 2>), dim3(grid), dim3(256), 0, stream, *a, ngroups); break;
-        // the deeper layers have few output pixels (20k at 4x4): keep every wavefront on all channels of 32 pixels so
-        // that there are enough workgroups; measured 105 / 121 us vs 191 / 199 us with channel-split wavefronts (c2)
-        case 4: hipLaunchKernelGGL((conv4x4s2_kernel<4, 2, 1, 4>), dim3(grid), dim3(256), 0, stream, *a, ngroups); break;
-        case 8: hipLaunchKernelGGL((conv4x4s2_kernel<8, 2, 1, 4>), dim3(grid), dim3(256), 0, stream, *a, ngroups); break;
-        default:
-            gcpx_set_error("conv4x4s2: unsupported Cout=%d", a->Cout);
-            return GCPX_ERR_UNSUPPORTED;
+    const int CT = a->Cout / 16;
+    if (CT != 2 && CT != 4 && CT != 8) {
+        gcpx_set_error("conv4x4s2: unsupported Cout=%d", a->Cout);
+        return GCPX_ERR_UNSUPPORTED;
     }
+    const int npix = a->F * a->Hout * a->Wout;
+    const int ngroups = (npix + 15) / 16;
+    const int per_blk = (CT == 2) ? 16 : 8;      // pixel groups per workgroup (WP * PRW)
+    const int nblk = (ngroups + per_blk - 1) / per_blk;
+    // these kernels hide their global-load latency with occupancy, not with LDS staging: 8 workgroups per CU
+    int grid = nrows;
+    // stats_partial has gcpx_conv4x4s2_grid() rows: all of them must be written
+    if (!a->stats_partial && grid > nblk) grid = nblk;
+    *f = EncForm{GCPX_ENC_FORM_DIRECT, 0, grid, nblk};
+    return GCPX_OK;
+}
+
+int conv4x4s2_image_check(int32_t F, int32_t Hin, int32_t Win) {
+    GCPX_CHECK_ARG(F > 0, "null pointer / F <= 0");
+    GCPX_CHECK_ARG(Hin % 2 == 0 && Win % 2 == 0, "even input size");
+    GCPX_CHECK_ARG((long long)F * 3 * Hin * Win * 4 < (1LL << 31), "image tensor must stay below 2 GiB (32-bit buffer offsets)");
+    return GCPX_OK;
+}
+
+// the same for gcpx_conv4x4s2_image / gcpx_conv4x4s2_image_form
+struct ImageForm { int form, grid; };
+
+ImageForm image_form(const int F, const int Hin, const int Win) {
+    if (Hin == Win && (Hin == 64 || Hin == 32) && !getenv("GCPX_ENC_IMAGE_DIRECT")) {
+        const int lds_bytes = Hin == 64 ? ImgLdsCfg<64>::LDS_BYTES : ImgLdsCfg<32>::LDS_BYTES;
+        int grid = gcpx_conv_grid() / 2 * (160 * 1024 / lds_bytes);      // as many workgroups as fit the CUs' LDS at once
+        if (grid > F) grid = F;
+        return ImageForm{GCPX_ENC_FORM_IMAGE_LDS, grid};
+    }
+    const int npix = F * (Hin / 2) * (Win / 2);
+    const int nblk = ((npix + 15) / 16 + 7) / 8;
+    int grid = gcpx_conv_grid() * 2;
+    if (grid > nblk) grid = nblk;
+    return ImageForm{GCPX_ENC_FORM_IMAGE_DIRECT, grid};
+}
+
+}  // namespace
+
+extern "C" int gcpx_conv4x4s2_grid(void) { return gcpx_conv_grid() * 4; }
+
+extern "C" int gcpx_conv4x4s2_form(const gcpx_conv_args* a, int32_t* out4) {
+    int st = conv4x4s2_check(a);
+    if (st != GCPX_OK) return st;
+    GCPX_CHECK_ARG(out4 != nullptr, "out4 is NULL");
+    EncForm f;
+    st = enc_form(a, &f);
+    if (st != GCPX_OK) return st;
+    out4[0] = f.form; out4[1] = f.fpb; out4[2] = f.grid; out4[3] = f.nblk;
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_conv4x4s2_image_form(int32_t F, int32_t Hin, int32_t Win, int32_t* out2) {
+    const int st = conv4x4s2_image_check(F, Hin, Win);
+    if (st != GCPX_OK) return st;
+    GCPX_CHECK_ARG(out2 != nullptr, "out2 is NULL");
+    const ImageForm f = image_form(F, Hin, Win);
+    out2[0] = f.form; out2[1] = f.grid;
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_conv4x4s2(const gcpx_conv_args* a, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    int st = conv4x4s2_check(a);
+    if (st != GCPX_OK) return st;
+    EncForm f;
+    st = enc_form(a, &f);
+    if (st != GCPX_OK) return st;
+    const int nrows = gcpx_conv4x4s2_grid();
+    if (f.form == GCPX_ENC_FORM_SPLIT) {
+        st = gcpx_launch_enc_split(a, stream, nrows, f.fpb, f.nblk, f.grid);
+    } else if (f.form == GCPX_ENC_FORM_LDS) {
+        st = GCPX_ERR_UNSUPPORTED;
+#define X(CIN, COUT, HIN, FPB, WP, WC, ZP)                              \
+        if (a->Cin == CIN && a->Cout == COUT && a->Hin == HIN)          \
+            st = launch_enc_lds<CIN, COUT, HIN, FPB, WP, WC, ZP>(a, stream, f.fpb, f.nblk, f.grid, nrows);
+        GCPX_ENC_LDS_SHAPES(X)
+#undef X
+    } else {
+        const int ngroups = (a->F * a->Hout * a->Wout + 15) / 16;
+        switch (a->Cout / 16) {
+            case 2: hipLaunchKernelGGL((conv4x4s2_kernel<1, 8, 2, 2>), dim3(f.grid), dim3(256), 0, stream, *a, ngroups); break;
+            // the deeper layers have few output pixels (20k at 4x4): keep every wavefront on all channels of 32 pixels so
+            // that there are enough workgroups; measured 105 / 121 us vs 191 / 199 us with channel-split wavefronts (c2)
+            case 4: hipLaunchKernelGGL((conv4x4s2_kernel<4, 2, 1, 4>), dim3(f.grid), dim3(256), 0, stream, *a, ngroups); break;
+            default: hipLaunchKernelGGL((conv4x4s2_kernel<8, 2, 1, 4>), dim3(f.grid), dim3(256), 0, stream, *a, ngroups); break;
+        }
+    }
+    if (st != GCPX_OK) return st;
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }
@@ -595,20 +687,17 @@ extern "C" int gcpx_conv4x4s2_image(const float* x, const float* wpk, const floa
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     GCPX_CHECK_ARG(x && wpk && bias && out && F > 0, "null pointer / F <= 0");
     GCPX_CHECK_ARG(Cout == 16, "first encoder layer: Cout must be 16 (ngf)");
-    GCPX_CHECK_ARG(Hin % 2 == 0 && Win % 2 == 0, "even input size");
-    GCPX_CHECK_ARG((long long)F * 3 * Hin * Win * 4 < (1LL << 31), "image tensor must stay below 2 GiB (32-bit buffer offsets)");
-    if (Hin == Win && (Hin == 64 || Hin == 32) && !getenv("GCPX_ENC_IMAGE_DIRECT")) {
-        const int st = Hin == 64 ? launch_image_lds<64>(x, wpk, bias, out, F, out_act, stream)
-                                 : launch_image_lds<32>(x, wpk, bias, out, F, out_act, stream);
+    const int chk = conv4x4s2_image_check(F, Hin, Win);
+    if (chk != GCPX_OK) return chk;
+    const ImageForm f = image_form(F, Hin, Win);
+    if (f.form == GCPX_ENC_FORM_IMAGE_LDS) {
+        const int st = Hin == 64 ? launch_image_lds<64>(x, wpk, bias, out, F, out_act, f.grid, stream)
+                                 : launch_image_lds<32>(x, wpk, bias, out, F, out_act, f.grid, stream);
         if (st != GCPX_OK) return st;
         GCPX_CHECK_LAUNCH();
         return GCPX_OK;
     }
-    const int npix = F * (Hin / 2) * (Win / 2);
-    const int nblk = ((npix + 15) / 16 + 7) / 8;
-    int grid = gcpx_conv_grid() * 2;
-    if (grid > nblk) grid = nblk;
-    hipLaunchKernelGGL(conv4x4s2_image_kernel<1>, dim3(grid), dim3(256), 0, stream, x, wpk, bias, out, F, Hin, Win,
+    hipLaunchKernelGGL(conv4x4s2_image_kernel<1>, dim3(f.grid), dim3(256), 0, stream, x, wpk, bias, out, F, Hin, Win,
                        Cout, out_act);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;

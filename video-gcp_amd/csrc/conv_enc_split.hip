@@ -256,10 +256,35 @@ __global__ void __launch_bounds__(256) conv4x4s2_split_kernel(const gcpx_conv_ar
     }
 }
 
+// Frames per workgroup.  With the MFMA time cut by 5x these layers are bound by the bytes a CU pulls (~10 B / cycle): per block
+// its frames in and out plus the filter bank once per wavefront COLUMN (wavefronts of a column read the same fragments at the
+// same time: they meet in L1) — so the cost of a choice is rounds x (frames x frame bytes + bank bytes), rounds = blocks on the
+// most loaded CU.  (The f32 kernel's rule — fewest frames on the most loaded CU — picks one-frame blocks for 1280 frames of
+// 16 x 16 x 32 and re-reads the 128 KB bank 5 times per CU: 76 us; three-frame blocks: see DESIGN.md.)
 template <int CIN, int COUT, int HIN, int FPB, int WP, int WC, bool ZP>
-int launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int cus) {
+int enc_split_fpb(const int F, const int cus) {
+    using Cfg = EncSplitCfg<CIN, COUT, HIN, FPB, WP, WC, ZP>;
+    int fpb = 1;
+    double best = -1.0;
+    const double frame_bytes = 4.0 * (HIN * HIN * CIN + Cfg::HOUT * Cfg::HOUT * COUT);
+    const double bank_bytes = 4.0 * 16 * CIN * COUT * (4 / WC) / WP;
+    for (int c = 1; c <= FPB; ++c) {
+        const int nb = (F + c - 1) / c;
+        const double cost = (double)((nb + cus - 1) / cus) * (c * frame_bytes + bank_bytes);
+        if (best < 0 || cost <= best) { best = cost; fpb = c; }
+    }
+    if (const char* e = getenv("GCPX_ENC_FPB")) { const int v = atoi(e); if (v >= 1 && v <= FPB) fpb = v; }
+    return fpb;
+}
+
+template <int CIN, int COUT, int HIN, int FPB, int WP, int WC, bool ZP>
+int launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int fpb, int nblk, int grid) {
     using Cfg = EncSplitCfg<CIN, COUT, HIN, FPB, WP, WC, ZP>;
     auto kern = conv4x4s2_split_kernel<CIN, COUT, HIN, FPB, WP, WC, ZP>;
+    if (fpb < 1 || fpb > FPB || nblk != (a->F + fpb - 1) / fpb || grid < 1 || grid > nblk) {
+        gcpx_set_error("conv4x4s2 (split): plan fpb=%d nblk=%d grid=%d does not fit F=%d, at most %d frames", fpb, nblk, grid, a->F, FPB);
+        return GCPX_ERR_INVALID_ARG;
+    }
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
@@ -269,36 +294,38 @@ int launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int
         }
         attr_set = true;
     }
-    // Frames per workgroup.  With the MFMA time cut by 5x these layers are bound by the bytes a CU pulls (~10 B / cycle): per block
-    // its frames in and out plus the filter bank once per wavefront COLUMN (wavefronts of a column read the same fragments at the
-    // same time: they meet in L1) — so the cost of a choice is rounds x (frames x frame bytes + bank bytes), rounds = blocks on the
-    // most loaded CU.  (The f32 kernel's rule — fewest frames on the most loaded CU — picks one-frame blocks for 1280 frames of
-    // 16 x 16 x 32 and re-reads the 128 KB bank 5 times per CU: 76 us; three-frame blocks: see DESIGN.md.)
-    int fpb = 1;
-    double best = -1.0;
-    const double frame_bytes = 4.0 * (HIN * HIN * CIN + Cfg::HOUT * Cfg::HOUT * COUT);
-    const double bank_bytes = 4.0 * 16 * CIN * COUT * (4 / WC) / WP;
-    for (int c = 1; c <= FPB; ++c) {
-        const int nb = (a->F + c - 1) / c;
-        const double cost = (double)((nb + cus - 1) / cus) * (c * frame_bytes + bank_bytes);
-        if (best < 0 || cost <= best) { best = cost; fpb = c; }
-    }
-    if (const char* e = getenv("GCPX_ENC_FPB")) { const int v = atoi(e); if (v >= 1 && v <= FPB) fpb = v; }
-    const int nblk = (a->F + fpb - 1) / fpb;
-    const int grid = nblk < nrows ? nblk : nrows;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), Cfg::lds_bytes(fpb), stream, *a, nblk, nrows, fpb);
     return GCPX_OK;
 }
 
 }  // namespace
 
-// Called by gcpx_conv4x4s2 (conv_enc.hip) when the caller supplies split-f16 weights: 0 = launched, 1 = no split form for this shape
-int gcpx_launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int cus) {
-    if (a->Hin != a->Win) return 1;
-    if (a->Cin == 16 && a->Cout == 32 && a->Hin == 32) return launch_enc_split<16, 32, 32, 1, 2, 2, false>(a, stream, nrows, cus);
-    if (a->Cin == 32 && a->Cout == 64 && a->Hin == 16) return launch_enc_split<32, 64, 16, 4, 1, 4, true>(a, stream, nrows, cus);
-    if (a->Cin == 64 && a->Cout == 128 && a->Hin == 8) return launch_enc_split<64, 128, 8, 8, 1, 4, true>(a, stream, nrows, cus);
-    if (a->Cin == 16 && a->Cout == 32 && a->Hin == 16) return launch_enc_split<16, 32, 16, 4, 2, 2, true>(a, stream, nrows, cus);
-    if (a->Cin == 32 && a->Cout == 64 && a->Hin == 8) return launch_enc_split<32, 64, 8, 16, 1, 4, true>(a, stream, nrows, cus);
-    return 1;
+// The shapes with a split form, once: X(CIN, COUT, HIN, FPB, WP, WC, ZP)
+#define GCPX_ENC_SPLIT_SHAPES(X)      \
+    X(16, 32, 32, 1, 2, 2, false)     \
+    X(32, 64, 16, 4, 1, 4, true)      \
+    X(64, 128, 8, 8, 1, 4, true)      \
+    X(16, 32, 16, 4, 2, 2, true)      \
+    X(32, 64, 8, 16, 1, 4, true)
+
+// Frames per workgroup the split form takes for this problem on `cus` CUs (GCPX_ENC_FPB read on every call); 0 = no split form for
+// this shape.  enc_form (conv_enc.hip) asks it for the dispatch query and for the launch alike.
+int gcpx_enc_split_fpb(const gcpx_conv_args* a, int cus) {
+    if (a->Hin != a->Win) return 0;
+#define X(CIN, COUT, HIN, FPB, WP, WC, ZP) \
+    if (a->Cin == CIN && a->Cout == COUT && a->Hin == HIN) return enc_split_fpb<CIN, COUT, HIN, FPB, WP, WC, ZP>(a->F, cus);
+    GCPX_ENC_SPLIT_SHAPES(X)
+#undef X
+    return 0;
+}
+
+// Called by gcpx_conv4x4s2 (conv_enc.hip) with the plan of enc_form when that is the split form
+int gcpx_launch_enc_split(const gcpx_conv_args* a, hipStream_t stream, int nrows, int fpb, int nblk, int grid) {
+#define X(CIN, COUT, HIN, FPB, WP, WC, ZP) \
+    if (a->Hin == a->Win && a->Cin == CIN && a->Cout == COUT && a->Hin == HIN) \
+        return launch_enc_split<CIN, COUT, HIN, FPB, WP, WC, ZP>(a, stream, nrows, fpb, nblk, grid);
+    GCPX_ENC_SPLIT_SHAPES(X)
+#undef X
+    gcpx_set_error("conv4x4s2 (split): no split form for %d -> %d at %d x %d", a->Cin, a->Cout, a->Hin, a->Win);
+    return GCPX_ERR_UNSUPPORTED;
 }

@@ -14,6 +14,7 @@ HEAD_RAW, HEAD_DLM_MEAN, HEAD_DLM_BOTH, HEAD_TANH_NCHW, HEAD_DLM_NLL, HEAD_DLM_N
 SPLIT_PLAIN, SPLIT_ROWFOLD, SPLIT_HEAD32, SPLIT_ROWFOLD16, SPLIT_LOWRES = 0, 1, 2, 3, 4
 EPI_NONE, EPI_LRELU, EPI_LSTM, EPI_GAUSS_SAMPLE = 0, 1, 2, 3
 GEMM_FORM_TILE, GEMM_FORM_SPLIT_K, GEMM_FORM_SPLIT_F16, GEMM_FORM_PLANES = 0, 1, 2, 3
+ENC_FORM_DIRECT, ENC_FORM_LDS, ENC_FORM_SPLIT, ENC_FORM_IMAGE_DIRECT, ENC_FORM_IMAGE_LDS = 0, 1, 2, 3, 4
 MLP_PLAIN, MLP_GAUSS, MLP_TANH = 0, 1, 2
 
 vp = C.c_void_p
@@ -145,6 +146,8 @@ SYMBOLS = [
     ("gcpx_conv4x4s2", C.c_int, [C.POINTER(ConvArgs), vp]),
     ("gcpx_conv4x4s2_grid", C.c_int, []),
     ("gcpx_conv4x4s2_image", C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    ("gcpx_conv4x4s2_form", C.c_int, [C.POINTER(ConvArgs), vp]),
+    ("gcpx_conv4x4s2_image_form", C.c_int, [i32, i32, i32, vp]),
     ("gcpx_conv4x4s2_image_fused", C.c_int, [vp, vp, vp, i32, vp, C.POINTER(ConvArgs), vp]),
     ("gcpx_conv4x4s2_image_fused_supported", C.c_int, [C.POINTER(ConvArgs), i32, i32]),
     ("gcpx_conv4x4s2_image_fused_grid", C.c_int, []),
