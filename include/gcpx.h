@@ -797,6 +797,19 @@ int gcpx_wgrad_image4x4s2(const float* da, const float* add, const float* r, con
    values gcpx_dlm_nll writes — the training step evaluates loss and gradient in ONE pass over the 2.3 GB of parameters */
 int gcpx_dlm_nll_bwd(const float* params, const float* target, const float* row_weight, float scale, float* dparams, float* colsum,
                      float* nll_out, int32_t rows, int32_t npix, int32_t pitch, int32_t n_mix, void* stream);
+/* The same for the gaussian head, whose likelihood is taken of mu = tanh(y) (GCPX_HEAD_TANH_NCHW): mu, target NCHW [rows][C][npix],
+   log_sigma one device scalar (decoder.log_sigma).  dy [rows][npix][pitch] = d (scale * row_weight[row] * NLL) / d y, the head's
+   PRE-tanh output, in the pixel-record layout the head's weight / data gradient launches read: slot c < C =
+   scale * w_row * (mu - x) * exp(-2 log_sigma) * (1 - mu^2), slots C .. pitch-1 = 0; rows with weight 0 are zero-filled
+   (row_weight NULL: every weight 1).  colsum (optional): [rows][pitch] per-row sums of dy over the pixels (the head's bias gradient,
+   summed over rows by gcpx_colsum).  nll_out (optional): [rows] what gcpx_gauss_nll reports, for rows of weight 0 too.
+   dls_rows [rows]: scale * w_row * sum over the row of (1 - ((x - mu) * exp(-log_sigma))^2), the rows' contributions to
+   d total / d log_sigma (sum them with gcpx_reduce_partials).  All sums in a fixed order, no atomics.
+   Shape contract: 1 <= C <= 4 and C <= pitch; pitch % 4 == 0, pitch <= 256; npix % 64 == 0; npix * pitch < 2^31.  Anything else
+   returns GCPX_ERR_INVALID_ARG and launches nothing. */
+int gcpx_gauss_nll_bwd(const float* mu, const float* target, const float* row_weight, const float* log_sigma, float scale, float* dy,
+                       float* colsum, float* nll_out, float* dls_rows, int32_t rows, int32_t C, int32_t npix, int32_t pitch,
+                       void* stream);
 /* d total / d logits of the length CE, existence BCE and state L2 heads (same arguments as gcpx_loss_combine);
    dlen [B][ceil16(T)] (pad columns zero), dexist [B*N][16] (column 0), dstate [B*T][16] (columns < state_dim); NULL outputs are skipped */
 int gcpx_loss_heads_bwd(const gcpx_loss_args* a, float* dlen, float* dexist, float* dstate, void* stream);

@@ -40,7 +40,7 @@ class BackwardStagesMixin:
         F, rpb = dec["F"], dec["rpb"]
         ngf = hp.ngf
         perm32 = buf("bw.dlm_perm", (pitch,), torch.int32)
-        perm32.copy_(m._dlm_perm.to(torch.int32))
+        perm32.copy_(torch.as_tensor(self._head_slot_map(), dtype=torch.int32))
         # output head: weight gradient over the frames that carry a loss gradient, data gradient to every node frame.
         # balanced: the matched frames (row b*T+t of dMD <- node matched to frame t); adaptive: every node frame
         all_frames = hp.adaptive and maps is None
@@ -55,8 +55,9 @@ class BackwardStagesMixin:
             row_map = buf("bw.f2n_abs", (B, T), torch.int32)
             plan.add("bw.f2n_abs", lib.gcpx_index_offset, o["frame2node"].data_ptr(), row_map.data_ptr(), B, T, N)
         hs = rec["head_src"]                                   # (pointer, channels, frame divisor, scale, shift, activation)
+        # (the 16-slot gaussian head has no `_src` form at 16 input channels: it takes the general path below)
         if (self.fuse_stage and m.split_f16 and self.split_wgrad and ngf == 16 and hs[2] == 1 and hs[5] == rt.ACT_LRELU and
-                hs[3] is not None and (S in (8, 16) or S % 32 == 0)):
+                hs[3] is not None and (S in (8, 16) or S % 32 == 0) and pitch > 16):
             # the split-f16 kernel reads the last block's raw output at the rows' frames and applies BatchNorm affine + LeakyReLU on load
             head_bias_fused = bool(rec.get("head_grad_fused")) and pitch == 112
             self._wgrad_conv3(plan, "dec.head", dMD.data_ptr(), pitch, None, R, S, S, ngf, hslots, self.g("decoder.gen_head.conv.weight"),
@@ -83,6 +84,11 @@ class BackwardStagesMixin:
             # bias: per-frame column sums come out of the loss-gradient kernel
             self._colsum(plan, "dec.head", buf("bw.dMD.colsum", (R, pitch)).data_ptr(), pitch, R, pitch,
                          self.g("decoder.gen_head.conv.bias"), n_map=perm32)
+        if hp.decoder_distribution == "gaussian":
+            # d total / d log_sigma: the rows' shares came out of the forward's gcpx_gauss_nll_bwd; summed in a fixed order into the
+            # gradient vector with the other side-lane work, which is issued behind the wait for the cleared vector below
+            self._side(plan, "bw.creduce:dec.log_sigma", lib.gcpx_reduce_partials, buf("bw.dls_rows", (R,)).data_ptr(), R, 1, 1,
+                       self.g("decoder.log_sigma"), 1)
         # (the weight gradients queued above go out behind the data gradients: forked in front of them they cost 0.25 ms on the critical lane)
         dA = buf("bw.dA.head", (F, S, S, ngf))
         a = m._conv_args([(dMD.data_ptr(), pitch, 1, None, None, rt.ACT_NONE)], F, S, S, S, S, ngf, ngf, self.bk["dec.head.wT"],

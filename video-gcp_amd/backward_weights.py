@@ -128,6 +128,22 @@ class BackwardWeightsMixin:
         m._gsplit_live = bool(descs)
         m._repack_gsplit(torch.cuda.current_stream(m.device).cuda_stream, None)
 
+    def _head_slot_map(self):
+        """kernel slot of the head's output -> canonical channel of decoder.gen_head (-1: an empty slot): the mixture head's channel order
+        (packing.dlm_channel_perm), the identity over the input_nc leading slots of the gaussian head's 16"""
+        m, hp = self.m, self.m._hp
+        if hp.decoder_distribution == "discrete_logistic_mixture":
+            return pk.dlm_channel_perm(hp.n_mixtures)
+        return [c if c < hp.input_nc else -1 for c in range(m._head_pitch)]
+
+    def _pack_head_T(self, hw):
+        """data gradient of the output head = 3x3 conv with the flipped, transposed weight [100 | 3, 16, 3, 3]; its inputs are the
+        kernel slots of the gradient rows (empty slots: zero weights)"""
+        perm = torch.as_tensor(self._head_slot_map(), device=hw.device)
+        wk = torch.zeros((len(perm),) + tuple(hw.shape[1:]), dtype=hw.dtype, device=hw.device)
+        wk[perm >= 0] = hw[perm[perm >= 0]]
+        return pk.pack_conv3x3(wk.flip(2, 3).transpose(0, 1).contiguous(), 16)
+
     def _pack_backward(self, sd):
         m, hp = self.m, self.m._hp
         nz, nv, H = hp.nz_enc, hp.nz_vae, hp.nz_mid_lstm
@@ -150,11 +166,7 @@ class BackwardWeightsMixin:
                 # (the f32 twin of the 32-channel launches of _decoder_backward: what the launch falls back to if its split form does not fit)
                 for h in range(cin // 32):
                     X[f"dec.{name}.wTq{h}"] = pk.pack_conv3x3(wT[32 * h:32 * (h + 1)], 16)
-        hw = sd["decoder.gen_head.conv.weight"]                              # [100, 16, 3, 3]; inputs of the dgrad = kernel slots
-        perm = torch.as_tensor(pk.dlm_channel_perm(hp.n_mixtures), device=hw.device)
-        wk = torch.zeros((len(perm),) + tuple(hw.shape[1:]), dtype=hw.dtype, device=hw.device)
-        wk[perm >= 0] = hw[perm[perm >= 0]]
-        X["dec.head.wT"] = pk.pack_conv3x3(wk.flip(2, 3).transpose(0, 1).contiguous(), 16)
+        X["dec.head.wT"] = self._pack_head_T(sd["decoder.gen_head.conv.weight"])
         for nm in (["input"] + [f"pyramid-{i}" for i in range(hp.conv_inf_enc_layers)] + ["head"]) if hp.seq_enc == "conv" else []:
             w = sd[f"inf_encoder.net.{nm}.conv.weight"]                     # [co, ci, 3] -> [n = ci][k = (tap, co)]
             X[f"seq.{nm}.wT"] = pk.pack_gemm(w.permute(1, 2, 0).reshape(w.shape[1], -1))

@@ -120,6 +120,82 @@ __global__ void __launch_bounds__(256) gauss_nll_kernel(const float* __restrict_
     if (threadIdx.x == 0) nll_out[row] = red[0];
 }
 
+// gaussian decoder, training forward: the likelihood of gauss_nll_kernel AND the gradient of scale * w_row * NLL w.r.t. the head's
+// pre-tanh output (mu = tanh(y): d mu / d y = 1 - mu^2) in one pass, one frame per workgroup.  The gradient leaves in the layout the
+// head's weight / data gradient launches read: pixel records of `pitch` floats, slots >= C zero.  A wavefront owns 64 pixels per trip:
+// lane l loads pixel l of every plane (coalesced), the gradients of a pixel travel to the lanes that store its record through
+// __shfl, and store j of the trip writes float4 j*64 + lane of the tile: 1 KiB of contiguous bytes per store instruction (the
+// record's leading float4 from the pixel's lane, zeros behind it) — no lane writes a whole record at a record's stride.
+// Sums (deterministic): a lane adds its pixels in trip order, the wavefront combines by a butterfly, the four wavefronts in order.
+__device__ __forceinline__ float wave64_sum(float v) {
+    v += __shfl_xor(v, 32);
+    v += __shfl_xor(v, 16);
+    return row16_sum(v);
+}
+
+__global__ void __launch_bounds__(256) gauss_nll_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ target,
+                                                            const float* __restrict__ row_weight, const float* __restrict__ log_sigma,
+                                                            const float scale, float* __restrict__ dy, float* __restrict__ colsum,
+                                                            float* __restrict__ nll_out, float* __restrict__ dls_rows, const int C,
+                                                            const int npix, const int pitch) {
+    __shared__ float red[4][6];
+    const int row = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int P4 = pitch >> 2;
+    const float ls = log_sigma[0];
+    const float inv = expf(-ls);
+    const float w = row_weight ? row_weight[row] : 1.f;
+    const bool live = w != 0.f;
+    const float k = scale * w * expf(-2.f * ls);
+    const float* mrow = mu + (size_t)row * C * npix;
+    const float* trow = target + (size_t)row * C * npix;
+    float4* drow = reinterpret_cast<float4*>(dy + (size_t)row * npix * pitch);
+    float nll = 0.f, dls = 0.f, cs[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live || nll_out != nullptr) {
+        for (int p0 = wave * 64; p0 < npix; p0 += 256) {
+            float g[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c < C) {
+                    const float m = mrow[(size_t)c * npix + p0 + lane], x = trow[(size_t)c * npix + p0 + lane];
+                    const float d = (x - m) * inv;
+                    nll += 0.5f * d * d + ls + 0.9189385332f;
+                    dls += fmaf(-d, d, 1.f);
+                    g[c] = k * (m - x) * fmaf(-m, m, 1.f);      // (saturated tanh: exactly 0)
+                    cs[c] += g[c];
+                }
+            }
+            if (live) {
+                float4* tile = drow + (size_t)p0 * P4;
+                for (int j = 0; j < P4; ++j) {
+                    const int i = j * 64 + lane, src = i / P4;
+                    float4 v = make_float4(__shfl(g[0], src), __shfl(g[1], src), __shfl(g[2], src), __shfl(g[3], src));
+                    if (i % P4 != 0) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    tile[i] = v;
+                }
+            }
+        }
+    }
+    if (!live)      // a row without weight: the buffer is reused between calls, nothing of an earlier one may stay
+        for (int i = tid; i < npix * P4; i += 256) drow[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    nll = wave64_sum(nll);
+    dls = wave64_sum(dls);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) cs[c] = wave64_sum(cs[c]);
+    if (lane == 0) {
+        red[wave][0] = nll; red[wave][1] = dls;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) red[wave][2 + c] = cs[c];
+    }
+    __syncthreads();
+    const auto total = [&](int i) { return (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]); };
+    if (tid == 0) {
+        if (nll_out) nll_out[row] = total(0);
+        dls_rows[row] = live ? scale * w * total(1) : 0.f;
+    }
+    if (colsum && tid < pitch) colsum[(size_t)row * pitch + tid] = (live && tid < C) ? total(2 + tid) : 0.f;
+}
+
 // analytic KL(q || p) of diagonal Gaussians, clamped below at free_nats per dimension, summed per batch element
 // one 1024-thread workgroup per sequence (deterministic sum), four dimensions per thread and trip: the 256-thread scalar
 // version took 39 - 76 us at the serial tail of the forward with B workgroups on the chip
@@ -330,6 +406,21 @@ extern "C" int gcpx_gauss_nll(const float* mu, const float* target, const float*
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     GCPX_CHECK_ARG(mu && target && log_sigma && nll_out && rows > 0 && nelem > 0, "null pointer / bad sizes");
     hipLaunchKernelGGL(gauss_nll_kernel, dim3(rows), dim3(256), 0, stream, mu, target, log_sigma, nll_out, nelem);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_gauss_nll_bwd(const float* mu, const float* target, const float* row_weight, const float* log_sigma, float scale,
+                                  float* dy, float* colsum, float* nll_out, float* dls_rows, int32_t rows, int32_t C, int32_t npix,
+                                  int32_t pitch, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(mu && target && log_sigma && dy && dls_rows && rows > 0, "null pointer / rows <= 0");
+    GCPX_CHECK_ARG(C >= 1 && C <= 4 && C <= pitch, "1 <= C <= 4 channels (one float4 of gradient per pixel record), C <= pitch");
+    GCPX_CHECK_ARG(pitch % 4 == 0 && pitch <= 256, "pitch must be a multiple of 4, at most 256");
+    GCPX_CHECK_ARG(npix > 0 && npix % 64 == 0, "pixels per frame must be a multiple of 64");
+    GCPX_CHECK_ARG((long long)npix * pitch < (1ll << 31), "npix * pitch must stay below 2^31");
+    hipLaunchKernelGGL(gauss_nll_bwd_kernel, dim3(rows), dim3(256), 0, stream, mu, target, row_weight, log_sigma, scale, dy, colsum,
+                       nll_out, dls_rows, C, npix, pitch);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

@@ -741,6 +741,18 @@ class ForwardPlanMixin:
                 else:
                     plan.add("loss.dlm_nll", lib.gcpx_dlm_nll, matched_distr.data_ptr(), tin["traj_seq"].data_ptr(),
                              tin["pad_mask"].data_ptr(), nll_bt.data_ptr(), B * T, S * S, self._head_pitch, hp.n_mixtures)
+            elif self.save_for_backward:
+                # training step, gaussian head: loss and its gradient w.r.t. the head's pre-tanh output of the matched frames in one
+                # pass, as above; the rows' shares of d total / d log_sigma wait in bw.dls_rows for the backward plan (which clears
+                # the gradient vector first)
+                dMD = self._buf("bw.dMD", (B * T, S, S, self._head_pitch))
+                div = float(T * hp.input_nc * S * S)
+                plan.add("loss.gauss_nll+bwd", lib.gcpx_gauss_nll_bwd, outs["soft_matched_estimates"].data_ptr(),
+                         tin["traj_seq"].data_ptr(), tin["pad_mask"].data_ptr(), self.sd["decoder.log_sigma"].data_ptr(),
+                         C.c_float(hp.dense_img_rec_weight / (B * div)), dMD.data_ptr(),
+                         self._buf("bw.dMD.colsum", (B * T, self._head_pitch)).data_ptr(), nll_bt.data_ptr(),
+                         self._buf("bw.dls_rows", (B * T,)).data_ptr(), B * T, hp.input_nc, S * S, self._head_pitch)
+                plan.rec["nll_bwd_fused"] = True
             else:
                 plan.add("loss.gauss_nll", lib.gcpx_gauss_nll, outs["soft_matched_estimates"].data_ptr(),
                          tin["traj_seq"].data_ptr(), self.sd["decoder.log_sigma"].data_ptr(), nll_bt.data_ptr(), B * T,

@@ -217,6 +217,7 @@ SYMBOLS = [
     ("gcpx_col2im4x4s2", C.c_int, [vp, vp, i32, i32, i32, i32, vp]),
     ("gcpx_im2col_image", C.c_int, [vp, vp, i32, i32, i32, vp]),
     ("gcpx_dlm_nll_bwd", C.c_int, [vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]),
+    ("gcpx_gauss_nll_bwd", C.c_int, [vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     ("gcpx_loss_heads_bwd", C.c_int, [C.POINTER(LossArgs), vp, vp, vp, vp]),
     ("gcpx_image_metrics", C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     ("gcpx_topn_accumulate", C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, i64,

@@ -544,6 +544,18 @@ class GCPSequentialModel(GCPTreeModel):
             elif dlm:
                 plan.add("loss.dlm_nll", lib.gcpx_dlm_nll, matched.data_ptr(), tin["traj_seq"].data_ptr(), tin["w0"].data_ptr(),
                          nll_bt.data_ptr(), B * T, S * S, self._head_pitch, hp.n_mixtures)
+            elif self.save_for_backward:
+                # training step, gaussian head: loss and its gradient w.r.t. the head's pre-tanh output in one pass (see
+                # GCPTreeModel._build_plan).  Rows (b, 0) compare I_0 with itself, weigh 0 and come out zero-filled; decoded frame
+                # (b, t) is row b*T + t + 1
+                row_map = self._buf("seq.row_map", (F,), torch.int32)
+                row_map.copy_((torch.arange(B)[:, None] * T + torch.arange(1, T)[None]).reshape(-1).to(torch.int32))
+                dMD = self._buf("bw.dMD", (B * T, S, S, self._head_pitch))
+                plan.add("loss.gauss_nll+bwd", lib.gcpx_gauss_nll_bwd, images.data_ptr(), tin["traj_seq"].data_ptr(), tin["w0"].data_ptr(),
+                         self.sd["decoder.log_sigma"].data_ptr(), C.c_float(hp.dense_img_rec_weight / (B * float(T * row))),
+                         dMD.data_ptr(), self._buf("bw.dMD.colsum", (B * T, self._head_pitch)).data_ptr(), nll_bt.data_ptr(),
+                         self._buf("bw.dls_rows", (B * T,)).data_ptr(), B * T, hp.input_nc, S * S, self._head_pitch)
+                plan.rec["nll_bwd_fused"] = True
             else:
                 # rows (b, 0) compare I_0 with itself-as-target and carry weight 0 in the combine below
                 plan.add("loss.gauss_nll", lib.gcpx_gauss_nll, images.data_ptr(), tin["traj_seq"].data_ptr(),

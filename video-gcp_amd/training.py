@@ -57,7 +57,10 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self.optimizer, self.momentum, self.gradient_clip = optimizer, float(momentum), gradient_clip
         self._clip_state_dirty, self._clip_part = True, None      # the clip coefficient slot of the optimizer state / its scratch
         hp = model._hp
-        assert hp.decoder_distribution == "discrete_logistic_mixture", "training path implements the DLM head"
+        if hp.decoder_distribution == "gaussian" and hp.adaptive:
+            # (the averaging criterion's image gradient would have to go through tanh instead of through the mixture mean)
+            raise ValueError("training the adaptive (matching_type='dtw_image') model with decoder_distribution='gaussian' is not built: "
+                             "its backward takes the image gradient through the mixture mean of the discrete_logistic_mixture head")
         if hp.attentive_inference:
             assert hp.n_attention_heads == 1, "attention backward is built for one head (hyperparameters.py:24 default)"
         self.m = model

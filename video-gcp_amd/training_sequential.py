@@ -60,11 +60,7 @@ class SequentialTrainStep(GCPTrainStep):
             wT = sd[f"decoder.net.{name}.conv.weight"].flip(2, 3).transpose(0, 1).contiguous()
             for h in range((wT.shape[0] + 63) // 64):
                 X[f"dec.{name}.wT{h}"] = pk.pack_conv3x3(wT[64 * h:64 * (h + 1)], 16)
-        hw = sd["decoder.gen_head.conv.weight"]
-        perm = torch.as_tensor(pk.dlm_channel_perm(hp.n_mixtures), device=hw.device)
-        wk = torch.zeros((len(perm),) + tuple(hw.shape[1:]), dtype=hw.dtype, device=hw.device)
-        wk[perm >= 0] = hw[perm[perm >= 0]]
-        X["dec.head.wT"] = pk.pack_conv3x3(wk.flip(2, 3).transpose(0, 1).contiguous(), 16)
+        X["dec.head.wT"] = self._pack_head_T(sd["decoder.gen_head.conv.weight"])
         if hp.regress_length:
             X["length_pred"] = self._pack_predictor_T(sd, "length_pred.p", [(0, 2 * nz)])
         if hp.attach_state_regressor:
