@@ -1069,7 +1069,7 @@ int gcpx_resize_assemble_batch(const uint8_t* frames, const int32_t* info, const
                                void* stream);
 
 /* The same two assemblies over a split whose frames stay on the device (video-gcp_amd/dataset_resident.py: ResidentStore holds them,
- *   ResidentLoader._assemble calls these where HostFedLoader._assemble calls gcpx_assemble_batch / gcpx_resize_assemble_batch on a
+ *   ResidentLoader._launch calls these where HostFedLoader._launch calls gcpx_assemble_batch / gcpx_resize_assemble_batch on a
  *   freshly uploaded slot).  No frame, state or action bytes are uploaded per batch: a sequence is a window of the store.
  *   store   uint8, store_bytes of them: every trajectory's frames [n_i][H][W][3] ([n_i][Hs][Ws][3] in the resize form) back to back,
  *           no padding between trajectories; 16-byte aligned (the plain form with H * W % 4 != 0 takes any alignment);
@@ -1104,7 +1104,7 @@ int gcpx_resize_assemble_batch_resident(const uint8_t* store, int64_t store_byte
 /* The assembly for the nav datasets, whose frames are not recorded images but top-down pictures of the maze drawn from the states
  *   (MazeTopRenderedGlobalSplitVarLenVideoDataset.process_data_dict, /root/reference/gcp/datasets/data_loader.py:299-319, calling
  *   Multiroom3dEnv.render_pos_top_down, gcp/planning/infra/envs/miniworld_env/multiroom3d/multiroom3d_env.py:185-219).  Called by
- *   video-gcp_amd/dataset.py: topdown_assemble_into (HostFedLoader._assemble).
+ *   video-gcp_amd/dataset.py: topdown_assemble_into (HostFedLoader._launch).
  *   background  uint8 [side][side][3]: the static picture padded by cw zeros on every side, after the reference's * 255 truncation;
  *   agent_stamp / goal_stamp  uint8 [k][k] (non-zero: painted), k odd, entry [k / 2][k / 2] on the point; agent_rgb / goal_rgb: the dot
  *   colours as r | g << 8 | b << 16;  coords int32 [B][T][2]: (x, y) of the agent in the padded picture for the frames of the window

@@ -229,6 +229,27 @@ def test_ring_reuse_five_batches_equal_the_numpy_batches(tmp_path, c1_model):
     assert n == len(loader) >= 5
 
 
+def test_three_slot_ring_of_both_loaders_equals_the_numpy_batches(tmp_path, c1_model):
+    """n_slots = 3 with fewer batches than slots (2) and with a slot reused (4), through the one ring of dataset.RingLoader"""
+    hp, model = c1_model
+    Tm, img, B = hp.max_seq_len, hp.img_sz, hp.batch_size
+    FX.write_random_dataset(str(tmp_path), T=Tm, img=img, n_files=2, traj_per_file=B, phases=("train",), min_len=5)
+    ds = DS.VideoDataset(str(tmp_path), DS.load_spec(str(tmp_path)), "train", img, randomize_length=True)
+    for n_repeat in (1, 2):
+        for loader in (DS.HostFedLoader(ds, model, B, n_repeat=n_repeat, seed=5, n_slots=3, n_workers=3),
+                       DR.ResidentLoader(ds, model, B, n_repeat=n_repeat, seed=5, n_slots=3)):
+            assert len(loader) == 2 * n_repeat
+            n = 0
+            for got, ref in zip(loader, loader.numpy_batches()):
+                torch.cuda.synchronize()
+                assert set(got) == set(KEYS)
+                for k in KEYS:
+                    assert got[k].data_ptr() == model.input_buffer(k, tuple(got[k].shape), got[k].dtype).data_ptr(), k
+                    assert torch.equal(got[k].cpu(), torch.from_numpy(ref[k])), (type(loader).__name__, n_repeat, n, k)
+                n += 1
+            assert n == len(loader)
+
+
 @pytest.mark.parametrize("resize,rl,rs,std", [(False, True, False, True), (False, False, True, False), (True, True, False, False)],
                          ids=["length_std", "start", "resize_length"])
 def test_loader_equals_the_host_fed_loader(tmp_path, c1_model, resize, rl, rs, std):

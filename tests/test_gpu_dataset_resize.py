@@ -162,7 +162,7 @@ def test_host_fed_loader_resizes_into_the_input_buffers(tmp_path, name):
             n += 1
         assert n == 3
     assert orders[0] != orders[1]
-    assert loader._bufs[1]["frames"][0].shape == (B, T, 2 * img, 2 * img, 3)        # uploaded at the stored size
+    assert loader.dev["frames"][0].shape == (B, T, 2 * img, 2 * img, 3)        # uploaded at the stored size
 
 
 def _trainer(name):

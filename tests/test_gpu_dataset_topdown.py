@@ -197,7 +197,7 @@ def test_host_fed_loader_renders_into_the_input_buffers(tmp_path):
             n += 1
         assert n == 3
     assert orders[0] != orders[1]
-    pin, devs = loader._bufs[0], loader._bufs[1]
+    pin, devs = loader.pin, loader.dev
     assert "frames" not in pin and "frames" not in devs                       # no frame buffer: a slot holds coordinates
     assert devs["coords"][0].shape == (B * T * 2 + B * 2,) and devs["coords"][0].dtype == torch.int32
     assert not any(v.dtype == torch.uint8 and v.numel() >= B * T * 3 * img * img for vs in list(pin.values()) + list(devs.values()) for v in vs)

@@ -1,8 +1,7 @@
 // The two integer passes of the 8-bit bilinear resampler (Pillow's Image.resize, see video-gcp_amd/dataset.py) as device functions over a
-// band of source rows staged in LDS, and the host-side choice of the band.  Shared by the kernels that resize inside the batch assembly:
-// csrc/batch_assemble.hip (recorded frames), csrc/batch_assemble_resident.hip (recorded frames kept on the device; it also shares the
-// staging loads and the conversion of frames that need no resize) and csrc/topdown_assemble.hip (frames rendered from states), so that
-// all do one arithmetic.
+// band of source rows staged in LDS, the band itself (ResizeBand: LDS carve-up, tables, where the rows go), the host-side choice of the
+// band, and the staging loads and the conversion of frames that need no resize.  Shared by the kernels of csrc/batch_assemble.hip
+// (recorded frames from an uploaded slot or from a resident store; frames rendered top-down from states), so that all do one arithmetic.
 #pragma once
 #include <algorithm>
 
@@ -12,7 +11,7 @@ namespace gcpx_resize {
 
 constexpr int kThreads = 256;
 constexpr int kInfo = 8;     // int32 per sequence: n_frames, n_states, n_actions, chop, zero_from, end_ind, -, -
-constexpr int kInfoResident = 8;   // int64 per sequence of the resident forms (csrc/batch_assemble_resident.hip, include/gcpx.h)
+constexpr int kInfoResident = 8;   // int64 per sequence of the resident forms (include/gcpx.h fixes the layout)
 constexpr int kPrecisionBits = 22;            // Pillow's PRECISION_BITS for 8-bit channels
 constexpr int kResizeMaxSide = 512;
 constexpr int kResizeMaxScale = 8;
@@ -241,9 +240,65 @@ inline int resize_choose_band(const int Hs, const int Ws, const int H, const int
     return 0;
 }
 
-// pad mask, end / start index, states and actions of one batch (assemble_small_kernel of csrc/batch_assemble.hip) on `stream`
-void launch_assemble_small(hipStream_t stream, const int32_t* info, const float* pad_in, const float* states_in, const float* actions_in,
-                           const float* mean, const float* den, int B, int T, int S, int A, float* pad_mask, int64_t* end_ind,
-                           int64_t* start_ind, float* states, float* actions);
+// One workgroup of a resizing kernel: the band of output rows [r0, r0 + nr) of one output frame.  Its parts of the LDS (ResizeLds), the
+// source rows [y_lo, y_lo + nrows) the band reads and where its rows go: dst in traj_seq, d0 / dg in I_0 / I_g when the frame is also
+// that (else null).  A kernel makes it (resize_band), loads lut and tables (resize_band_tables), stages the source rows into `raw` its own
+// way and ends with resize_band_store.
+struct ResizeBand {
+    float* tab;
+    int32_t *skx, *sbx, *sky, *sby;
+    uint8_t *raw, *hres;
+    int Hs, Ws, W, ksx, ksy, cap, HW, r0, nr, y_lo, nrows;
+    float *dst, *d0, *dg;
+};
+
+// the band blockIdx.y of output frame t of sequence b (source Hs x Ws, output H x W, R rows to a band, at most cap source rows)
+__device__ __forceinline__ ResizeBand resize_band(uint8_t* smem, const int Hs, const int Ws, const int H, const int W, const int ksx,
+                                                  const int ksy, const int R, const int cap, const int b, const int t, const int T,
+                                                  const int end_ind, float* traj, float* I0, float* Ig) {
+    const ResizeLds L = resize_lds(Ws, W, ksx, ksy, R, cap);
+    ResizeBand d;
+    d.tab = reinterpret_cast<float*>(smem);
+    d.skx = reinterpret_cast<int32_t*>(smem) + 256;
+    d.sbx = d.skx + W * ksx;
+    d.sky = d.sbx + 2 * W;
+    d.sby = d.sky + R * ksy;
+    d.raw = smem + L.raw_off;
+    d.hres = smem + L.hres_off;
+    d.Hs = Hs, d.Ws = Ws, d.W = W, d.ksx = ksx, d.ksy = ksy, d.cap = cap, d.HW = H * W;
+    d.r0 = blockIdx.y * R;
+    d.nr = min(R, H - d.r0);
+    d.dst = traj + ((size_t)b * T + t) * 3 * d.HW + (size_t)d.r0 * W;
+    d.d0 = t == 0 ? I0 + (size_t)b * 3 * d.HW + (size_t)d.r0 * W : nullptr;
+    d.dg = t == end_ind ? Ig + (size_t)b * 3 * d.HW + (size_t)d.r0 * W : nullptr;
+    return d;
+}
+
+// lut and the band's tables into LDS, y_lo / nrows from the bounds table; no barrier: the caller's staged bytes go under the same one.
+// A frame that is not valid resizes to zeros: the band is lut[0], no table or frame is read, and the result is false (nothing left to do).
+__device__ __forceinline__ bool resize_band_tables(ResizeBand& d, const bool valid, const float* lut, const int32_t* kx, const int32_t* bx,
+                                                   const int32_t* ky, const int32_t* by, const int tid) {
+    d.tab[tid] = lut[tid];
+    if (!valid) {
+        store_pad_band(lut[0], d.nr, d.W >> 2, d.HW, d.dst, d.d0, d.dg, tid);
+        return false;
+    }
+    for (int i = tid; i < d.W * d.ksx; i += kThreads) d.skx[i] = kx[i];
+    for (int i = tid; i < 2 * d.W; i += kThreads) d.sbx[i] = bx[i];
+    for (int i = tid; i < d.nr * d.ksy; i += kThreads) d.sky[i] = ky[d.r0 * d.ksy + i];
+    for (int i = tid; i < 2 * d.nr; i += kThreads) d.sby[i] = by[2 * d.r0 + i];
+    const int last = d.r0 + d.nr - 1;
+    d.y_lo = min(max(by[2 * d.r0], 0), d.Hs - 1);
+    d.nrows = min(min(max(by[2 * last] + by[2 * last + 1], d.y_lo + 1), d.Hs) - d.y_lo, d.cap);
+    return true;
+}
+
+// tables and source rows (byte `shift` of raw is the first) are written: horizontal pass LDS -> LDS, vertical pass, conversion, stores
+__device__ __forceinline__ void resize_band_store(const ResizeBand& d, const int shift, const int tid) {
+    __syncthreads();
+    resize_rows_any(d.ksx, d.raw, shift, d.hres, d.skx, d.sbx, d.nrows, d.Ws, d.W, tid);
+    __syncthreads();
+    resize_cols_store(d.hres, d.sky, d.sby, d.tab, d.y_lo, d.nrows, d.nr, d.W, d.ksy, d.HW, d.dst, d.d0, d.dg, tid);
+}
 
 }  // namespace gcpx_resize

@@ -30,7 +30,7 @@ end_ind), resized to img_sz; later frames are zero.  The picture and the dot's s
 the reference; both are constant for a dataset and enter as data, `<data_dir>/topdown_assets.npz` (INTEGRATION.md has the recipe).  From
 those arrays on the renderer is integer work: `topdown_pixels` is the reference's float32 state -> pixel arithmetic, `render_topdown_numpy`
 the crop and the two dots.  Recorded images are neither read nor uploaded: an item carries the agent's pixel per window frame and the
-goal's pixel, and gcpx_topdown_assemble_batch (csrc/topdown_assemble.hip) renders, resizes and converts in the launch that writes the
+goal's pixel, and gcpx_topdown_assemble_batch (csrc/batch_assemble.hip) renders, resizes and converts in the launch that writes the
 model's inputs.  The model gets states[..., :2] (MazeGlobalSplit..., data_loader.py:292-296).
 
 Keeping a whole split on the device and assembling batches from it there, with the same draws and the same bits
@@ -498,16 +498,33 @@ def pack_item(item, j, frames, aux, info, B, T, S, A, topdown=None):
     info[j] = (fr.shape[0], n_s, n_a, p["chop"], p["zero_from"], p["end_ind"], 0, 0)
 
 
+# ---- the argument groups the five assembly entry points share (include/gcpx.h), each built in one place ----
+def opt_ptr(x):
+    return x.data_ptr() if x is not None else None
+
+
+def aux_args(aux, B, T, S, A):
+    """pad_in, states_in, actions_in: the three parts of aux = [pad_mask B*T | states B*T*S | actions B*(T-1)*A] (f32, on the device)"""
+    a = aux.data_ptr()
+    return a, a + 4 * B * T if S else None, a + 4 * B * T * (1 + S) if A else None
+
+
+def table_args(tables):
+    """kx, bx, ky, by of `tables` = resize_tables on the device; the tap counts ksx, ksy are kx.shape[1], ky.shape[1]"""
+    return tuple(t.data_ptr() for t in tables)
+
+
+def output_args(out, stream):
+    """the tail of every entry point: the eight tensors of `out` (the model's input names; absent ones null) and the stream"""
+    return tuple(opt_ptr(out.get(k)) for k in ("traj_seq", "I_0", "I_g", "pad_mask", "end_ind", "start_ind", "traj_seq_states",
+                                             "actions")) + (stream,)
+
+
 def assemble_into(lib, frames, aux, info, lut, mean, den, out, S, A, stream):
     """gcpx_assemble_batch from device staging tensors into the device tensors of `out` (the model's input names)"""
     B, T, H, W, _ = frames.shape
-    a = aux.data_ptr()
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    rt.check(lib.gcpx_assemble_batch(frames.data_ptr(), info.data_ptr(), lut.data_ptr(), a, a + 4 * B * T if S else None,
-                                     a + 4 * B * T * (1 + S) if A else None, mean.data_ptr() if mean is not None else None,
-                                     den.data_ptr() if den is not None else None, B, T, H, W, S, A, ptr("traj_seq"), ptr("I_0"),
-                                     ptr("I_g"), ptr("pad_mask"), ptr("end_ind"), ptr("start_ind"), ptr("traj_seq_states"),
-                                     ptr("actions"), stream), "assemble_batch")
+    rt.check(lib.gcpx_assemble_batch(frames.data_ptr(), info.data_ptr(), lut.data_ptr(), *aux_args(aux, B, T, S, A), opt_ptr(mean),
+                                     opt_ptr(den), B, T, H, W, S, A, *output_args(out, stream)), "assemble_batch")
 
 
 def resize_tables(Hs, Ws, img_sz):
@@ -522,15 +539,9 @@ def resize_assemble_into(lib, frames, aux, info, lut, tables, mean, den, out, S,
     into the device tensors of `out` (the model's input names, at the model's size)"""
     B, T, Hs, Ws, _ = frames.shape
     H, W = out["traj_seq"].shape[-2:]
-    kx, bx, ky, by = tables
-    a = aux.data_ptr()
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    rt.check(lib.gcpx_resize_assemble_batch(frames.data_ptr(), info.data_ptr(), lut.data_ptr(), kx.data_ptr(), bx.data_ptr(),
-                                            ky.data_ptr(), by.data_ptr(), a, a + 4 * B * T if S else None,
-                                            a + 4 * B * T * (1 + S) if A else None, mean.data_ptr() if mean is not None else None,
-                                            den.data_ptr() if den is not None else None, B, T, Hs, Ws, H, W, kx.shape[1], ky.shape[1],
-                                            S, A, ptr("traj_seq"), ptr("I_0"), ptr("I_g"), ptr("pad_mask"), ptr("end_ind"),
-                                            ptr("start_ind"), ptr("traj_seq_states"), ptr("actions"), stream), "resize_assemble_batch")
+    rt.check(lib.gcpx_resize_assemble_batch(frames.data_ptr(), info.data_ptr(), lut.data_ptr(), *table_args(tables),
+                                            *aux_args(aux, B, T, S, A), opt_ptr(mean), opt_ptr(den), B, T, Hs, Ws, H, W, tables[0].shape[1],
+                                            tables[2].shape[1], S, A, *output_args(out, stream)), "resize_assemble_batch")
 
 
 def topdown_device_assets(assets, img_sz, device):
@@ -550,18 +561,13 @@ def topdown_assemble_into(lib, dev_assets, coords, aux, info, lut, mean, den, ou
     [B*T*2 + B*2], aux, info) into the device tensors of `out` (the model's input names)"""
     B, T = out["traj_seq"].shape[:2]
     H, W = out["traj_seq"].shape[-2:]
-    d = dev_assets
-    kx, bx, ky, by = d["tables"]
-    a, c = aux.data_ptr(), coords.data_ptr()
-    ptr = lambda k: out[k].data_ptr() if k in out else None
+    d, c = dev_assets, coords.data_ptr()
+    tables = d["tables"]
     rt.check(lib.gcpx_topdown_assemble_batch(d["background"].data_ptr(), d["background"].shape[0], d["cw"], d["agent_stamp"].data_ptr(),
                                              d["goal_stamp"].data_ptr(), d["k"], d["agent_rgb"], d["goal_rgb"], c, c + 4 * B * T * 2,
-                                             info.data_ptr(), lut.data_ptr(), kx.data_ptr(), bx.data_ptr(), ky.data_ptr(), by.data_ptr(),
-                                             a, a + 4 * B * T if S else None, a + 4 * B * T * (1 + S) if A else None,
-                                             mean.data_ptr() if mean is not None else None, den.data_ptr() if den is not None else None,
-                                             B, T, H, W, kx.shape[1], ky.shape[1], S, A, ptr("traj_seq"), ptr("I_0"), ptr("I_g"),
-                                             ptr("pad_mask"), ptr("end_ind"), ptr("start_ind"), ptr("traj_seq_states"), ptr("actions"),
-                                             stream), "topdown_assemble_batch")
+                                             info.data_ptr(), lut.data_ptr(), *table_args(tables), *aux_args(aux, B, T, S, A),
+                                             opt_ptr(mean), opt_ptr(den), B, T, H, W, tables[0].shape[1], tables[2].shape[1], S, A,
+                                             *output_args(out, stream)), "topdown_assemble_batch")
 
 
 class _Streams:
@@ -574,16 +580,25 @@ class _Streams:
         self.assembled = [torch.cuda.Event() for _ in range(n)]
 
 
-class HostFedLoader:
-    """Yields the model's input dicts, assembled on the device from uint8 frames uploaded from a ring of pinned host slots.  The
-    tensors it yields ARE `model.input_buffer(...)` (no staging copy in the forward); each batch is assembled on the caller's current
-    stream when the next one is asked for, i.e. behind the previous training step.  RepeatedDataLoader semantics (n_repeat passes
-    per epoch, data_loader.py:83-88), drop_last, shuffle in the train phase only.  A dataset read with resize=True whose frames are
-    stored at another size than the model's is uploaded at that size (the slots hold H_s x W_s frames) and resized in the assembly,
-    over tables uploaded once.  A top-rendered dataset (dataset.topdown) has no frame slots at all: a slot holds int32 pixel coordinates
-    [B][T][2] + [B][2], and the padded picture, the stamps and the tables for (2cw, 2cw, img_sz) stay on the device."""
+class RingLoader:
+    """What HostFedLoader and ResidentLoader (dataset_resident.py) share: the epoch's schedule and a ring of `n_slots` slots, each a set
+    of pinned host tensors and their device copies.  Per batch a slot is filled on worker threads, copied up on the copy stream and
+    read by one assembly call on the caller's current stream, which writes `model.input_buffer(...)`: the tensors yielded ARE those
+    buffers (no staging copy in the forward), and each batch is assembled when the next one is asked for, i.e. behind the previous
+    step.  RepeatedDataLoader semantics (n_repeat passes per epoch, data_loader.py:83-88), drop_last, shuffle in the train phase only.
 
-    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None):
+    Slot reuse has two rules, each enforced in one place:
+      1. a pinned slot is refilled only after its upload has completed (`_job`, on the worker thread);
+      2. a device slot is overwritten only after the assembly that read it has run (`_upload`, on the copy stream).
+
+    A loader supplies three things:
+      `_jobs(batch)` -> [(method, *args)]: how a slot is filled, the calls method(slot, *args) of one worker job each;
+      `_alloc_slots(dev, n)` -> (Hs, Ws) the frames are stored at, or None: what is copied up, self.pin / self.dev = {name: [per slot]};
+      `_launch(slot, out, stream)`: the assembly call that reads device slot `slot` and writes the tensors of `out` on `stream`.
+    `__iter__` decides from the fill futures alone (when to wait, when to upload, when to upload the next slot early, when to
+    resubmit) and reaches the device only through `_submit`, `_upload` and `_assemble`."""
+
+    def __init__(self, dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers):
         if rank is None or world is None:
             d = torch.distributed
             on = d.is_available() and d.is_initialized()
@@ -600,10 +615,8 @@ class HostFedLoader:
             raise ValueError(f"dataset (T={dataset.T}, {dataset.img_sz}px) and model (T={hp.max_seq_len}, {hp.img_sz}px) differ")
         if hp.batch_size != self.B:
             raise ValueError(f"loader batch {self.B} != model batch {hp.batch_size}")
-        raw0 = dataset.read(0)
-        self.S = raw0["states"].shape[-1] if "states" in raw0 else 0
-        self.A = raw0["actions"].shape[-1] if "actions" in raw0 else 0
-        self._bufs = None
+        self.S = self.A = 0                            # state / action widths: the loader sets them
+        self.pin = self.dev = self.streams = None      # the ring, allocated with the first batch (_alloc)
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -622,52 +635,37 @@ class HostFedLoader:
 
     # ---- the ring ----
     def _alloc(self):
-        dev, B, T, n = self.model.device, self.B, self.ds.T, self.n_slots
-        H, W = self.ds.src_size                        # the slots hold the frames as stored; the resize is part of the assembly
-        S, A = self.S, self.A
-        naux = B * T + B * T * S + B * (T - 1) * A
-        top = self.ds.topdown is not None
-        fkey, fshape, ftype = ("coords", (B * T * 2 + B * 2,), torch.int32) if top else ("frames", (B, T, H, W, 3), torch.uint8)
-        pin = {fkey: [torch.empty(fshape, dtype=ftype, pin_memory=True) for _ in range(n)]}
-        pin.update(aux=[torch.empty(naux, dtype=torch.float32, pin_memory=True) for _ in range(n)],
-                   info=[torch.zeros(B, N_INFO, dtype=torch.int32, pin_memory=True) for _ in range(n)])
-        devs = {fkey: [torch.empty(fshape, dtype=ftype, device=dev) for _ in range(n)]}
-        devs.update(aux=[torch.empty(naux, dtype=torch.float32, device=dev) for _ in range(n)],
-                    info=[torch.empty(B, N_INFO, dtype=torch.int32, device=dev) for _ in range(n)])
-        lut = torch.from_numpy(LUT).to(dev)
-        mean = den = None
-        if self.ds.states_mean is not None and S:
-            mean = torch.from_numpy(self.ds.states_mean).to(dev)
-            den = torch.from_numpy(self.ds.states_den).to(dev)
-        self._tables = self._topdown = None
-        if top:
-            self._topdown = topdown_device_assets(self.ds.topdown, self.ds.img_sz, dev)
-        elif (H, W) != (self.ds.img_sz, self.ds.img_sz):
-            self._tables = tuple(torch.from_numpy(t).to(dev) for t in resize_tables(H, W, self.ds.img_sz))
-        self._bufs = (pin, devs, lut, mean, den, _Streams(dev, n))
+        dev = self.model.device
+        src = self._alloc_slots(dev, self.n_slots)
+        self.lut = torch.from_numpy(LUT).to(dev)
+        self.mean = self.den = self.tables = None
+        if self.ds.states_mean is not None and self.S:
+            self.mean = torch.from_numpy(self.ds.states_mean).to(dev)
+            self.den = torch.from_numpy(self.ds.states_den).to(dev)
+        if src is not None and tuple(src) != (self.ds.img_sz, self.ds.img_sz):
+            self.tables = tuple(torch.from_numpy(t).to(dev) for t in resize_tables(src[0], src[1], self.ds.img_sz))
+        self.streams = _Streams(dev, self.n_slots)
 
-    def _fill_item(self, slot, j, index, pos, cycle):
-        pin, _, _, _, _, st = self._bufs
-        st.copy_done[slot].synchronize()              # rule 1: the slot's previous upload has completed (a worker thread waits)
-        item = self.ds.item(index, item_rng(self.seed, cycle, pos))
-        fkey = "coords" if self.ds.topdown is not None else "frames"
-        pack_item(item, j, pin[fkey][slot].numpy(), pin["aux"][slot].numpy(), pin["info"][slot].numpy(), self.B, self.ds.T,
-                  self.S, self.A, topdown=self.ds.topdown)
+    def _job(self, slot, fn, *args):
+        self.streams.copy_done[slot].synchronize()    # rule 1: the slot's previous upload has completed (the worker thread waits)
+        fn(slot, *args)
 
     def _submit(self, slot, batch):
-        return [self.pool.submit(self._fill_item, slot, j, i, p, c) for j, (i, p, c) in enumerate(batch)]
+        """start filling pinned slot `slot` with `batch` -> the futures of its jobs"""
+        if self.streams is None:
+            self._alloc()
+        return [self.pool.submit(self._job, slot, *job) for job in self._jobs(batch)]
 
     def _upload(self, slot):
-        pin, devs, _, _, _, st = self._bufs
+        st = self.streams
         with torch.cuda.stream(st.copy):
             st.copy.wait_event(st.assembled[slot])    # rule 2: the assembly that read this device slot has run
-            for k in pin:
-                devs[k][slot].copy_(pin[k][slot], non_blocking=True)
+            for k in self.pin:
+                self.dev[k][slot].copy_(self.pin[k][slot], non_blocking=True)
             st.copy_done[slot].record(st.copy)
 
     def _assemble(self, slot):
-        m = self.model
-        pin, devs, lut, mean, den, st = self._bufs
+        m, st = self.model, self.streams
         B, T, S, A, H = self.B, self.ds.T, self.S, self.A, self.ds.img_sz
         caller = torch.cuda.current_stream(m.device)
         caller.wait_event(st.copy_done[slot])
@@ -678,20 +676,11 @@ class HostFedLoader:
             out["traj_seq_states"] = ib("traj_seq_states", (B, T, S))
         if A:
             out["actions"] = ib("actions", (B, T - 1, A))
-        if self._topdown is not None:
-            topdown_assemble_into(m.lib, self._topdown, devs["coords"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out,
-                                  S, A, caller.cuda_stream)
-        elif self._tables is None:
-            assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, mean, den, out, S, A, caller.cuda_stream)
-        else:
-            resize_assemble_into(m.lib, devs["frames"][slot], devs["aux"][slot], devs["info"][slot], lut, self._tables, mean, den, out,
-                                 S, A, caller.cuda_stream)
+        self._launch(slot, out, caller.cuda_stream)
         st.assembled[slot].record(caller)
         return out
 
     def __iter__(self):
-        if self._bufs is None:
-            self._alloc()
         batches = self.schedule()
         n = self.n_slots
         futs = {k: self._submit(k % n, batches[k]) for k in range(min(n, len(batches)))}
@@ -712,3 +701,49 @@ class HostFedLoader:
                 self._upload((k + 1) % n)
                 uploaded.add(k + 1)
             yield out
+
+
+class HostFedLoader(RingLoader):
+    """Yields the model's input dicts, assembled on the device from uint8 frames uploaded from the ring's pinned host slots: every
+    item is read, sliced and packed by one of `n_workers` threads.  A dataset read with resize=True whose frames are stored at
+    another size than the model's is uploaded at that size (the slots hold H_s x W_s frames) and resized in the assembly, over tables
+    uploaded once.  A top-rendered dataset (dataset.topdown) has no frame slots at all: a slot holds int32 pixel coordinates
+    [B][T][2] + [B][2], and the padded picture, the stamps and the tables for (2cw, 2cw, img_sz) stay on the device."""
+
+    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None):
+        super().__init__(dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers)
+        raw0 = dataset.read(0)
+        self.S = raw0["states"].shape[-1] if "states" in raw0 else 0
+        self.A = raw0["actions"].shape[-1] if "actions" in raw0 else 0
+        self.topdown = None                            # topdown_device_assets of a top-rendered dataset
+
+    def _alloc_slots(self, dev, n):
+        B, T, S, A = self.B, self.ds.T, self.S, self.A
+        H, W = self.ds.src_size                        # the slots hold the frames as stored; the resize is part of the assembly
+        top = self.ds.topdown is not None
+        slot = {"coords": ((B * T * 2 + B * 2,), torch.int32)} if top else {"frames": ((B, T, H, W, 3), torch.uint8)}
+        slot.update(aux=((B * T + B * T * S + B * (T - 1) * A,), torch.float32), info=((B, N_INFO), torch.int32))
+        self.pin = {k: [torch.zeros(shape, dtype=t, pin_memory=True) for _ in range(n)] for k, (shape, t) in slot.items()}
+        self.dev = {k: [torch.empty(shape, dtype=t, device=dev) for _ in range(n)] for k, (shape, t) in slot.items()}
+        if top:
+            self.topdown = topdown_device_assets(self.ds.topdown, self.ds.img_sz, dev)
+        return None if top else (H, W)
+
+    def _jobs(self, batch):
+        return [(self._fill_item, j, i, p, c) for j, (i, p, c) in enumerate(batch)]
+
+    def _fill_item(self, slot, j, index, pos, cycle):
+        item = self.ds.item(index, item_rng(self.seed, cycle, pos))
+        fkey = "coords" if self.ds.topdown is not None else "frames"
+        pack_item(item, j, self.pin[fkey][slot].numpy(), self.pin["aux"][slot].numpy(), self.pin["info"][slot].numpy(), self.B,
+                  self.ds.T, self.S, self.A, topdown=self.ds.topdown)
+
+    def _launch(self, slot, out, stream):
+        lib, d = self.model.lib, {k: v[slot] for k, v in self.dev.items()}
+        tail = (self.mean, self.den, out, self.S, self.A, stream)
+        if self.topdown is not None:
+            topdown_assemble_into(lib, self.topdown, d["coords"], d["aux"], d["info"], self.lut, *tail)
+        elif self.tables is None:
+            assemble_into(lib, d["frames"], d["aux"], d["info"], self.lut, *tail)
+        else:
+            resize_assemble_into(lib, d["frames"], d["aux"], d["info"], self.lut, self.tables, *tail)

@@ -11,7 +11,7 @@ and on the host one row per trajectory: first frame index, n_i, first state / ac
 
 Per batch `ResidentLoader` makes the B draws, writes 8 int64 per sequence (`resident_info`: which window of which trajectory, chop,
 zero_from, end_ind) and the pad masks into one pinned slot, copies that slot (B * (64 + 4 T) bytes) and launches
-gcpx_assemble_batch_resident / gcpx_resize_assemble_batch_resident (csrc/batch_assemble_resident.hip) into `model.input_buffer(...)`.
+gcpx_assemble_batch_resident / gcpx_resize_assemble_batch_resident (csrc/batch_assemble.hip) into `model.input_buffer(...)`.
 No frame, state or action byte crosses per batch.  Schedule, draws and every tensor of every batch are HostFedLoader's bit for bit;
 `resident_batch_numpy` is the same indexing over host copies of the three arrays, the kernels' check on the CPU.
 
@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import runtime as rt
-from .dataset import LUT, _Streams, epoch_schedule, item_rng, numpy_batch, resize_frames_numpy, resize_tables
+from .dataset import LUT, RingLoader, item_rng, opt_ptr, output_args, resize_frames_numpy, table_args
 
 N_INFO_RESIDENT = 8     # int64 per sequence read by gcpx_assemble_batch_resident (include/gcpx.h)
 MAX_WORKERS = 16
@@ -218,135 +218,45 @@ def resident_assemble_into(lib, store_ptr, store_bytes, states_ptr, actions_ptr,
     """the resident assembly of one batch into the device tensors of `out` (the model's input names).  slot_ptr: the device slot
     [info int64 B * 8 | pad_mask f32 B * T]; src = (Hs, Ws) of the store; tables None: frames stored at the model's size."""
     H, W = out["traj_seq"].shape[-2:]
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    opt = lambda x: x.data_ptr() if x is not None else None
-    pad_ptr = slot_ptr + 8 * N_INFO_RESIDENT * B
-    tail = (ptr("traj_seq"), ptr("I_0"), ptr("I_g"), ptr("pad_mask"), ptr("end_ind"), ptr("start_ind"), ptr("traj_seq_states"),
-            ptr("actions"), stream)
+    head = (store_ptr, store_bytes, slot_ptr, lut.data_ptr())
+    rows = (slot_ptr + 8 * N_INFO_RESIDENT * B, states_ptr if S else None, actions_ptr if A else None, opt_ptr(mean), opt_ptr(den))
     if tables is None:
-        rt.check(lib.gcpx_assemble_batch_resident(store_ptr, store_bytes, slot_ptr, lut.data_ptr(), pad_ptr, states_ptr if S else None,
-                                                  actions_ptr if A else None, opt(mean), opt(den), B, T, H, W, S, A, *tail),
-                 "assemble_batch_resident")
+        rt.check(lib.gcpx_assemble_batch_resident(*head, *rows, B, T, H, W, S, A, *output_args(out, stream)), "assemble_batch_resident")
     else:
-        kx, bx, ky, by = tables
-        rt.check(lib.gcpx_resize_assemble_batch_resident(store_ptr, store_bytes, slot_ptr, lut.data_ptr(), kx.data_ptr(), bx.data_ptr(),
-                                                         ky.data_ptr(), by.data_ptr(), pad_ptr, states_ptr if S else None,
-                                                         actions_ptr if A else None, opt(mean), opt(den), B, T, src[0], src[1], H, W,
-                                                         kx.shape[1], ky.shape[1], S, A, *tail), "resize_assemble_batch_resident")
+        rt.check(lib.gcpx_resize_assemble_batch_resident(*head, *table_args(tables), *rows, B, T, src[0], src[1], H, W, tables[0].shape[1],
+                                                         tables[2].shape[1], S, A, *output_args(out, stream)),
+                 "resize_assemble_batch_resident")
 
 
-class ResidentLoader:
-    """HostFedLoader's interface and batches (set_epoch, __len__, schedule, numpy_batches, __iter__; the tensors it yields ARE
-    `model.input_buffer(...)`) over a ResidentStore built at construction.  Per batch one worker thread makes the B draws from the
-    store's pad masks and fills a pinned slot with info and pad masks; the slot is copied on the copy stream and the resident assembly
-    runs on the caller's stream behind the slot's event.  Slot reuse follows HostFedLoader's two rules: a pinned slot is refilled after
-    its upload has completed, a device slot is overwritten after the assembly that read it has run.
+class ResidentLoader(RingLoader):
+    """HostFedLoader's interface and batches (dataset.RingLoader) over a ResidentStore built at construction.  A slot is
+    [info int64 B * 8 | pad_mask f32 B * T]: per batch one worker thread makes the B draws from the store's pad masks and fills it, and
+    the resident assembly reads it and the store.
     Under a process group every rank holds the whole split (the shuffled order is one global order; a rank may draw any trajectory)."""
 
     def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, shuffle=None, budget_bytes=None):
-        if rank is None or world is None:
-            d = torch.distributed
-            on = d.is_available() and d.is_initialized()
-            rank = d.get_rank() if on else 0
-            world = d.get_world_size() if on else 1
-        assert n_slots >= 2
-        self.ds, self.model, self.B = dataset, model, int(batch_size)
-        self.n_repeat, self.seed, self.rank, self.world = int(n_repeat), int(seed), int(rank), int(world)
-        self.shuffle = (dataset.phase == "train") if shuffle is None else bool(shuffle)
-        self.n_slots, self.epoch = n_slots, 0
-        hp = model._hp
-        if hp.max_seq_len != dataset.T or hp.img_sz != dataset.img_sz:
-            raise ValueError(f"dataset (T={dataset.T}, {dataset.img_sz}px) and model (T={hp.max_seq_len}, {hp.img_sz}px) differ")
-        if hp.batch_size != self.B:
-            raise ValueError(f"loader batch {self.B} != model batch {hp.batch_size}")
+        super().__init__(dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers=1)
         self.store = ResidentStore(dataset, model.device, budget_bytes=budget_bytes)
         self.S, self.A = self.store.S, self.store.A
-        self.pool = ThreadPoolExecutor(max_workers=1)
-        self._bufs = None
 
-    def set_epoch(self, epoch):
-        self.epoch = int(epoch)
+    def _alloc_slots(self, dev, n):
+        nbytes = 8 * N_INFO_RESIDENT * self.B + 4 * self.B * self.ds.T
+        self.pin = {"slot": [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(n)]}
+        self.dev = {"slot": [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(n)]}
+        return self.store.Hs, self.store.Ws
 
-    def __len__(self):
-        return self.n_repeat * (len(self.ds) // (self.B * self.world))
-
-    def schedule(self):
-        """this rank's batches of the current epoch: [(dataset index, position, cycle)]"""
-        return epoch_schedule(len(self.ds), self.B, self.n_repeat, self.seed, self.epoch, self.shuffle, self.rank, self.world)
-
-    def numpy_batches(self):
-        """the same batches assembled on the host from the files (dataset.numpy_batch), as HostFedLoader.numpy_batches"""
-        for b in self.schedule():
-            yield numpy_batch(self.ds, b, self.seed)
-
-    # ---- the ring: one slot = [info int64 B * 8 | pad_mask f32 B * T] ----
-    def _alloc(self):
-        dev, B, T, n = self.model.device, self.B, self.ds.T, self.n_slots
-        nbytes = 8 * N_INFO_RESIDENT * B + 4 * B * T
-        pin = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(n)]
-        devs = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(n)]
-        lut = torch.from_numpy(LUT).to(dev)
-        mean = den = None
-        if self.ds.states_mean is not None and self.S:
-            mean = torch.from_numpy(self.ds.states_mean).to(dev)
-            den = torch.from_numpy(self.ds.states_den).to(dev)
-        tables = None
-        if (self.store.Hs, self.store.Ws) != (self.ds.img_sz, self.ds.img_sz):
-            tables = tuple(torch.from_numpy(t).to(dev) for t in resize_tables(self.store.Hs, self.store.Ws, self.ds.img_sz))
-        self._bufs = (pin, devs, lut, mean, den, tables, _Streams(dev, n))
+    def _jobs(self, batch):
+        return [(self._fill, batch)]
 
     def _fill(self, slot, batch):
-        pin, st = self._bufs[0], self._bufs[-1]
-        st.copy_done[slot].synchronize()              # rule 1: the slot's previous upload has completed (the worker thread waits)
         B, T = self.B, self.ds.T
         info, pad = resident_batch_info(self.store, batch, self.seed)
-        buf = pin[slot].numpy()
+        buf = self.pin["slot"][slot].numpy()
         buf[:8 * N_INFO_RESIDENT * B].view(np.int64).reshape(B, N_INFO_RESIDENT)[:] = info
         buf[8 * N_INFO_RESIDENT * B:].view(np.float32).reshape(B, T)[:] = pad
 
-    def _upload(self, slot):
-        pin, devs, st = self._bufs[0], self._bufs[1], self._bufs[-1]
-        with torch.cuda.stream(st.copy):
-            st.copy.wait_event(st.assembled[slot])    # rule 2: the assembly that read this device slot has run
-            devs[slot].copy_(pin[slot], non_blocking=True)
-            st.copy_done[slot].record(st.copy)
-
-    def _assemble(self, slot):
-        m, store = self.model, self.store
-        _, devs, lut, mean, den, tables, st = self._bufs
-        B, T, S, A, H = self.B, self.ds.T, self.S, self.A, self.ds.img_sz
-        caller = torch.cuda.current_stream(m.device)
-        caller.wait_event(st.copy_done[slot])
-        ib = m.input_buffer
-        out = dict(traj_seq=ib("traj_seq", (B, T, 3, H, H)), I_0=ib("I_0", (B, 3, H, H)), I_g=ib("I_g", (B, 3, H, H)),
-                   pad_mask=ib("pad_mask", (B, T)), end_ind=ib("end_ind", (B,)), start_ind=ib("start_ind", (B,), torch.int64))
-        if S:
-            out["traj_seq_states"] = ib("traj_seq_states", (B, T, S))
-        if A:
-            out["actions"] = ib("actions", (B, T - 1, A))
-        resident_assemble_into(m.lib, store.frames.data_ptr(), store.frames_bytes, store.states.data_ptr(), store.actions.data_ptr(),
-                               devs[slot].data_ptr(), B, T, (store.Hs, store.Ws), lut, tables, mean, den, out, S, A, caller.cuda_stream)
-        st.assembled[slot].record(caller)
-        return out
-
-    def __iter__(self):
-        if self._bufs is None:
-            self._alloc()
-        batches = self.schedule()
-        n = self.n_slots
-        futs = {k: self.pool.submit(self._fill, k % n, batches[k]) for k in range(min(n, len(batches)))}
-        uploaded = set()
-        for k in range(len(batches)):
-            s = k % n
-            if k not in uploaded:
-                futs.pop(k).result()
-                self._upload(s)
-            out = self._assemble(s)
-            if k + n < len(batches):
-                futs[k + n] = self.pool.submit(self._fill, s, batches[k + n])
-            # the next batch's slot goes up now if it is filled: the copy then runs under this step
-            if k + 1 < len(batches) and futs[k + 1].done():
-                futs.pop(k + 1).result()
-                self._upload((k + 1) % n)
-                uploaded.add(k + 1)
-            yield out
+    def _launch(self, slot, out, stream):
+        store = self.store
+        resident_assemble_into(self.model.lib, store.frames.data_ptr(), store.frames_bytes, store.states.data_ptr(),
+                               store.actions.data_ptr(), self.dev["slot"][slot].data_ptr(), self.B, self.ds.T, (store.Hs, store.Ws),
+                               self.lut, self.tables, self.mean, self.den, out, self.S, self.A, stream)
