@@ -888,6 +888,15 @@ int gcpx_optim_range(float* theta, const float* grad, float* m, float* v, float*
    one workgroup adds the partials the same way). */
 int gcpx_grad_clip_coef(const float* grad, int64_t n, float grad_scale, float max_norm, float* partial, int32_t n_partial, float* state,
                         void* stream);
+/* Gradient accumulation over the micro-batches of one optimizer step (the trainer's accumulate=k; no reference counterpart: k
+   micro-batches stand for the k replicas of nn.DataParallel, gcp_builder.py:71-78).  assign = 0: dst[i] = dst[i] + src[i]; assign = 1:
+   dst[i] = src[i] (the first micro-step of a cycle: no separate zero pass).  Exactly one float32 addition per element, nothing
+   contracted: the result does not depend on how a vector is cut into slices, and NaN / +-Inf propagate (gcpx_grad_health reads the
+   sum).  dst and src are any 4-byte aligned, non-overlapping slices (the bucket ranges of the flat gradient start anywhere): both
+   16-byte aligned takes four elements per access, two accesses in flight; the remainder and unaligned slices a scalar loop.  Nothing
+   outside [dst, dst + n) is written.  max_blocks as in gcpx_optim_range (0 = full grid).  n = 0 is a no-op that returns 0.
+   Memory bound: 12 n bytes of traffic (8 n with assign). */
+int gcpx_grad_accumulate(float* dst, const float* src, int64_t n, int32_t assign, int32_t max_blocks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * hipGraph helpers: capture a launch sequence once, replay it per step.

@@ -450,6 +450,40 @@ __global__ void __launch_bounds__(256) clip_coef_kernel(const float* __restrict_
     }
 }
 
+// Gradient accumulation over micro-batches: dst += src (ASSIGN: dst = src, the first micro-step of a cycle, so no zero pass).  One f32
+// addition per element and nothing to contract, so -- the rule of radam_kernel -- a vector cut into slices leaves the bits of one call.
+// VEC: both pointers 16-byte aligned, as in radam_kernel (four elements per access, two accesses in flight); the remainder and unaligned
+// slices take the scalar loop.  The additions on the float4 are written per component (this file: no packed f32).
+__device__ __forceinline__ void acc_add4(float4& d, const float4& s) { d.x = d.x + s.x; d.y = d.y + s.y; d.z = d.z + s.z; d.w = d.w + s.w; }
+template <bool VEC, bool ASSIGN>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, const long long n) {
+    const long long stride = (long long)gridDim.x * 256, first = (long long)blockIdx.x * 256 + threadIdx.x;
+    long long done = 0;
+    if (VEC) {
+        const long long n4 = n >> 2;
+        float4* __restrict__ d4 = reinterpret_cast<float4*>(dst);
+        const float4* __restrict__ s4 = reinterpret_cast<const float4*>(src);
+        for (long long i = first; i < n4; i += 2 * stride) {
+            const long long j = i + stride;
+            const bool two = j < n4;
+            float4 sa = s4[i], sb = sa;
+            if (two) sb = s4[j];
+            if (ASSIGN) {
+                d4[i] = sa;
+                if (two) d4[j] = sb;
+            } else {
+                float4 da = d4[i], db = da;
+                if (two) db = d4[j];
+                acc_add4(da, sa);
+                d4[i] = da;
+                if (two) { acc_add4(db, sb); d4[j] = db; }
+            }
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + first; i < n; i += stride) dst[i] = ASSIGN ? src[i] : dst[i] + src[i];
+}
+
 int blocks_for(long long items, int cap = 4096) {
     long long b = (items + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -529,6 +563,24 @@ extern "C" int gcpx_optim_range(float* theta, const float* grad, float* m, float
         hipLaunchKernelGGL(optim_kernel, dim3(max_blocks > 0 ? std::min(max_blocks, blocks_for(n, 16384)) : blocks_for(n, 16384)), dim3(256), 0,
                            stream, theta, grad, m, v, state, (long long)n, kind, lr, p1, p2, eps, grad_scale);
     if (tick) hipLaunchKernelGGL(radam_tick_kernel, dim3(1), dim3(1), 0, stream, state);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_grad_accumulate(float* dst, const float* src, int64_t n, int32_t assign, int32_t max_blocks, void* stream_) {
+    STREAM();
+    GCPX_CHECK_ARG(n >= 0 && (assign == 0 || assign == 1), "n >= 0, assign 0 (add) or 1 (copy)");
+    GCPX_CHECK_ARG(max_blocks >= 0, "max_blocks: 0 (no limit) or a positive number of workgroups");
+    if (n == 0) return GCPX_OK;
+    GCPX_CHECK_ARG(dst && src && ((((uintptr_t)dst | (uintptr_t)src) & 3) == 0), "dst / src: 4-byte aligned device pointers");
+    const bool vec = ((((uintptr_t)dst | (uintptr_t)src) & 15) == 0) && n >= 4;
+    int nb = blocks_for(vec ? (n + 7) / 8 : n, 16384);
+    if (max_blocks > 0) nb = std::min(nb, max_blocks);
+    const dim3 grid(nb), block(256);
+    if (vec && assign) hipLaunchKernelGGL((grad_accumulate_kernel<true, true>), grid, block, 0, stream, dst, src, (long long)n);
+    else if (vec) hipLaunchKernelGGL((grad_accumulate_kernel<true, false>), grid, block, 0, stream, dst, src, (long long)n);
+    else if (assign) hipLaunchKernelGGL((grad_accumulate_kernel<false, true>), grid, block, 0, stream, dst, src, (long long)n);
+    else hipLaunchKernelGGL((grad_accumulate_kernel<false, false>), grid, block, 0, stream, dst, src, (long long)n);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

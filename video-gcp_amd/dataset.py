@@ -465,6 +465,18 @@ def epoch_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank=0, 
     return out
 
 
+def accumulate_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank=0, world=1, accumulate=1):
+    """epoch_schedule of a loader that feeds gradient accumulation over `accumulate` = k micro-batches: for each global batch g of a pass
+    and j = 0 .. k-1, the batch of virtual rank rank·k + j of a virtual world world·k -- the sequences k times as many ranks would
+    read, in the order one trainer folds them.  A pass drops its leftover items as the world·k run drops them, so every pass (n_repeat
+    > 1 included) is a whole number of cycles."""
+    k = int(accumulate)
+    if k == 1:
+        return epoch_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank, world)
+    per = [epoch_schedule(n_items, batch_size, n_repeat, seed, epoch, shuffle, rank * k + j, world * k) for j in range(k)]
+    return [per[j][g] for g in range(len(per[0])) for j in range(k)]
+
+
 def numpy_batch(ds, batch, seed):
     """one scheduled batch assembled on the host by assemble_numpy"""
     return assemble_numpy([ds.item(i, item_rng(seed, c, p)) for i, p, c in batch], ds.T, ds.states_mean, ds.states_den,
@@ -598,13 +610,16 @@ class RingLoader:
     `__iter__` decides from the fill futures alone (when to wait, when to upload, when to upload the next slot early, when to
     resubmit) and reaches the device only through `_submit`, `_upload` and `_assemble`."""
 
-    def __init__(self, dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers):
+    def __init__(self, dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers, accumulate=1):
         if rank is None or world is None:
             d = torch.distributed
             on = d.is_available() and d.is_initialized()
             rank = d.get_rank() if on else 0
             world = d.get_world_size() if on else 1
         assert n_slots >= 2
+        if int(accumulate) < 1:
+            raise ValueError(f"accumulate must be a positive number of micro-batches, not {accumulate!r}")
+        self.accumulate = int(accumulate)              # micro-batches per optimizer step (accumulate_schedule)
         self.ds, self.model, self.B = dataset, model, int(batch_size)
         self.n_repeat, self.seed, self.rank, self.world = int(n_repeat), int(seed), int(rank), int(world)
         self.shuffle = (dataset.phase == "train") if shuffle is None else bool(shuffle)
@@ -622,11 +637,12 @@ class RingLoader:
         self.epoch = int(epoch)
 
     def __len__(self):
-        return self.n_repeat * (len(self.ds) // (self.B * self.world))
+        return self.n_repeat * self.accumulate * (len(self.ds) // (self.B * self.world * self.accumulate))
 
     def schedule(self):
         """this rank's batches of the current epoch: [(dataset index, position, cycle)]"""
-        return epoch_schedule(len(self.ds), self.B, self.n_repeat, self.seed, self.epoch, self.shuffle, self.rank, self.world)
+        return accumulate_schedule(len(self.ds), self.B, self.n_repeat, self.seed, self.epoch, self.shuffle, self.rank, self.world,
+                                   self.accumulate)
 
     def numpy_batches(self):
         """the same batches as numpy arrays assembled on the host (the device-fed path of the tests and of tools/host_fed_loop.py)"""
@@ -710,8 +726,9 @@ class HostFedLoader(RingLoader):
     uploaded once.  A top-rendered dataset (dataset.topdown) has no frame slots at all: a slot holds int32 pixel coordinates
     [B][T][2] + [B][2], and the padded picture, the stamps and the tables for (2cw, 2cw, img_sz) stay on the device."""
 
-    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None):
-        super().__init__(dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers)
+    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, n_workers=4, shuffle=None,
+                 accumulate=1):
+        super().__init__(dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers, accumulate=accumulate)
         raw0 = dataset.read(0)
         self.S = raw0["states"].shape[-1] if "states" in raw0 else 0
         self.A = raw0["actions"].shape[-1] if "actions" in raw0 else 0

@@ -234,8 +234,9 @@ class ResidentLoader(RingLoader):
     the resident assembly reads it and the store.
     Under a process group every rank holds the whole split (the shuffled order is one global order; a rank may draw any trajectory)."""
 
-    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, shuffle=None, budget_bytes=None):
-        super().__init__(dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers=1)
+    def __init__(self, dataset, model, batch_size, n_repeat=1, seed=0, rank=None, world=None, n_slots=2, shuffle=None, budget_bytes=None,
+                 accumulate=1):
+        super().__init__(dataset, model, batch_size, n_repeat, seed, rank, world, n_slots, shuffle, n_workers=1, accumulate=accumulate)
         self.store = ResidentStore(dataset, model.device, budget_bytes=budget_bytes)
         self.S, self.A = self.store.S, self.store.A
 

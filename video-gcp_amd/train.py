@@ -53,6 +53,11 @@ weights and optimizer state, in the checkpoint format), prints the two lists and
 the step on the device without a sync and goes on; with --log_scalars 1 `gradients/skipped_steps_train` counts them, and the total is
 printed at the end.  Under either, a checkpoint is written only from finite parameters and running statistics.
 Deviation: the reference always installs its hook; `--nan_guard` defaults to off, and a plain run is what it was.
+Gradient accumulation: `--accumulate_steps k` (no reference counterpart, and a flag only: `batch_size` of a conf stays the micro-batch)
+makes every optimizer step the mean gradient of k consecutive micro-batches, each with its own BatchNorm statistics -- what k times as
+many data-parallel ranks compute, up to the summation order and the noise streams (training.py, dataset.accumulate_schedule).
+global_step, model.step() (KL burn-in), the picture-log interval and the print / scalar-log block count optimizer steps; the printed
+and logged loss terms are the cycle's means; `--nan_guard raise` dumps the inputs of the cycle's LAST micro-batch.  Defaults to 1.
 """
 import argparse
 import json
@@ -97,7 +102,18 @@ def get_cmd_args(argv=None):
     p.add_argument("--nan_guard", default="off", choices=("off", "raise", "skip"), help="tests every gradient for NaN / Inf on the device "
                    "before the optimizer applies it: 'raise' dumps the batch and a checkpoint and stops (the reference always does), "
                    "'skip' drops the step and goes on")
-    return p.parse_args(argv)
+    p.add_argument("--accumulate_steps", default=1, type=int, help="micro-batches of `batch_size` whose mean gradient makes one optimizer "
+                   "step: one GPU then trains with the batch of k ranks")
+    args = p.parse_args(argv)
+    if args.accumulate_steps < 1:
+        p.error("--accumulate_steps must be at least 1")
+    return args
+
+
+def startup_line(micro_batch, accumulate, world):
+    """what the trainer prints once: the batch an optimizer step averages over"""
+    return "[train] micro-batch {} x accumulate_steps {} x world {} = effective batch {}".format(
+        micro_batch, accumulate, world, micro_batch * accumulate * world)
 
 
 def _raw_conf(path):
@@ -143,23 +159,27 @@ def val_phase(args):
 
 
 def make_loader(data_dir, spec, phase, hp, model, data_opts, n_repeat=1, seed=0, rank=0, world=1, resize=False, resident=False,
-                budget_bytes=None):
+                budget_bytes=None, accumulate=1):
     """the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, shuffled in the train phase only;
     `resize`: frames stored at another size are resized to hp.img_sz in the batch assembly (--resize_frames);
     `resident`: the split is uploaded once and the batches are assembled from it on the device (--device_dataset, dataset_resident.py;
-    at most `budget_bytes` of it, a top-rendered dataset raises)"""
+    at most `budget_bytes` of it, a top-rendered dataset raises);
+    `accumulate`: k micro-batches per optimizer step (--accumulate_steps): the pass walks dataset.accumulate_schedule"""
     from .dataset import HostFedLoader, VideoDataset
     ds = VideoDataset(data_dir, spec, phase, hp.img_sz, resize=resize, **data_opts)
     if resident:
         from .dataset_resident import ResidentLoader
-        return ResidentLoader(ds, model, hp.batch_size, n_repeat=n_repeat, seed=seed, rank=rank, world=world, budget_bytes=budget_bytes)
-    return HostFedLoader(ds, model, hp.batch_size, n_repeat=n_repeat, seed=seed, rank=rank, world=world)
+        return ResidentLoader(ds, model, hp.batch_size, n_repeat=n_repeat, seed=seed, rank=rank, world=world, budget_bytes=budget_bytes,
+                              accumulate=accumulate)
+    return HostFedLoader(ds, model, hp.batch_size, n_repeat=n_repeat, seed=seed, rank=rank, world=world, accumulate=accumulate)
 
 
 class SyntheticLoader:
-    """Seeded synthetic batches: a different shard per rank, a different batch per step."""
+    """Seeded synthetic batches: a different shard per rank, a different batch per step.
+    accumulate = k: k * (n_batches // k) batches, so that a pass ends on a cycle boundary."""
 
-    def __init__(self, hp, n_batches, seed, device, variant="B"):
+    def __init__(self, hp, n_batches, seed, device, variant="B", accumulate=1):
+        n_batches = int(accumulate) * (n_batches // int(accumulate))
         self.hp, self.n, self.seed, self.device, self.variant = hp, n_batches, seed, device, variant
 
     def __len__(self):
@@ -226,6 +246,11 @@ class ModelTrainer:
         guard = getattr(args, "nan_guard", "off")
         self.nan_guard = None if guard in (None, "off") else guard
         guard_kw = {"nan_guard": self.nan_guard} if self.nan_guard else {}
+        self.accumulate = k_acc = int(getattr(args, "accumulate_steps", 1) or 1)
+        if k_acc > 1:
+            guard_kw["accumulate"] = k_acc
+        if self.rank == 0:
+            print(startup_line(hp.batch_size, k_acc, max(self.world, 1)), flush=True)
         self.trainer = step_cls(self.model, lr=lr, betas=(conf.get("adam_beta", 0.9), 0.999), process_group=pg,
                                 optimizer=conf.get("optimizer", "radam"), momentum=conf.get("momentum", 0),
                                 gradient_clip=conf.get("gradient_clip"), **guard_kw)       # gcp_builder.py:174-186,255-263
@@ -234,15 +259,16 @@ class ModelTrainer:
             # the reference's loaders (gcp_builder.py:100-103,105-120): epoch_cycles_train passes per epoch, val / test unshuffled
             reps = int(conf.get("epoch_cycles_train", 1))
             gb = getattr(args, "device_dataset_gb", None)
-            mk = lambda phase: make_loader(self.data_dir, spec, phase, hp, self.model, data_opts, n_repeat=reps, seed=seed, rank=self.rank,
-                                           world=max(self.world, 1), resize=bool(getattr(args, "resize_frames", 0)),
-                                           resident=bool(getattr(args, "device_dataset", 0)),
-                                           budget_bytes=None if gb is None else int(gb * 2 ** 30))
-            train_loader = train_loader or mk("train")
+            # (validation is not accumulated: its loader walks the plain schedule)
+            mk = lambda phase, k=1: make_loader(self.data_dir, spec, phase, hp, self.model, data_opts, n_repeat=reps, seed=seed,
+                                                rank=self.rank, world=max(self.world, 1), resize=bool(getattr(args, "resize_frames", 0)),
+                                                resident=bool(getattr(args, "device_dataset", 0)),
+                                                budget_bytes=None if gb is None else int(gb * 2 ** 30), accumulate=k)
+            train_loader = train_loader or mk("train", k_acc)
             val_loader = val_loader or mk(val_phase(args))
         if not args.feed_random_data and train_loader is None:
             raise ValueError("no dataset reader ships with this build: pass --feed_random_data 1 or give ModelTrainer a loader")
-        self.train_loader = train_loader or SyntheticLoader(hp, nb, 1000 + 100000 * self.rank, self.device)
+        self.train_loader = train_loader or SyntheticLoader(hp, nb, 1000 + 100000 * self.rank, self.device, accumulate=k_acc)
         self.val_loader = val_loader or SyntheticLoader(hp, max(1, nb // 5), 500000 + 100000 * self.rank, self.device)
         self.global_step = 0
         self.log = []
@@ -365,7 +391,10 @@ class ModelTrainer:
             self.train_loader.set_epoch(epoch)          # the dataset loader's shuffle and draws are keyed on the epoch
         end = time.time()
         # train.py:147 (an epoch shorter than --imepoch batches logs every step instead of dividing by zero)
-        images_interval = max(1, int(len(self.train_loader) / max(1, getattr(self.cmd_args, "imepoch", 4)))) if self.log_images else 0
+        k_acc = self.accumulate
+        images_interval = max(1, int(len(self.train_loader) // k_acc / max(1, getattr(self.cmd_args, "imepoch", 4)))) if self.log_images else 0
+        if k_acc > 1:
+            self.trainer.reset_accumulation()          # a pass ends on a cycle boundary; a loader that was cut short leaves no partial cycle
         slog = self.scalar_log
         tick, data_time, n_timed = time.time(), 0.0, 0          # (--log_scalars only) time spent waiting for the loader
         for batch_idx, inputs in enumerate(self.train_loader):
@@ -376,12 +405,21 @@ class ModelTrainer:
             except ValueError as err:                  # --nan_guard raise: the reference's hook (gcp_builder.py:99-103)
                 from .health import NonFiniteGradients
                 if isinstance(err, NonFiniteGradients) and self.rank == 0:
+                    if k_acc > 1:
+                        print("[train] --accumulate_steps {}: the gradient is the sum over {} micro-batches; the inputs dumped are "
+                              "the LAST micro-batch's".format(k_acc, k_acc), flush=True)
                     self.dump_nan_debug(err, inputs, epoch)
                 raise
+            if not self.trainer.stepped:               # a micro-step of an accumulation cycle: no optimizer step yet
+                if slog is not None:
+                    tick = time.time()
+                continue
             self.model.step()                          # train.py:163
             if self.log_images and self.global_step % images_interval == 0:          # train.py:125-126,170-172
                 self.image_files += self.model.log_outputs(out, inputs, None, self.global_step, True, "train")
             if self.global_step % self.cmd_args.log_outputs_interval == 0:
+                if k_acc > 1:                          # the cycle's mean loss vector stands in for the last micro-batch's below
+                    last_losses, out.raw["losses"] = out.raw["losses"], self.trainer.mean_losses()
                 total = float(out.raw["losses"][5])    # the only host sync of the loop, on logging steps
                 self.log.append((self.global_step, total))
                 batch_time = (time.time() - end) / max(1, self.cmd_args.log_outputs_interval)
@@ -391,6 +429,8 @@ class ModelTrainer:
                 if slog is not None:
                     self.log_train_scalars(out, inputs, total, batch_time, data_time / max(n_timed, 1))
                     data_time, n_timed = 0.0, 0
+                if k_acc > 1:
+                    out.raw["losses"] = last_losses
                 end = time.time()
             self.global_step += 1
             if slog is not None:

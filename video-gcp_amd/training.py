@@ -38,17 +38,30 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
     OPTIMIZERS = {"radam": 0, "adam": 1, "rmsprop": 2, "sgd": 3}
     _early_on, _caller, last_bplan_caller_lane = False, None, False          # (see __init__: early_optimizer)
     _pending_slices = ()
+    accumulate, micro_index, stepped, _accumulating, _grad_div = 1, 0, False, False, 1      # (see __init__: accumulate)
     NAN_GUARDS = (None, "raise", "skip")
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, optimizer="radam", momentum=0.0,
-                 gradient_clip=None, nan_guard=None):
+                 gradient_clip=None, nan_guard=None, accumulate=1):
         """optimizer / momentum / gradient_clip: the trainer's `optimizer` ('radam' default, 'adam', 'rmsprop', 'sgd'), `momentum`
         (RMSprop / SGD) and `gradient_clip` settings (gcp_builder.py:174-186,255-263).
         nan_guard: None (nothing is tested: the step as it always was), "raise" or "skip" -- the reference's NanGradHook
         (base_trainer.py:20-66) as a device kernel between the backward and the optimizer (health.py): one gcpx_grad_health over the
         whole (all-reduced) gradient and the loss vector writes the gate of the optimizer state, and the step kernels and the tick
         return at entry when it is closed.  "raise": step() then reads the 32-byte summary and raises NonFiniteGradients; "skip": no
-        sync, training goes on, health() holds the counts.  Either way a non-finite gradient never reaches theta or the moments."""
+        sync, training goes on, health() holds the counts.  Either way a non-finite gradient never reaches theta or the moments.
+        accumulate: k > 1 makes `step()` one MICRO-step of a cycle of k (gradient accumulation, no reference counterpart: the k
+        micro-batches stand for the k replicas of nn.DataParallel, gcp_builder.py:71-78, each with its own BatchNorm statistics).  Micro-
+        steps 1 .. k-1 run forward + backward and fold self.grad into a second flat vector (gcpx_grad_accumulate: assign on the first,
+        add afterwards) -- no optimizer, re-pack, tick, clip norm, health launch or collective; micro-step k adds that vector into
+        self.grad and runs the optimizer path as it stands with grad_scale = 1 / (k world).  The early optimizer slices and the overlap
+        of the bucket all-reduces with the backward are off for k > 1 (as under gradient_clip: they need the cycle's whole sum).
+        `micro_index`: position in the cycle; `stepped`: whether the last step() applied the optimizer; `mean_losses()`: the loss vector's
+        mean over the cycle.  1: the step as it always was -- no buffer, no launch."""
+        if int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError("accumulate must be a positive number of micro-batches, not {!r}".format(accumulate))
+        self.accumulate, self.micro_index, self.stepped = int(accumulate), 0, False
+        self._accumulating, self._grad_div, self._acc, self._loss_acc = False, 1, None, None
         if optimizer not in self.OPTIMIZERS:
             raise ValueError("Optimizer '{}' not supported!".format(optimizer))          # gcp_builder.py:185
         if nan_guard not in self.NAN_GUARDS:
@@ -72,6 +85,9 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self.exp_avg = torch.zeros_like(model.theta)
         self.exp_avg_sq = torch.zeros_like(model.theta)
         self.opt_state = torch.zeros(4, device=model.device)
+        if self.accumulate > 1:
+            self._acc = torch.zeros_like(model.theta)          # the sum of the cycle's earlier micro-gradients
+            self._loss_acc = torch.zeros(16, device=model.device)          # ... and of its loss vectors (out.raw["losses"])
         from .dist import GradBuckets, gradient_bucket_ranges
         ranges = gradient_bucket_ranges(model._poff, hp.hierarchy_levels, hp.untied_layers)
         self._ranges = ranges
@@ -151,8 +167,9 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
     def backward(self, inputs, noise=None):
         """forward (phase 'train', losses on device) + backward; gradients in self.grad.  Returns the forward outputs."""
         m = self.m
-        if self.buckets is not None:
+        if self.buckets is not None and not self._accumulating:
             self.buckets.begin()          # a backward without an optimizer step in between must exchange its buckets again
+        self._grad_div = 1                # self.grad is one batch's gradient again (gradient_stats)
         out = m.forward(inputs, "train", noise)
         if "losses" not in out.raw:
             raise ValueError("the training step needs traj_seq and pad_mask")
@@ -198,8 +215,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         if tag == "slices":
             self._issue_pending_slices()
             return
-        if tag != "bucket" or (self.buckets is None and not self._early_on):
-            return
+        if tag != "bucket" or (self.buckets is None and not self._early_on) or self._accumulating:
+            return                        # (a micro-step of an accumulation cycle: the collectives run once, on the cycle's sum)
         if self._lane_streams is None:
             self._lane_streams = [torch.cuda.ExternalStream(int(s.value if hasattr(s, "value") else s), device=self.m.device)
                                   for s in self._backward_streams()]
@@ -284,6 +301,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         if self.buckets is not None:
             # the tree-level buckets were started during the backward; the last one (conv stacks, heads, level 0) goes now
             scale = self.buckets.finish()
+        if self._grad_div > 1:
+            scale = 1.0 / (self._grad_div * round(1.0 / scale))        # the mean over the cycle's micro-batches and the ranks
         if self.nan_guard:
             # the whole gradient is final here (data-parallel: the ranks' sum, the same bits on every rank, so every rank reaches the
             # same verdict without a further collective); the verdict lands in opt_state[3] before anything below reads it
@@ -325,6 +344,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         m.repack(st)
 
     def step(self, inputs, noise=None):
+        if self.accumulate > 1:
+            return self._micro_step(inputs, noise)
         # (no early slices under a nan_guard either: the verdict needs the whole gradient, as the clipping norm does)
         self._early_on = self.early_optimizer and not self.gradient_clip and not self.nan_guard and len(self._ranges) > 1
         if self._early_on and self._clip_state_dirty:
@@ -335,7 +356,47 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         finally:
             self._early_on = False
         self.optimizer_step(out)
+        self.stepped = True
         return out
+
+    # ---- gradient accumulation (accumulate > 1) ----
+    def _micro_step(self, inputs, noise):
+        """step() with accumulate = k > 1: micro-step `micro_index` of the cycle.  Everything the optimizer path reads is in place
+        after the last one: self.grad holds the cycle's sum, the health check sees it and the summed loss vector."""
+        m, k, j = self.m, self.accumulate, self.micro_index
+        self._early_on, self._accumulating, self.stepped = False, True, False
+        try:
+            out = self.backward(inputs, noise)
+        finally:
+            self._accumulating = False
+        st = torch.cuda.current_stream(m.device).cuda_stream          # (the backward has been joined onto it)
+        n, lv = self.grad.numel(), out.raw["losses"]
+        acc = m.lib.gcpx_grad_accumulate
+        rt.check(acc(self._loss_acc.data_ptr(), lv.data_ptr(), lv.numel(), 1 if j == 0 else 0, 1, st), "grad_accumulate")
+        if j < k - 1:
+            rt.check(acc(self._acc.data_ptr(), self.grad.data_ptr(), n, 1 if j == 0 else 0, 0, st), "grad_accumulate")
+            self.micro_index = j + 1
+            return out
+        rt.check(acc(self.grad.data_ptr(), self._acc.data_ptr(), n, 0, 0, st), "grad_accumulate")
+        self.micro_index, self._grad_div = 0, k
+        if self.buckets is not None:
+            self.buckets.begin()          # nothing was exchanged during the micro-steps: finish() reduces every bucket of the sum
+        if self.nan_guard:
+            self._health_extra = self._loss_acc
+        self.stepped = True               # (also when the guard drops or raises: the cycle is over)
+        self.optimizer_step(out)
+        return out
+
+    def reset_accumulation(self):
+        """drops a partial cycle: the next step() is the first micro-step again (pass ends, load_optimizer_state)"""
+        self.micro_index, self.stepped = 0, False
+
+    def mean_losses(self):
+        """the loss vector (out.raw["losses"]) averaged over the micro-batches of the cycle that just completed: a device tensor, no
+        sync.  Without accumulation there is nothing to average: call it with accumulate > 1."""
+        if self.accumulate == 1:
+            raise ValueError("mean_losses() is the cycle mean of a trainer with accumulate > 1; read out.raw['losses'] instead")
+        return self._loss_acc / float(self.accumulate)
 
     # ---- the training guard (health.py) ----
     def _grad_health(self):
@@ -373,6 +434,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
                 "optimizer": self.optimizer, "momentum": self.momentum, "gradient_clip": self.gradient_clip}
 
     def load_optimizer_state(self, st):
+        self.reset_accumulation()
         self.exp_avg.copy_(st["exp_avg"])
         self.exp_avg_sq.copy_(st["exp_avg_sq"])
         state = torch.as_tensor(st["state"]).detach().to("cpu", torch.float32, copy=True)
@@ -403,6 +465,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         scale = 1.0
         if self.buckets is not None and torch.distributed.is_initialized():
             scale = 1.0 / torch.distributed.get_world_size(self.buckets.group)
+        if self._grad_div > 1:            # after a completed accumulation cycle: the buffer holds the sum of its micro-gradients
+            scale = 1.0 / (self._grad_div * round(1.0 / scale))
         st = torch.cuda.current_stream(self.m.device).cuda_stream
         seg_norm, stats = self._grad_stats.launch(self.m.lib, self.grad, scale, self.opt_state.data_ptr() + 4, st)
         return Outputs(names=self._grad_stats.names, seg_norm=seg_norm, stats=stats)
