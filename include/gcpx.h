@@ -1028,6 +1028,28 @@ int gcpx_dlm_mean_bwd(const float* params, const float* dimg, float* dparams, fl
 int gcpx_attention_bwd(const float* q, const float* k, const float* v, const float* att, const float* d_out, const int64_t* end_ind,
                        const float* temperature, float* dS, float* dq, float* dtemp_row, float* dK, int64_t ldk, float* dV, int64_t ldv,
                        int32_t M, int32_t rpb, int32_t T, int32_t dk, int32_t nz, void* stream);
+/* backward of gcpx_attention with `heads` heads (blox MultiheadAttention as called at adaptive_binding/attentive_inference.py:81;
+ *   hyperparameters.py:24 n_attention_heads).  The forward keeps only the head-averaged weights, which carry no gradient (they are
+ *   logged) and are the softmax of no head: the probabilities of head h are computed again from q, k, end_ind and the temperature, by
+ *   the forward's own arithmetic.  With dh = dk / heads, vh = nz / heads, per head h:
+ *     a = softmax over [0, end_ind[b]] of q_h . k_h[t] / sqrt(dh) / temp,  dA[t] = dO_h . V_h[t],  dS = a * (dA - sum_t a dA),
+ *     dq_h = sum_t dS[t] k_h[t] / (sqrt(dh) temp),  dK_h[b][t] = sum_j dS[(b, j)][t] q_h[(b, j)] / (sqrt(dh) temp),
+ *     dV_h[b][t] = sum_j a[(b, j)][t] dO_h[(b, j)],  dtemp_row[r] = - sum_h sum_t dS[t] score[t] / temp.
+ *   Arguments as gcpx_attention_bwd, except: no att; stats [M][heads][2] scratch (maximum and sum of each softmax, written by the
+ *   row launch for the key / value launch); dS [M][heads][T] scratch.  Every element of dq, dtemp_row and of the [B][T] rows of
+ *   dK / dV is written (zeros past end_ind).  Sums run in a fixed order, no atomics; with heads = 1 the results have the bits of
+ *   gcpx_attention_bwd.  T <= 4096; head widths multiples of 4, dh / 4 and vh / 4 divisors of 256; rpb * heads <= 8192. */
+int gcpx_attention_bwd_heads(const float* q, const float* k, const float* v, const float* d_out, const int64_t* end_ind,
+                             const float* temperature, float* stats, float* dS, float* dq, float* dtemp_row, float* dK, int64_t ldk,
+                             float* dV, int64_t ldv, int32_t M, int32_t rpb, int32_t T, int32_t dk, int32_t nz, int32_t heads,
+                             void* stream);
+/* Row layer-norm without affine between the attention layers (F.layer_norm(x, x.shape[1:]) at attentive_inference.py:82-83;
+ *   hyperparameters.py:25 n_attention_layers): y[r] = (s - mean(s)) / sqrt(var(s) + eps), s = x[r] (+ add[r] if add is not NULL),
+ *   biased variance; x, add, y dense [M][W], W a multiple of 4 up to 1024; rstd [M] = 1 / sqrt(var + eps) for the backward, or NULL. */
+int gcpx_row_layernorm(const float* x, const float* add, float* y, float* rstd, int32_t M, int32_t W, float eps, void* stream);
+/* its backward from the saved y and rstd: dx[r] = rstd[r] * (dy[r] - mean(dy[r]) - y[r] * mean(dy[r] * y[r])); with an addend the
+ *   same dx is the gradient of both summands */
+int gcpx_row_layernorm_bwd(const float* dy, const float* y, const float* rstd, float* dx, int32_t M, int32_t W, void* stream);
 
 /* ---- collectives of the data-parallel paths: RCCL over xGMI, one communicator per process (one process
  *   per GPU), enqueued on the caller's stream, no synchronisation.  Replaces nn.DataParallel's gradient reduce

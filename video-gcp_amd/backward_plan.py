@@ -9,7 +9,7 @@ import torch
 
 from . import packing as pk
 from . import runtime as rt
-from .plan_ops import _Plan, _addr, N_LANES
+from .plan_ops import _Plan, _addr, N_LANES, attn_layer_suffix
 from .params import decoder_layers
 
 
@@ -160,8 +160,8 @@ class BackwardPlanMixin:
             plan.add("bw.addrows", lib.gcpx_add_rows, _addr(dE, nz), PS * nz, nz, dE_dec.data_ptr(), dE_ex.data_ptr(), B, N, nz)
         if attentive:
             kv = rec["attn_kv"]
-            n_mod, dk = kv["n_mod"], hp.nz_attn_key
-            dKp, dVp = buf("bw.dKp", (B * T, n_mod * dk)), buf("bw.dVp", (B * T, n_mod * nz))
+            n_mod, nblk, dk = kv["n_mod"], kv["nblk"], hp.nz_attn_key
+            dKp, dVp = buf("bw.dKp", (B * T, nblk * dk)), buf("bw.dVp", (B * T, nblk * nz))
             if n_mod < L:       # tied levels accumulate: not built
                 raise NotImplementedError("attentive training with tied tree layers")
 
@@ -329,11 +329,13 @@ class BackwardPlanMixin:
                 # this level's column block of dKp / dVp is final now: its k_proj / v_proj weight gradients belong to the level's
                 # module (and to its bucket of the data-parallel exchange), so they go out with this level's flush, in front of
                 # the bucket mark — issued after the tree loop they were written into a slice whose all-reduce had already started
-                a_ = f"tree_module.tree_modules.{li}.inference.attention.attention_layers.0"
-                self._wgrad(plan, f"attn.k_proj{l}", _addr(dKp, li * dk), n_mod * dk, B * T, dk, kv["keys"].data_ptr(), dk,
-                            self.g(f"{a_}.k_proj.weight"), ldw=dk, sr=dk, sb=B * T * dk, rpb=B * T, dbias=self.g(f"{a_}.k_proj.bias"))
-                self._wgrad(plan, f"attn.v_proj{l}", _addr(dVp, li * nz), n_mod * nz, B * T, nz, o["inf_enc_seq"].data_ptr(), nz,
-                            self.g(f"{a_}.v_proj.weight"), ldw=nz, sr=nz, sb=B * T * nz, rpb=B * T, dbias=self.g(f"{a_}.v_proj.bias"))
+                for i in range(hp.n_attention_layers):
+                    a_, sfx = f"tree_module.tree_modules.{li}.inference.attention.attention_layers.{i}", attn_layer_suffix(i)
+                    blk = li * hp.n_attention_layers + i
+                    self._wgrad(plan, f"attn.k_proj{l}{sfx}", _addr(dKp, blk * dk), nblk * dk, B * T, dk, kv["keys"].data_ptr(), dk,
+                                self.g(f"{a_}.k_proj.weight"), ldw=dk, sr=dk, sb=B * T * dk, rpb=B * T, dbias=self.g(f"{a_}.k_proj.bias"))
+                    self._wgrad(plan, f"attn.v_proj{l}{sfx}", _addr(dVp, blk * nz), nblk * nz, B * T, nz, o["inf_enc_seq"].data_ptr(), nz,
+                                self.g(f"{a_}.v_proj.weight"), ldw=nz, sr=nz, sb=B * T * nz, rpb=B * T, dbias=self.g(f"{a_}.v_proj.bias"))
             self._mlp_bwd(plan, f"prior{l}", f"{p}.prior", rec[f"mlp:prior{l}"], Wt["prior"], dp.data_ptr(), 2 * nv,
                           [(dXp.data_ptr(), n * 2 * nz, 2 * nz)], group=grp)
             self._mlp_bwd_group(plan, f"level{l}", grp)
@@ -364,9 +366,9 @@ class BackwardPlanMixin:
             # values: d inf_enc_seq = [dV'_0 | dV'_1 | ...] @ [Wv_0; ...]; keys: the same through k_proj, the per-frame key Linear
             # and the second temporal encoder (base_gcp.py:122-123, :200)
             dense = lambda t, w: m._rowsrc(t.data_ptr(), 0, w, w)
-            self._dgemm(plan, "attn.v_proj", [dense(dVp, n_mod * nz)], B * T, nz, B * T, self.bk["attn.v_proj.wT"], d_inf.data_ptr(), 0, nz)
+            self._dgemm(plan, "attn.v_proj", [dense(dVp, kv["nblk"] * nz)], B * T, nz, B * T, self.bk["attn.v_proj.wT"], d_inf.data_ptr(), 0, nz)
             dkeys = buf("bw.dkeys", (B * T, dk))
-            self._dgemm(plan, "attn.k_proj", [dense(dKp, n_mod * dk)], B * T, dk, B * T, self.bk["attn.k_proj.wT"], dkeys.data_ptr(), 0, dk)
+            self._dgemm(plan, "attn.k_proj", [dense(dKp, kv["nblk"] * dk)], B * T, dk, B * T, self.bk["attn.k_proj.wT"], dkeys.data_ptr(), 0, dk)
             self._wgrad(plan, "kseq.key", dkeys.data_ptr(), dk, B * T, dk, kv["kenc"].data_ptr(), nz,
                         self.g("inf_key_encoder.1.linear.weight"), ldw=nz, sr=nz, sb=B * T * nz, rpb=B * T,
                         dbias=self.g("inf_key_encoder.1.linear.bias"))

@@ -8,7 +8,7 @@ import torch
 
 from . import packing as pk
 from . import runtime as rt
-from .plan_ops import _Plan, _addr, N_LANES
+from .plan_ops import _Plan, _addr, N_LANES, attn_layer_suffix
 from .params import decoder_layers
 
 
@@ -240,38 +240,68 @@ class BackwardStagesMixin:
 
     # ---- attention of the attentive posterior (attentive_inference.py:47-86), one tree level ----
     def _attention_backward(self, plan, fplan, l, Wt, dEt, dKp, dVp, B):
-        """dEt [M, nz] = gradient of e_tilde.  Writes this level's column block of dKp / dVp (projected keys / values) and
-        returns dXa [M, 2 nz], the gradient w.r.t. the query network's inputs (e_l | e_r)."""
+        """dEt [M, nz] = gradient of e_tilde.  Writes this level's column blocks of dKp / dVp (projected keys / values, one block per
+        attention layer) and returns dXa [M, 2 nz], the gradient w.r.t. the query network's inputs (e_l | e_r).  The layers are walked
+        last first: only the last layer's raw feeds Attention.out; raw_i of an earlier layer gets its gradient through
+        x = LN(raw_i) -> predictor_layers[i] -> LN(. + query_i) = query_{i+1}, and query_i gets the same layer-norm gradient again."""
         m, hp, lib = self.m, self.m._hp, self.m.lib
         rec = fplan.rec
         ar = rec["attn"][l]
         kv = rec["attn_kv"]
         M, n, li = ar["M"], ar["n"], ar["li"]
-        T, nz, dk = hp.max_seq_len, hp.nz_enc, hp.nz_attn_key
-        n_mod = kv["n_mod"]
+        T, nz, dk, heads = hp.max_seq_len, hp.nz_enc, hp.nz_attn_key, hp.n_attention_heads
+        nblk, Ln = kv["nblk"], len(ar["layers"])
         buf = m._buf
         a_ = f"tree_module.tree_modules.{li}.inference.attention"
         dense = lambda t, w: m._rowsrc(t.data_ptr(), 0, w, w)
         lin = lambda tag, dy, x, N, K, name: self._wgrad(plan, tag, dy.data_ptr(), N, M, N, x.data_ptr(), K, self.g(f"{name}.weight"),
                                                          ldw=K, sr=K, sb=M * K, rpb=M, dbias=self.g(f"{name}.bias"))
         # e_tilde = out(raw); raw = out_proj(o)
-        lin(f"attn.out{l}", dEt, ar["raw"], nz, nz, f"{a_}.out")
+        lin(f"attn.out{l}", dEt, ar["layers"][-1]["raw"], nz, nz, f"{a_}.out")
         draw = buf(f"bw.attn.draw{l}", (M, nz))
         self._dgemm(plan, f"attn.out{l}", [dense(dEt, nz)], M, nz, M, Wt["attn.out.wT"], draw.data_ptr(), 0, nz)
-        lin(f"attn.out_proj{l}", draw, ar["o"], nz, nz, f"{a_}.attention_layers.0.out_proj")
-        do = buf(f"bw.attn.do{l}", (M, nz))
-        self._dgemm(plan, f"attn.out_proj{l}", [dense(draw, nz)], M, nz, M, Wt["attn.out_proj.wT"], do.data_ptr(), 0, nz)
-        # softmax attention
-        dS, dqp, dtr = buf(f"bw.attn.dS{l}", (M, T)), buf(f"bw.attn.dq{l}", (M, dk)), buf(f"bw.attn.dtemp{l}", (M,))
-        plan.add(f"bw.attn{l}", lib.gcpx_attention_bwd, ar["qp"].data_ptr(), _addr(kv["Kp"], li * B * T * dk), _addr(kv["Vp"], li * B * T * nz),
-                 ar["gamma"].data_ptr(), do.data_ptr(), fplan.rec["tin"]["end_ind"].data_ptr(), ar["temp"].data_ptr(), dS.data_ptr(),
-                 dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, li * dk), n_mod * dk, _addr(dVp, li * nz), n_mod * nz, M, n, T, dk, nz)
-        self._side(plan, f"bw.attn.dtemp:{l}", lib.gcpx_reduce_partials, dtr.data_ptr(), M, 1, 1,
-                   self.g(f"{a_}.attention_layers.0.temperature"), 1)
-        # q' = q_proj(query MLP(e_l, e_r))
-        lin(f"attn.q_proj{l}", dqp, ar["qin"], dk, dk, f"{a_}.attention_layers.0.q_proj")
-        dqin = buf(f"bw.attn.dqin{l}", (M, dk))
-        self._dgemm(plan, f"attn.q_proj{l}", [dense(dqp, dk)], M, dk, M, Wt["attn.q_proj.wT"], dqin.data_ptr(), 0, dk)
+        dqin = None                                            # gradient of the query the layer above read
+        for i in reversed(range(Ln)):
+            lay, sfx = ar["layers"][i], attn_layer_suffix(i)
+            al = f"{a_}.attention_layers.{i}"
+            dq_ln = None
+            if i < Ln - 1:
+                # query_{i+1} = LN(predictor_layers[i](LN(raw_i)) + query_i)
+                dq_ln = buf(f"bw.attn.dq_ln{l}{sfx}", (M, dk))
+                plan.add(f"bw.attn.ln_q{l}{sfx}", lib.gcpx_row_layernorm_bwd, dqin.data_ptr(), lay["qn"].data_ptr(), lay["rs_q"].data_ptr(),
+                         dq_ln.data_ptr(), M, dk)
+                dx = buf(f"bw.attn.dx{l}{sfx}", (M, nz))
+                self._mlp_bwd(plan, f"attn.pred{l}{sfx}", f"{a_}.predictor_layers.{i}", rec[f"mlp:attn.pred{l}{sfx}"], Wt[f"attn.pred{sfx}"],
+                              dq_ln.data_ptr(), dk, [(dx.data_ptr(), M * nz, nz)])
+                draw = buf(f"bw.attn.draw_ln{l}{sfx}", (M, nz))
+                plan.add(f"bw.attn.ln_x{l}{sfx}", lib.gcpx_row_layernorm_bwd, dx.data_ptr(), lay["x"].data_ptr(), lay["rs_x"].data_ptr(),
+                         draw.data_ptr(), M, nz)
+            lin(f"attn.out_proj{l}{sfx}", draw, lay["o"], nz, nz, f"{al}.out_proj")
+            do = buf(f"bw.attn.do{l}{sfx}", (M, nz))
+            self._dgemm(plan, f"attn.out_proj{l}{sfx}", [dense(draw, nz)], M, nz, M, Wt[f"attn.out_proj{sfx}.wT"], do.data_ptr(), 0, nz)
+            # softmax attention
+            dqp, dtr = buf(f"bw.attn.dq{l}{sfx}", (M, dk)), buf(f"bw.attn.dtemp{l}{sfx}", (M,))
+            blk = lay["blk"]
+            Kb, Vb = _addr(kv["Kp"], blk * B * T * dk), _addr(kv["Vp"], blk * B * T * nz)
+            end_ind = fplan.rec["tin"]["end_ind"].data_ptr()
+            if heads == 1 and not self.attn_bwd_heads_export:
+                dS = buf(f"bw.attn.dS{l}{sfx}", (M, T))
+                plan.add(f"bw.attn{l}{sfx}", lib.gcpx_attention_bwd, lay["qp"].data_ptr(), Kb, Vb, lay["gamma"].data_ptr(), do.data_ptr(), end_ind,
+                         lay["temp"].data_ptr(), dS.data_ptr(), dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, blk * dk), nblk * dk,
+                         _addr(dVp, blk * nz), nblk * nz, M, n, T, dk, nz)
+            else:
+                # the saved weights are the mean over heads: the per-head probabilities are computed again (gcpx_attention_bwd_heads)
+                dS, stats = buf(f"bw.attn.dS{l}{sfx}", (M, heads, T)), buf(f"bw.attn.stats{l}{sfx}", (M, heads, 2))
+                plan.add(f"bw.attn{l}{sfx}", lib.gcpx_attention_bwd_heads, lay["qp"].data_ptr(), Kb, Vb, do.data_ptr(), end_ind,
+                         lay["temp"].data_ptr(), stats.data_ptr(), dS.data_ptr(), dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, blk * dk),
+                         nblk * dk, _addr(dVp, blk * nz), nblk * nz, M, n, T, dk, nz, heads)
+            self._side(plan, f"bw.attn.dtemp:{l}{sfx}", lib.gcpx_reduce_partials, dtr.data_ptr(), M, 1, 1, self.g(f"{al}.temperature"), 1)
+            # q' = q_proj(query_i)
+            lin(f"attn.q_proj{l}{sfx}", dqp, lay["qin"], dk, dk, f"{al}.q_proj")
+            dqin = buf(f"bw.attn.dqin{l}{sfx}", (M, dk))
+            self._dgemm(plan, f"attn.q_proj{l}{sfx}", [dense(dqp, dk)], M, dk, M, Wt[f"attn.q_proj{sfx}.wT"], dqin.data_ptr(), 0, dk)
+            if dq_ln is not None:
+                plan.add(f"bw.attn.addq{l}{sfx}", lib.gcpx_add_rows, dqin.data_ptr(), 0, dk, dq_ln.data_ptr(), None, 1, M, dk)
         dXa = buf(f"bw.dXa{l}", (M, 2 * nz))
         self._mlp_bwd(plan, f"attn.query{l}", f"{a_}.query_net", rec[f"mlp:attn.query{l}"], Wt["attn.query"], dqin.data_ptr(), dk,
                       [(dXa.data_ptr(), n * 2 * nz, 2 * nz)])

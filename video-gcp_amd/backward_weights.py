@@ -8,7 +8,7 @@ import torch
 
 from . import packing as pk
 from . import runtime as rt
-from .plan_ops import _Plan, _addr, N_LANES
+from .plan_ops import _Plan, _addr, N_LANES, attn_layer_suffix
 from .params import decoder_layers
 
 
@@ -188,10 +188,11 @@ class BackwardWeightsMixin:
                 X[f"kseq.{nm}.wT"] = pk.pack_gemm(w.permute(1, 2, 0).reshape(w.shape[1], -1))
             X["kseq.key.wT"] = pk.pack_gemm(sd["inf_key_encoder.1.linear.weight"].t().contiguous())                # [nz][dk]
             n_mod = hp.hierarchy_levels if hp.untied_layers else 1
-            att = lambda l, nm: sd[f"tree_module.tree_modules.{l}.inference.attention.attention_layers.0.{nm}.weight"]
-            # d keys = [dK'_0 | dK'_1 | ...] @ [Wk_0; Wk_1; ...]: one GEMM over the level blocks laid side by side
-            X["attn.k_proj.wT"] = pk.pack_gemm(torch.cat([att(l, "k_proj") for l in range(n_mod)], 0).t().contiguous())   # [dk][n_mod*dk]
-            X["attn.v_proj.wT"] = pk.pack_gemm(torch.cat([att(l, "v_proj") for l in range(n_mod)], 0).t().contiguous())   # [nz][n_mod*nz]
+            att = lambda l, i, nm: sd[f"tree_module.tree_modules.{l}.inference.attention.attention_layers.{i}.{nm}.weight"]
+            blocks = [(l, i) for l in range(n_mod) for i in range(hp.n_attention_layers)]
+            # d keys = [dK'_0 | dK'_1 | ...] @ [Wk_0; Wk_1; ...]: one GEMM over the (level, layer) blocks laid side by side
+            X["attn.k_proj.wT"] = pk.pack_gemm(torch.cat([att(l, i, "k_proj") for l, i in blocks], 0).t().contiguous())   # [dk][blocks*dk]
+            X["attn.v_proj.wT"] = pk.pack_gemm(torch.cat([att(l, i, "v_proj") for l, i in blocks], 0).t().contiguous())   # [nz][blocks*nz]
         for l in range(hp.hierarchy_levels if hp.untied_layers else 1):
             p = f"tree_module.tree_modules.{l}"
             T = {}
@@ -218,8 +219,12 @@ class BackwardWeightsMixin:
             if hp.attentive_inference:
                 a = f"{p}.inference.attention"
                 T["attn.query"] = self._pack_predictor_T(sd, f"{a}.query_net", [(0, 2 * nz)])
-                T["attn.q_proj.wT"] = pk.pack_gemm(sd[f"{a}.attention_layers.0.q_proj.weight"].t().contiguous())
-                T["attn.out_proj.wT"] = pk.pack_gemm(sd[f"{a}.attention_layers.0.out_proj.weight"].t().contiguous())
+                for i in range(hp.n_attention_layers):
+                    sfx = attn_layer_suffix(i)
+                    T[f"attn.q_proj{sfx}.wT"] = pk.pack_gemm(sd[f"{a}.attention_layers.{i}.q_proj.weight"].t().contiguous())
+                    T[f"attn.out_proj{sfx}.wT"] = pk.pack_gemm(sd[f"{a}.attention_layers.{i}.out_proj.weight"].t().contiguous())
+                    if i < hp.n_attention_layers - 1:
+                        T[f"attn.pred{sfx}"] = self._pack_predictor_T(sd, f"{a}.predictor_layers.{i}", [(0, nz)])
                 T["attn.out.wT"] = pk.pack_gemm(sd[f"{a}.out.weight"].t().contiguous())
             X[f"tree{l}"] = T
         return X

@@ -839,6 +839,260 @@ __global__ void __launch_bounds__(192) attention_bwd_kv_kernel(const float* __re
     }
 }
 
+// attention backward with several heads, per query row: the forward keeps only the head-averaged weights, so the probabilities of
+// head h are computed again from q, k, the window and the temperature, by the arithmetic of attention_kernel (score, maximum, sum
+// and quotient in the same order: with one head a[t] has the bits of the saved weights).  Per head: dS as in the one-head kernel
+// over the head's dh / vh channels; stats[r][h] = (maximum, sum) for the key / value kernel; dtemp_row[r] sums the heads in order.
+__global__ void __launch_bounds__(256) attention_bwd_heads_row_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                      const float* __restrict__ v, const float* __restrict__ d_out,
+                                                                      const int64_t* __restrict__ end_ind,
+                                                                      const float* __restrict__ temperature, float* __restrict__ stats,
+                                                                      float* __restrict__ dS, float* __restrict__ dq,
+                                                                      float* __restrict__ dtemp_row, const int M, const int rpb,
+                                                                      const int T, const int dk, const int nz, const int heads) {
+    extern __shared__ float smem[];
+    const int T4 = (T + 3) & ~3;
+    float* p = smem;                                      // [T] scores -> probabilities
+    float* pd = smem + T4;                                // [T] dA -> dS
+    float* part = smem + 2 * T4;                          // [256 * 4] partial sums of the query gradient
+    __shared__ float red[4];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.x;
+    const int b = r / rpb;
+    const int e = (int)end_ind[b];
+    const int te = e >= T ? T - 1 : e;
+    const float* kb = k + (size_t)b * T * dk;
+    const float* vb = v + (size_t)b * T * nz;
+    const int dh = dk / heads, vh = nz / heads;
+    const float sq = sqrtf((float)dh), temp = temperature[0];
+    const float inv = 1.f / sqrtf((float)dh) / temperature[0];
+    const int c4n = dh / 4, G = 256 / c4n;
+    float dtp_row = 0.f;
+    for (int h = 0; h < heads; ++h) {
+        const float* qr = q + (size_t)r * dk + h * dh;
+        const float* dor = d_out + (size_t)r * nz + h * vh;
+        float mx = -INFINITY;
+        for (int t = tid; t < T; t += 256) {
+            const float* kr = kb + (size_t)t * dk + h * dh;
+            float d = 0.f;
+            for (int i = 0; i < dh; i += 4) {
+                const float4 a4 = *reinterpret_cast<const float4*>(qr + i), b4 = *reinterpret_cast<const float4*>(kr + i);
+                d = fmaf(a4.x, b4.x, d); d = fmaf(a4.y, b4.y, d); d = fmaf(a4.z, b4.z, d); d = fmaf(a4.w, b4.w, d);
+            }
+            float sc = d * inv;
+            if (t > e) sc = -INFINITY;
+            p[t] = sc;
+            mx = fmaxf(mx, sc);
+        }
+        mx = block_reduce(mx, red, true);
+        float sum = 0.f;
+        for (int t = tid; t < T; t += 256) {
+            const float ex = (p[t] == -INFINITY) ? 0.f : expf(p[t] - mx);
+            p[t] = ex;
+            sum += ex;
+        }
+        sum = block_reduce(sum, red, false);
+        if (tid == 0) {
+            stats[((size_t)r * heads + h) * 2] = mx;
+            stats[((size_t)r * heads + h) * 2 + 1] = sum;
+        }
+        float dot = 0.f;
+        for (int t = tid; t < T; t += 256) {
+            const float a = p[t] / sum;
+            float da = 0.f;
+            if (t <= te) {
+                const float* vr = vb + (size_t)t * nz + h * vh;
+                for (int c = 0; c < vh; c += 4) {
+                    const float4 a4 = *reinterpret_cast<const float4*>(dor + c), b4 = *reinterpret_cast<const float4*>(vr + c);
+                    da = fmaf(a4.x, b4.x, da); da = fmaf(a4.y, b4.y, da); da = fmaf(a4.z, b4.z, da); da = fmaf(a4.w, b4.w, da);
+                }
+            }
+            p[t] = a;
+            pd[t] = da;
+            dot += a * da;
+        }
+        dot = block_reduce(dot, red, false);
+        float dtp = 0.f;
+        for (int t = tid; t < T; t += 256) {
+            const float ds = p[t] * (pd[t] - dot);
+            pd[t] = ds;
+            dS[((size_t)r * heads + h) * T + t] = ds;
+            if (t <= te && ds != 0.f) {
+                const float* kr = kb + (size_t)t * dk + h * dh;
+                float sc = 0.f;
+                for (int i = 0; i < dh; i += 4) {
+                    const float4 a4 = *reinterpret_cast<const float4*>(qr + i), b4 = *reinterpret_cast<const float4*>(kr + i);
+                    sc = fmaf(a4.x, b4.x, sc); sc = fmaf(a4.y, b4.y, sc); sc = fmaf(a4.z, b4.z, sc); sc = fmaf(a4.w, b4.w, sc);
+                }
+                dtp -= ds * (sc / sq / temp) / temp;
+            }
+        }
+        dtp = block_reduce(dtp, red, false);
+        dtp_row = h == 0 ? dtp : dtp_row + dtp;
+        __syncthreads();
+        const int c4 = tid % c4n, tg = tid / c4n;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tg < G) {
+#pragma unroll 4
+            for (int t = tg; t <= te; t += G) {
+                const float4 x = *reinterpret_cast<const float4*>(kb + (size_t)t * dk + h * dh + c4 * 4);
+                const float w = pd[t];
+                acc.x = fmaf(w, x.x, acc.x); acc.y = fmaf(w, x.y, acc.y); acc.z = fmaf(w, x.z, acc.z); acc.w = fmaf(w, x.w, acc.w);
+            }
+        }
+        reinterpret_cast<float4*>(part)[tid] = acc;
+        __syncthreads();
+        if (tid < c4n) {
+            float4 o = reinterpret_cast<float4*>(part)[tid];
+            for (int g = 1; g < G; ++g) {
+                const float4 x = reinterpret_cast<float4*>(part)[g * c4n + tid];
+                o.x += x.x; o.y += x.y; o.z += x.z; o.w += x.w;
+            }
+            const float sc = 1.f / sq / temp;
+            *reinterpret_cast<float4*>(dq + (size_t)r * dk + h * dh + tid * 4) = make_float4(o.x * sc, o.y * sc, o.z * sc, o.w * sc);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) dtemp_row[r] = dtp_row;
+}
+
+// attention backward with several heads, per (sequence, frame): the weight of frame t in row (b, j), head h comes back from the row
+// kernel's (maximum, sum) and one dh-long score, into LDS; then one thread per channel as in attention_bwd_kv_kernel, the rows of the
+// sequence summed in order.
+__global__ void __launch_bounds__(256) attention_bwd_heads_kv_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                     const float* __restrict__ stats, const float* __restrict__ dS,
+                                                                     const float* __restrict__ d_out,
+                                                                     const int64_t* __restrict__ end_ind,
+                                                                     const float* __restrict__ temperature, float* __restrict__ dK,
+                                                                     const long long ldk, float* __restrict__ dV, const long long ldv,
+                                                                     const int rpb, const int T, const int dk, const int nz,
+                                                                     const int heads) {
+    extern __shared__ float a_s[];                        // [rpb][heads] weights of this frame
+    const int bt = blockIdx.x, b = bt / T, t = bt % T;
+    const int e = (int)end_ind[b];
+    const int dh = dk / heads, vh = nz / heads;
+    const float inv = 1.f / sqrtf((float)dh) / temperature[0];
+    const float* kr = k + (size_t)bt * dk;
+    for (int i = threadIdx.x; i < rpb * heads; i += 256) {
+        const int j = i / heads, h = i % heads;
+        const size_t r = (size_t)b * rpb + j;
+        float a = 0.f;
+        if (t <= e) {
+            const float* qr = q + r * dk + h * dh;
+            float d = 0.f;
+            for (int c = 0; c < dh; c += 4) {
+                const float4 a4 = *reinterpret_cast<const float4*>(qr + c), b4 = *reinterpret_cast<const float4*>(kr + h * dh + c);
+                d = fmaf(a4.x, b4.x, d); d = fmaf(a4.y, b4.y, d); d = fmaf(a4.z, b4.z, d); d = fmaf(a4.w, b4.w, d);
+            }
+            // the forward rounds the scaled score (it stores it) before it subtracts the maximum: the empty statement keeps the compiler
+            // from contracting this product and that difference into one fma, which would change the last bit of the weight
+            float sc = d * inv;
+            asm volatile("" : "+v"(sc));
+            a = expf(sc - stats[(r * heads + h) * 2]) / stats[(r * heads + h) * 2 + 1];
+        }
+        a_s[i] = a;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < dk + nz; c += 256) {
+        float acc = 0.f;
+        if (c < dk) {
+            const int h = c / dh;
+            for (int j = 0; j < rpb; ++j) {
+                const size_t r = (size_t)b * rpb + j;
+                acc = fmaf(dS[(r * heads + h) * T + t], q[r * dk + c], acc);
+            }
+            dK[(size_t)bt * ldk + c] = acc * inv;
+        } else {
+            const int cc = c - dk, h = cc / vh;
+            for (int j = 0; j < rpb; ++j) {
+                const size_t r = (size_t)b * rpb + j;
+                acc = fmaf(a_s[j * heads + h], d_out[r * nz + cc], acc);
+            }
+            dV[(size_t)bt * ldv + cc] = acc;
+        }
+    }
+}
+
+// row layer-norm without affine (F.layer_norm(x, x.shape[1:]) of attentive_inference.py:82-83): one wavefront per row of W <= 1024
+// floats, the row (plus the optional addend row) held in registers; biased variance, two passes
+__global__ void __launch_bounds__(256) row_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ add,
+                                                            float* __restrict__ y, float* __restrict__ rstd, const int M, const int W,
+                                                            const float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int n4 = W / 4;
+    const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * W);
+    const float4* ar = add ? reinterpret_cast<const float4*>(add + (size_t)row * W) : nullptr;
+    float4 val[4];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        val[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < n4) {
+            val[i] = xr[c];
+            if (ar) {
+                const float4 a4 = ar[c];
+                val[i].x += a4.x; val[i].y += a4.y; val[i].z += a4.z; val[i].w += a4.w;
+            }
+            s += (val[i].x + val[i].y) + (val[i].z + val[i].w);
+        }
+    }
+    const float mean = wave_sum(s) / (float)W;
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (lane + 64 * i < n4) {
+            val[i].x -= mean; val[i].y -= mean; val[i].z -= mean; val[i].w -= mean;
+            ss += (val[i].x * val[i].x + val[i].y * val[i].y) + (val[i].z * val[i].z + val[i].w * val[i].w);
+        }
+    }
+    const float rs = 1.f / sqrtf(wave_sum(ss) / (float)W + eps);
+    float4* yr = reinterpret_cast<float4*>(y + (size_t)row * W);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (c < n4) yr[c] = make_float4(val[i].x * rs, val[i].y * rs, val[i].z * rs, val[i].w * rs);
+    }
+    if (rstd && lane == 0) rstd[row] = rs;
+}
+
+// backward of the row layer-norm from its saved output and 1 / sqrt(var + eps): dx = rstd * (dy - mean(dy) - y * mean(dy * y))
+__global__ void __launch_bounds__(256) row_layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
+                                                                const float* __restrict__ rstd, float* __restrict__ dx, const int M,
+                                                                const int W) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int n4 = W / 4;
+    const float4* gr = reinterpret_cast<const float4*>(dy + (size_t)row * W);
+    const float4* yr = reinterpret_cast<const float4*>(y + (size_t)row * W);
+    float4 g[4], o[4];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        g[i] = o[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < n4) {
+            g[i] = gr[c];
+            o[i] = yr[c];
+            s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
+            s2 += (g[i].x * o[i].x + g[i].y * o[i].y) + (g[i].z * o[i].z + g[i].w * o[i].w);
+        }
+    }
+    const float m1 = wave_sum(s1) / (float)W, m2 = wave_sum(s2) / (float)W;
+    const float rs = rstd[row];
+    float4* xr = reinterpret_cast<float4*>(dx + (size_t)row * W);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (c < n4)
+            xr[c] = make_float4(rs * (g[i].x - m1 - o[i].x * m2), rs * (g[i].y - m1 - o[i].y * m2), rs * (g[i].z - m1 - o[i].z * m2),
+                                rs * (g[i].w - m1 - o[i].w * m2));
+    }
+}
+
 }  // namespace
 
 extern "C" int gcpx_attention(const float* q, const float* k, const float* v, const int64_t* start_ind, const int64_t* end_ind,
@@ -996,6 +1250,46 @@ extern "C" int gcpx_attention_bwd(const float* q, const float* k, const float* v
                        end_ind, temperature, dS, dq, dtemp_row, M, rpb, T, dk, nz);
     hipLaunchKernelGGL(attention_bwd_kv_kernel, dim3((M / rpb) * T), dim3(192), 0, stream, q, att, dS, d_out, temperature, dK,
                        (long long)ldk, dV, (long long)ldv, rpb, T, dk, nz);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_attention_bwd_heads(const float* q, const float* k, const float* v, const float* d_out, const int64_t* end_ind,
+                                        const float* temperature, float* stats, float* dS, float* dq, float* dtemp_row, float* dK,
+                                        int64_t ldk, float* dV, int64_t ldv, int32_t M, int32_t rpb, int32_t T, int32_t dk, int32_t nz,
+                                        int32_t heads, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(q && k && v && d_out && end_ind && temperature && stats && dS && dq && dtemp_row && dK && dV, "null pointer");
+    GCPX_CHECK_ARG(M > 0 && rpb > 0 && M % rpb == 0 && T > 0 && T <= 4096 && heads > 0 && dk > 0 && nz > 0 && dk % heads == 0 &&
+                       nz % heads == 0 && (int64_t)rpb * heads <= 8192,
+                   "bad sizes");
+    GCPX_CHECK_ARG((dk / heads) % 4 == 0 && (nz / heads) % 4 == 0 && dk / heads <= 1024 && nz / heads <= 1024 &&
+                       256 % (dk / heads / 4) == 0 && 256 % (nz / heads / 4) == 0,
+                   "head widths must be multiples of 4, dk / heads / 4 and nz / heads / 4 divisors of 256");
+    hipLaunchKernelGGL(attention_bwd_heads_row_kernel, dim3(M), dim3(256), (2 * (T + 4) + 1024) * sizeof(float), stream, q, k, v, d_out,
+                       end_ind, temperature, stats, dS, dq, dtemp_row, M, rpb, T, dk, nz, heads);
+    hipLaunchKernelGGL(attention_bwd_heads_kv_kernel, dim3((M / rpb) * T), dim3(256), (size_t)rpb * heads * sizeof(float), stream, q, k,
+                       stats, dS, d_out, end_ind, temperature, dK, (long long)ldk, dV, (long long)ldv, rpb, T, dk, nz, heads);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_row_layernorm(const float* x, const float* add, float* y, float* rstd, int32_t M, int32_t W, float eps,
+                                  void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(x && y, "null pointer");
+    GCPX_CHECK_ARG(M > 0 && W > 0 && W % 4 == 0 && W <= 1024 && eps >= 0.f, "rows of 4 .. 1024 floats, a multiple of 4");
+    hipLaunchKernelGGL(row_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, x, add, y, rstd, M, W, eps);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_row_layernorm_bwd(const float* dy, const float* y, const float* rstd, float* dx, int32_t M, int32_t W,
+                                      void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(dy && y && rstd && dx, "null pointer");
+    GCPX_CHECK_ARG(M > 0 && W > 0 && W % 4 == 0 && W <= 1024, "rows of 4 .. 1024 floats, a multiple of 4");
+    hipLaunchKernelGGL(row_layernorm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, dy, y, rstd, dx, M, W);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

@@ -12,7 +12,7 @@ from . import packing as pk
 from . import runtime as rt
 from .hparams import GCPHParams
 from .params import init_params, encoder_layers, encoder_skip_layers, decoder_layers
-from .plan_ops import _Plan, _addr, N_LANES
+from .plan_ops import _Plan, _addr, N_LANES, attn_layer_suffix
 
 
 class ForwardPlanMixin:
@@ -110,31 +110,51 @@ class ForwardPlanMixin:
                    B * T, nz, T, P[f"{tag}.head.w"], P[f"{tag}.head.b"], out=out.data_ptr(), ob=T * nz, orow=nz)
 
     def _plan_attention(self, plan, l, W, el, er, M, n, B, Kp, Vp, tin):
-        """Attention.forward for one tree level (attentive_inference.py:47-86, one layer, mask = the sequence's own
-        [start_ind, end_ind]): query MLP -> q_proj -> masked softmax over the T frames -> out_proj -> Attention.out.
-        Returns the row source of e_tilde [M, nz_enc]; the attention weights (gamma) stay in plan.rec."""
+        """Attention.forward for one tree level (attentive_inference.py:47-86; mask = the sequence's own [start_ind, end_ind]):
+        query MLP, then per layer i: q_proj -> masked softmax over the T frames -> out_proj = raw_i, and between two layers
+        x = LN(raw_i), query_{i+1} = LN(predictor_layers[i](x) + query_i) (:80-84).  e_tilde = Attention.out(raw of the last layer).
+        The last layer's predictor and layer-norms, which the reference computes and drops, are not launched.
+        Returns the row source of e_tilde [M, nz_enc]; the last layer's attention weights (gamma) stay in plan.rec."""
         hp, lib = self._hp, self.lib
         T, nz, dk = hp.max_seq_len, hp.nz_enc, hp.nz_attn_key
+        Ln = hp.n_attention_layers
         li = l if hp.untied_layers else 0
         qin = self._buf(f"attn.qin{l}", (M, dk))
         self._mlp(plan, f"attn.query{l}", W["attn.query"], [el, er], M, n, out=qin.data_ptr(), ob=n * dk, orow=dk)
         dense = lambda t, w: self._rowsrc(t.data_ptr(), 0, w, w)
-        qp = self._buf(f"attn.q{l}", (M, dk))
-        self._gemm(plan, f"attn.q_proj{l}", [dense(qin, dk)], M, dk, M, W["attn.q_proj.w"], W["attn.q_proj.b"],
-                   out=qp.data_ptr(), ob=0, orow=dk)
-        o = self._buf(f"attn.o{l}", (M, nz))
-        gamma = self._buf(f"attn.gamma{l}", (M, T))
-        temp = self.sd[f"tree_module.tree_modules.{li}.inference.attention.attention_layers.0.temperature"]
-        plan.add(f"attn{l}", lib.gcpx_attention, qp.data_ptr(), _addr(Kp, li * B * T * dk), _addr(Vp, li * B * T * nz), None,
-                 tin["end_ind"].data_ptr(), temp.data_ptr(), o.data_ptr(), gamma.data_ptr(), M, n, T, dk, nz, hp.n_attention_heads)
-        raw = self._buf(f"attn.raw{l}", (M, nz))
-        self._gemm(plan, f"attn.out_proj{l}", [dense(o, nz)], M, nz, M, W["attn.out_proj.w"], W["attn.out_proj.b"],
-                   out=raw.data_ptr(), ob=0, orow=nz)
+        layers = []
+        for i in range(Ln):
+            sfx = attn_layer_suffix(i)
+            blk = li * Ln + i                                    # this (module, layer)'s block of the projected keys / values
+            qp = self._buf(f"attn.q{l}{sfx}", (M, dk))
+            self._gemm(plan, f"attn.q_proj{l}{sfx}", [dense(qin, dk)], M, dk, M, W[f"attn.q_proj{sfx}.w"], W[f"attn.q_proj{sfx}.b"],
+                       out=qp.data_ptr(), ob=0, orow=dk)
+            o = self._buf(f"attn.o{l}{sfx}", (M, nz))
+            gamma = self._buf(f"attn.gamma{l}{sfx}", (M, T))
+            temp = self.sd[f"tree_module.tree_modules.{li}.inference.attention.attention_layers.{i}.temperature"]
+            plan.add(f"attn{l}{sfx}", lib.gcpx_attention, qp.data_ptr(), _addr(Kp, blk * B * T * dk), _addr(Vp, blk * B * T * nz), None,
+                     tin["end_ind"].data_ptr(), temp.data_ptr(), o.data_ptr(), gamma.data_ptr(), M, n, T, dk, nz, hp.n_attention_heads)
+            raw = self._buf(f"attn.raw{l}{sfx}", (M, nz))
+            self._gemm(plan, f"attn.out_proj{l}{sfx}", [dense(o, nz)], M, nz, M, W[f"attn.out_proj{sfx}.w"], W[f"attn.out_proj{sfx}.b"],
+                       out=raw.data_ptr(), ob=0, orow=nz)
+            lay = dict(qin=qin, qp=qp, o=o, raw=raw, gamma=gamma, temp=temp, blk=blk)
+            layers.append(lay)
+            if i < Ln - 1:
+                x, qn = self._buf(f"attn.x{l}{sfx}", (M, nz)), self._buf(f"attn.qin{l}{attn_layer_suffix(i + 1)}", (M, dk))
+                rs_x, rs_q = self._buf(f"attn.x.rstd{l}{sfx}", (M,)), self._buf(f"attn.qn.rstd{l}{sfx}", (M,))
+                pred = self._buf(f"attn.pred{l}{sfx}", (M, dk))
+                plan.add(f"attn.ln_x{l}{sfx}", lib.gcpx_row_layernorm, raw.data_ptr(), None, x.data_ptr(), rs_x.data_ptr(), M, nz,
+                         C.c_float(1e-5))
+                self._mlp(plan, f"attn.pred{l}{sfx}", W[f"attn.pred{sfx}"], [dense(x, nz)], M, M, out=pred.data_ptr(), ob=0, orow=dk)
+                plan.add(f"attn.ln_q{l}{sfx}", lib.gcpx_row_layernorm, pred.data_ptr(), qin.data_ptr(), qn.data_ptr(), rs_q.data_ptr(),
+                         M, dk, C.c_float(1e-5))
+                lay.update(x=x, rs_x=rs_x, qn=qn, rs_q=rs_q)
+                qin = qn
         et = self._buf(f"attn.e_tilde{l}", (M, nz))
         self._gemm(plan, f"attn.out{l}", [dense(raw, nz)], M, nz, M, W["attn.out.w"], W["attn.out.b"], out=et.data_ptr(), ob=0, orow=nz)
         plan.rec.setdefault("gamma", {})[l] = gamma
         plan.rec.setdefault("e_tilde", {})[l] = et
-        plan.rec.setdefault("attn", {})[l] = dict(qin=qin, qp=qp, o=o, raw=raw, gamma=gamma, et=et, M=M, n=n, li=li, temp=temp)
+        plan.rec.setdefault("attn", {})[l] = dict(layers=layers, et=et, M=M, n=n, li=li)
         return self._rowsrc(et.data_ptr(), n * nz, nz, nz)          # rows (b, j) of the level, as the posterior MLP walks them
 
     def _plan_decoder_features(self, plan, e_src, F, rpb, skips):
@@ -300,13 +320,14 @@ class ForwardPlanMixin:
                     dense = lambda t, w: self._rowsrc(t.data_ptr(), 0, w, w)
                     self._gemm(plan, "kseq.key", [dense(kenc, nz)], B * T, dk, B * T, P["kseq.key.w"], P["kseq.key.b"],
                                out=keys.data_ptr(), ob=0, orow=dk)
-                    Kp = self._buf("attn.K", (n_mod, B * T, dk))
-                    Vp = self._buf("attn.V", (n_mod, B * T, nz))
+                    nblk = n_mod * hp.n_attention_layers        # one block per (tree-level module, attention layer)
+                    Kp = self._buf("attn.K", (nblk, B * T, dk))
+                    Vp = self._buf("attn.V", (nblk, B * T, nz))
                     self._gemm(plan, "attn.k_proj", [dense(keys, dk)], B * T, dk, B * T, P["attn.k_proj.w"], P["attn.k_proj.b"],
-                               out=Kp.data_ptr(), ob=0, orow=dk, batch=(n_mod, 0, P["attn.k_proj.w"][0].numel(), dk, B * T * dk))
+                               out=Kp.data_ptr(), ob=0, orow=dk, batch=(nblk, 0, P["attn.k_proj.w"][0].numel(), dk, B * T * dk))
                     self._gemm(plan, "attn.v_proj", [dense(inf_enc, nz)], B * T, nz, B * T, P["attn.v_proj.w"], P["attn.v_proj.b"],
-                               out=Vp.data_ptr(), ob=0, orow=nz, batch=(n_mod, 0, P["attn.v_proj.w"][0].numel(), nz, B * T * nz))
-                    plan.rec["attn_kv"] = dict(Kp=Kp, Vp=Vp, keys=keys, kenc=kenc, n_mod=n_mod)
+                               out=Vp.data_ptr(), ob=0, orow=nz, batch=(nblk, 0, P["attn.v_proj.w"][0].numel(), nz, B * T * nz))
+                    plan.rec["attn_kv"] = dict(Kp=Kp, Vp=Vp, keys=keys, kenc=kenc, n_mod=n_mod, nblk=nblk)
 
         if traj_first:
             plan_traj_encoder()

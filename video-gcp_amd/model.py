@@ -127,7 +127,12 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
         if hp.lstm_init not in ("mlp", "zero"):
             raise ValueError("dont know lstm init type {}!".format(hp.lstm_init))  # tree_lstm.py:74
         if hp.attentive_inference:
-            assert hp.n_attention_layers == 1, "one attention layer is built (hyperparameters.py:25 default)"
+            h = hp.n_attention_heads
+            dh, vh = hp.nz_attn_key // h, hp.nz_enc // h
+            if hp.n_attention_layers < 1 or dh % 4 or vh % 4 or 256 % (dh // 4) or 256 % (vh // 4):
+                raise ValueError(f"n_attention_heads = {h}, n_attention_layers = {hp.n_attention_layers}: the attention kernels take at "
+                                 f"least one layer and head widths nz_attn_key / heads = {dh}, nz_enc / heads = {vh} that are "
+                                 "multiples of 4 with a quarter that divides 256")
         assert not (hp.action_conditioned_pred or hp.deterministic or hp.non_goal_conditioned), \
             "the vmpc.py variants belong to the flat predictor (SequentialModel): GCPSequentialModel"
         if hp.adaptive:

@@ -14,6 +14,11 @@ def _addr(t, off_elems=0):
     return t.data_ptr() + 4 * off_elems
 
 
+def attn_layer_suffix(i):
+    """name suffix of attention layer i in packs, buffers and launch names: layer 0 keeps the names of the one-layer model"""
+    return "" if i == 0 else f"@{i}"
+
+
 N_LANES = 3
 
 

@@ -255,6 +255,10 @@ SYMBOLS = [
     ("gcpx_averaging_nll_bwd", C.c_int, [vp, vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, i64, vp, vp, vp]),
     ("gcpx_dlm_mean_bwd", C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     ("gcpx_attention_bwd", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, vp]),
+    # several attention heads / layers (attentive_inference.py:80-84; hyperparameters.py:24-25)
+    ("gcpx_attention_bwd_heads", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
+    ("gcpx_row_layernorm", C.c_int, [vp, vp, vp, vp, i32, i32, C.c_float, vp]),
+    ("gcpx_row_layernorm_bwd", C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
     ("gcpx_dtw_align", C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     ("gcpx_graph_begin", C.c_int, [vp]),
     ("gcpx_graph_end", C.c_int, [vp, C.POINTER(vp)]),

@@ -74,8 +74,6 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             # (the averaging criterion's image gradient would have to go through tanh instead of through the mixture mean)
             raise ValueError("training the adaptive (matching_type='dtw_image') model with decoder_distribution='gaussian' is not built: "
                              "its backward takes the image gradient through the mixture mean of the discrete_logistic_mixture head")
-        if hp.attentive_inference:
-            assert hp.n_attention_heads == 1, "attention backward is built for one head (hyperparameters.py:24 default)"
         self.m = model
         self.lr, self.betas, self.eps = lr, betas, eps
         self.pg = process_group
@@ -133,6 +131,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self.batch_dh = os.environ.get("GCPX_NO_BATCH_DH") is None                 # a level's d h_prev GEMMs as one batched launch
         self.group_mlp_bwd = os.environ.get("GCPX_NO_MLP_BWD_GROUP") is None       # a level's posterior + prior backward as one launch
         self.fused_mlp_bwd = os.environ.get("GCPX_NO_FUSED_MLP_BWD") is None
+        # one attention head through gcpx_attention_bwd_heads too (same bits as gcpx_attention_bwd: tests/test_gpu_attention_layers.py)
+        self.attn_bwd_heads_export = os.environ.get("GCPX_ATTN_BWD_HEADS") is not None
         self._pad_fixups = []                 # (see _mlp_in_dst)
         # the decoder's weight gradients (5 ms of throughput-bound kernels) are forked after the decoder's data-gradient chain: they then
         # fill the chip during the latency-bound tree phase instead of competing with the data gradients (23.2 -> 22.8 ms / step)

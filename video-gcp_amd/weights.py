@@ -11,7 +11,7 @@ from . import packing as pk
 from . import runtime as rt
 from .hparams import GCPHParams
 from .params import init_params, encoder_layers, encoder_skip_layers, decoder_layers
-from .plan_ops import _addr
+from .plan_ops import _addr, attn_layer_suffix
 
 
 class WeightsMixin:
@@ -409,11 +409,12 @@ class WeightsMixin:
         H = hp.nz_mid_lstm
         n_mod = hp.hierarchy_levels if hp.untied_layers else 1
         if hp.attentive_inference:
-            # key / value projections of every level's attention stacked: one batched launch each (blockIdx.z = level)
-            att = lambda l, nm: sd[f"tree_module.tree_modules.{l}.inference.attention.attention_layers.0.{nm}"]
+            # key / value projections of every level's attention layers stacked: one batched launch each (blockIdx.z = level * layers + layer)
+            att = lambda l, i, nm: sd[f"tree_module.tree_modules.{l}.inference.attention.attention_layers.{i}.{nm}"]
+            blocks = [(l, i) for l in range(n_mod) for i in range(hp.n_attention_layers)]
             for nm in ("k_proj", "v_proj"):
-                P[f"attn.{nm}.w"] = torch.stack([pk.pack_gemm(att(l, f"{nm}.weight")) for l in range(n_mod)]).contiguous()
-                P[f"attn.{nm}.b"] = torch.stack([att(l, f"{nm}.bias") for l in range(n_mod)]).contiguous()
+                P[f"attn.{nm}.w"] = torch.stack([pk.pack_gemm(att(l, i, f"{nm}.weight")) for l, i in blocks]).contiguous()
+                P[f"attn.{nm}.b"] = torch.stack([att(l, i, f"{nm}.bias") for l, i in blocks]).contiguous()
         for l in range(hp.hierarchy_levels if hp.untied_layers else 1):
             p = f"tree_module.tree_modules.{l}"
             T = {}
@@ -445,8 +446,15 @@ class WeightsMixin:
             if hp.attentive_inference:
                 a = f"{p}.inference.attention"
                 T["attn.query"] = self._pack_predictor(f"{a}.query_net", hp.nz_attn_key)
-                for nm, key in (("q_proj", f"{a}.attention_layers.0.q_proj"), ("out_proj", f"{a}.attention_layers.0.out_proj"),
-                                ("out", f"{a}.out")):
+                # layer 0 keeps the names of the one-layer model; layer i > 0 carries "@i".  The last layer's predictor_layers entry is
+                # computed and dropped by the reference (attentive_inference.py:83-85): it is not packed
+                named = []
+                for i in range(hp.n_attention_layers):
+                    sfx = attn_layer_suffix(i)
+                    named += [(f"q_proj{sfx}", f"{a}.attention_layers.{i}.q_proj"), (f"out_proj{sfx}", f"{a}.attention_layers.{i}.out_proj")]
+                    if i < hp.n_attention_layers - 1:
+                        T[f"attn.pred{sfx}"] = self._pack_predictor(f"{a}.predictor_layers.{i}", hp.nz_attn_key)
+                for nm, key in named + [("out", f"{a}.out")]:
                     T[f"attn.{nm}.w"] = pk.pack_gemm(sd[f"{key}.weight"])
                     T[f"attn.{nm}.b"] = sd[f"{key}.bias"].contiguous()
             P[f"tree{l}"] = T
