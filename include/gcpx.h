@@ -949,6 +949,14 @@ int gcpx_attention(const float* q, const float* k, const float* v, const int64_t
 int gcpx_cdist_splits(int64_t K);
 int gcpx_cdist(const float* x, const float* y, int32_t B, int32_t N, int32_t T, int64_t K, float* partial, float* xnorm,
                float* ynorm, float* out, void* stream);
+/* gcpx_cdist with x read where it lies: row (b, n) is the K floats at x + b * x_sb + n * x_sr (strides in floats, multiples of 4,
+ *   x 16-byte aligned; x_sr >= K, and a batch element's rows end before the next one's begin).  y, the scratch and out as above;
+ *   the same kernels in the same order, so with x_sb = N * K, x_sr = K the result has the bits of gcpx_cdist.
+ *   Call site: forward_plan.py, the `matching` block with matching_type = 'dtw_latent' (adaptive.py:45-47: the cost between
+ *   tree.df.e_g_prime and enc_traj_seq) — the node latents in position layout, node n at slot n + 1: x = E + nz_enc,
+ *   x_sb = (2^L + 1) * nz_enc, x_sr = nz_enc, K = nz_enc; no gathered copy. */
+int gcpx_cdist_strided(const float* x, int64_t x_sb, int64_t x_sr, const float* y, int32_t B, int32_t N, int32_t T, int64_t K,
+                       float* partial, float* xnorm, float* ynorm, float* out, void* stream);
 
 /* soft_dtw(cost / temp, end_ind) + normalize(w, 1) of adaptive.py:50-58 (probabilistic_dtw.py:11-122), float64 inside:
  *   cost[b][n][t] = (dsum[b][n][t] / D) / temp[0]  ('mean' reduction of the cdist, then the matching temperature);
@@ -971,6 +979,15 @@ int gcpx_soft_dtw(const float* dsum, float D, const float* temp, const int64_t* 
 int gcpx_soft_dtw_dtemp(const float* dsum, float D, const float* temp, const int64_t* end_ind, const double* acc,
                         const float* pad_mask, const float* log_sigma, float coef, int32_t B, int32_t N, int32_t T,
                         double* tangent, double* partial, float* dtemp, void* stream);
+/* The same with the lattice cost and the criterion's per-cell value taken from two matrices: the alignment runs over
+ *   cost[b][n][t] = (cost_dsum / cost_D) / temp[0] (acc: what gcpx_soft_dtw left for cost_dsum / cost_D), the criterion is
+ *   coef * sum w * pad * (0.5 loss_dsum exp(-2 ls) + loss_D (ls + 0.5 log 2 pi)).  Same float64 sweep and summation order:
+ *   with loss_dsum == cost_dsum and loss_D == cost_D the result has the bits of gcpx_soft_dtw_dtemp.
+ *   Call site: backward_plan.py, "bw.dtw_dtemp" with matching_type = 'dtw_latent' and learn_matching_temp (the matching costs
+ *   latents, adaptive.py:45-47; LossAveragingCriterion.loss still weighs image distances, binding_loss.py:24). */
+int gcpx_soft_dtw_dtemp_split(const float* cost_dsum, float cost_D, const float* loss_dsum, float loss_D, const float* temp,
+                              const int64_t* end_ind, const double* acc, const float* pad_mask, const float* log_sigma, float coef,
+                              int32_t B, int32_t N, int32_t T, double* tangent, double* partial, float* dtemp, void* stream);
 
 /* Bookkeeping on the matching distribution w [B][N = 2^L - 1][T] (depth-first):
  *   frame2node [B][T]  depth-first position of argmax over nodes, first maximum in BREADTH-first order
@@ -1050,6 +1067,14 @@ int gcpx_row_layernorm(const float* x, const float* add, float* y, float* rstd, 
 /* its backward from the saved y and rstd: dx[r] = rstd[r] * (dy[r] - mean(dy[r]) - y[r] * mean(dy[r] * y[r])); with an addend the
  *   same dx is the gradient of both summands */
 int gcpx_row_layernorm_bwd(const float* dy, const float* y, const float* rstd, float* dx, int32_t M, int32_t W, void* stream);
+/* Sum of `nblocks` column blocks lying side by side: dst[r][c] = ((src[r][c] + src[r][width + c]) + src[r][2 width + c]) + ...,
+ *   r < rows, c < width; src rows have leading dimension ld >= nblocks * width, dst rows ldd >= width.  float32, one thread per
+ *   element adds the blocks left to right (no atomics: the order is fixed).  dst may be block 0 of src; nothing else is written.
+ *   Call site: backward_plan.py, "bw.attn.ksum" / "bw.attn.vsum" — tied tree levels (untied_layers = False) share the projected
+ *   keys / values of an attention layer, whose gradient is the sum over the levels of what gcpx_attention_bwd(_heads) wrote for
+ *   each level into a block of its own, the blocks laid out in the order the backward walks the levels (level L - 1 first). */
+int gcpx_add_col_blocks(const float* src, int64_t ld, int32_t nblocks, float* dst, int64_t ldd, int64_t rows, int32_t width,
+                        void* stream);
 
 /* ---- collectives of the data-parallel paths: RCCL over xGMI, one communicator per process (one process
  *   per GPU), enqueued on the caller's stream, no synchronisation.  Replaces nn.DataParallel's gradient reduce

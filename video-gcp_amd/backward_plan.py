@@ -68,12 +68,17 @@ class BackwardPlanMixin:
             if hp.learn_matching_temp:
                 # adaptive.py:19-21, :51: only the COST is detached; the division by the learned temperature is not, so the criterion
                 # reaches `temp` through the matching weights (forward-mode sweep along the forward pass's accumulators)
-                self._side(plan, "bw.dtw_dtemp", lib.gcpx_soft_dtw_dtemp, o["cdist_sum"].data_ptr(), C.c_float(float(Dd)),
-                           m.sd["tree_module.tree_modules.0.binding.temp"].data_ptr(), tin["end_ind"].data_ptr(),
-                           o["dtw_acc"].data_ptr(), tin["pad_mask"].data_ptr(), m.sd["decoder.log_sigma"].data_ptr(),
-                           C.c_float(hp.dense_img_rec_weight / (B * div)), B, N, T,
-                           buf("bw.dtw.tangent", (2 * B, N, T), torch.float64).data_ptr(),
-                           buf("bw.dtw.partial", (B,), torch.float64).data_ptr(), self.g("tree_module.tree_modules.0.binding.temp"))
+                tail = (m.sd["tree_module.tree_modules.0.binding.temp"].data_ptr(), tin["end_ind"].data_ptr(),
+                        o["dtw_acc"].data_ptr(), tin["pad_mask"].data_ptr(), m.sd["decoder.log_sigma"].data_ptr(),
+                        C.c_float(hp.dense_img_rec_weight / (B * div)), B, N, T,
+                        buf("bw.dtw.tangent", (2 * B, N, T), torch.float64).data_ptr(),
+                        buf("bw.dtw.partial", (B,), torch.float64).data_ptr(), self.g("tree_module.tree_modules.0.binding.temp"))
+                if hp.matching_type == "dtw_latent":
+                    # the alignment ran over the latent cost (adaptive.py:45-47); the criterion still weighs image distances
+                    self._side(plan, "bw.dtw_dtemp", lib.gcpx_soft_dtw_dtemp_split, o["match_cost_sum"].data_ptr(),
+                               C.c_float(float(rec["match_cost_D"])), o["cdist_sum"].data_ptr(), C.c_float(float(Dd)), *tail)
+                else:
+                    self._side(plan, "bw.dtw_dtemp", lib.gcpx_soft_dtw_dtemp, o["cdist_sum"].data_ptr(), C.c_float(float(Dd)), *tail)
             dMD = buf("bw.dMD", (B * N, S, S, pitch))
             # (lean: the mean depends on the leading 8 x mixtures slots only — the gradient's other slots are neither written here nor read
             # by the head's data / weight gradient launches, backward_stages._lean_head)
@@ -162,8 +167,14 @@ class BackwardPlanMixin:
             kv = rec["attn_kv"]
             n_mod, nblk, dk = kv["n_mod"], kv["nblk"], hp.nz_attn_key
             dKp, dVp = buf("bw.dKp", (B * T, nblk * dk)), buf("bw.dVp", (B * T, nblk * nz))
-            if n_mod < L:       # tied levels accumulate: not built
-                raise NotImplementedError("attentive training with tied tree layers")
+            tied_kv = n_mod < L
+            if tied_kv:
+                # Tied levels (untied_layers = False, the reference's default: hyperparameters.py:117) share the projected keys / values
+                # of an attention layer, whose gradient is the SUM over the levels.  Every (layer, level) writes a column block of its
+                # own, the levels of a layer side by side in the order this backward walks them (level L - 1 first); behind level 0
+                # gcpx_add_col_blocks adds them left to right into the layer's block of dKp / dVp — a fixed order, no atomics
+                nal = hp.n_attention_layers
+                dKl, dVl = buf("bw.dKp.levels", (B * T, nal * L * dk)), buf("bw.dVp.levels", (B * T, nal * L * nz))
 
         # ---- tree levels, leaves first (tree_utils.py:21-44 backward) ----
         MERGE_LANE = 1 + self.n_side                    # the caller's stream (backward(): the last entry of the stream list)
@@ -325,11 +336,23 @@ class BackwardPlanMixin:
                           [(dXq.data_ptr(), n * 2 * nz, 2 * nz), et_out], group=grp)
             dXa = None
             if attentive:
-                dXa = self._attention_backward(plan, fplan, l, Wt, dEt_l, dKp, dVp, B)
+                if tied_kv:
+                    dXa = self._attention_backward(plan, fplan, l, Wt, dEt_l, dKl, dVl, B,
+                                                   grad_blocks=(nal * L, lambda i, p=L - 1 - l: i * L + p))
+                    if l == 0:
+                        for i in range(nal):
+                            sfx = attn_layer_suffix(i)
+                            plan.add(f"bw.attn.ksum{sfx}", lib.gcpx_add_col_blocks, _addr(dKl, i * L * dk), nal * L * dk, L,
+                                     _addr(dKp, i * dk), nblk * dk, B * T, dk)
+                            plan.add(f"bw.attn.vsum{sfx}", lib.gcpx_add_col_blocks, _addr(dVl, i * L * nz), nal * L * nz, L,
+                                     _addr(dVp, i * nz), nblk * nz, B * T, nz)
+                else:
+                    dXa = self._attention_backward(plan, fplan, l, Wt, dEt_l, dKp, dVp, B)
                 # this level's column block of dKp / dVp is final now: its k_proj / v_proj weight gradients belong to the level's
                 # module (and to its bucket of the data-parallel exchange), so they go out with this level's flush, in front of
-                # the bucket mark — issued after the tree loop they were written into a slice whose all-reduce had already started
-                for i in range(hp.n_attention_layers):
+                # the bucket mark — issued after the tree loop they were written into a slice whose all-reduce had already started.
+                # (Tied levels: once, from the summed blocks, behind level 0.)
+                for i in range(hp.n_attention_layers if (not tied_kv or l == 0) else 0):
                     a_, sfx = f"tree_module.tree_modules.{li}.inference.attention.attention_layers.{i}", attn_layer_suffix(i)
                     blk = li * hp.n_attention_layers + i
                     self._wgrad(plan, f"attn.k_proj{l}{sfx}", _addr(dKp, blk * dk), nblk * dk, B * T, dk, kv["keys"].data_ptr(), dk,

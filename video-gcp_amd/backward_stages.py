@@ -239,11 +239,13 @@ class BackwardStagesMixin:
         return d_enc
 
     # ---- attention of the attentive posterior (attentive_inference.py:47-86), one tree level ----
-    def _attention_backward(self, plan, fplan, l, Wt, dEt, dKp, dVp, B):
+    def _attention_backward(self, plan, fplan, l, Wt, dEt, dKp, dVp, B, grad_blocks=None):
         """dEt [M, nz] = gradient of e_tilde.  Writes this level's column blocks of dKp / dVp (projected keys / values, one block per
         attention layer) and returns dXa [M, 2 nz], the gradient w.r.t. the query network's inputs (e_l | e_r).  The layers are walked
         last first: only the last layer's raw feeds Attention.out; raw_i of an earlier layer gets its gradient through
-        x = LN(raw_i) -> predictor_layers[i] -> LN(. + query_i) = query_{i+1}, and query_i gets the same layer-norm gradient again."""
+        x = LN(raw_i) -> predictor_layers[i] -> LN(. + query_i) = query_{i+1}, and query_i gets the same layer-norm gradient again.
+        grad_blocks = (blocks in a row of dKp / dVp, layer -> this level's block): tied levels, which read the same K' / V' block and
+        write their gradients side by side (backward_plan: summed behind level 0); None: the gradient lies where K' / V' do."""
         m, hp, lib = self.m, self.m._hp, self.m.lib
         rec = fplan.rec
         ar = rec["attn"][l]
@@ -282,19 +284,20 @@ class BackwardStagesMixin:
             # softmax attention
             dqp, dtr = buf(f"bw.attn.dq{l}{sfx}", (M, dk)), buf(f"bw.attn.dtemp{l}{sfx}", (M,))
             blk = lay["blk"]
+            gn, gblk = (grad_blocks[0], grad_blocks[1](i)) if grad_blocks is not None else (nblk, blk)
             Kb, Vb = _addr(kv["Kp"], blk * B * T * dk), _addr(kv["Vp"], blk * B * T * nz)
             end_ind = fplan.rec["tin"]["end_ind"].data_ptr()
             if heads == 1 and not self.attn_bwd_heads_export:
                 dS = buf(f"bw.attn.dS{l}{sfx}", (M, T))
                 plan.add(f"bw.attn{l}{sfx}", lib.gcpx_attention_bwd, lay["qp"].data_ptr(), Kb, Vb, lay["gamma"].data_ptr(), do.data_ptr(), end_ind,
-                         lay["temp"].data_ptr(), dS.data_ptr(), dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, blk * dk), nblk * dk,
-                         _addr(dVp, blk * nz), nblk * nz, M, n, T, dk, nz)
+                         lay["temp"].data_ptr(), dS.data_ptr(), dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, gblk * dk), gn * dk,
+                         _addr(dVp, gblk * nz), gn * nz, M, n, T, dk, nz)
             else:
                 # the saved weights are the mean over heads: the per-head probabilities are computed again (gcpx_attention_bwd_heads)
                 dS, stats = buf(f"bw.attn.dS{l}{sfx}", (M, heads, T)), buf(f"bw.attn.stats{l}{sfx}", (M, heads, 2))
                 plan.add(f"bw.attn{l}{sfx}", lib.gcpx_attention_bwd_heads, lay["qp"].data_ptr(), Kb, Vb, do.data_ptr(), end_ind,
-                         lay["temp"].data_ptr(), stats.data_ptr(), dS.data_ptr(), dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, blk * dk),
-                         nblk * dk, _addr(dVp, blk * nz), nblk * nz, M, n, T, dk, nz, heads)
+                         lay["temp"].data_ptr(), stats.data_ptr(), dS.data_ptr(), dqp.data_ptr(), dtr.data_ptr(), _addr(dKp, gblk * dk),
+                         gn * dk, _addr(dVp, gblk * nz), gn * nz, M, n, T, dk, nz, heads)
             self._side(plan, f"bw.attn.dtemp:{l}{sfx}", lib.gcpx_reduce_partials, dtr.data_ptr(), M, 1, 1, self.g(f"{al}.temperature"), 1)
             # q' = q_proj(query_i)
             lin(f"attn.q_proj{l}{sfx}", dqp, lay["qin"], dk, dk, f"{al}.q_proj")

@@ -50,8 +50,11 @@ _BASE_CONFIGS = {
     "base_tree": (dict(model="TreeModel", logger="HierarchyLogger"), dict(_BASE_TREE)),
     "gcp_tree": (dict(model="TreeModel", logger="HierarchyLogger", metric_pruning_scheme="pruned_dtw"),
                  dict(_BASE_TREE, matching_type="balanced")),
+    # (untied_layers: the file does not set it, so the reference's default holds, hyperparameters.py:117 — tied tree levels; stated here
+    # because this build's dataclass default is the 25-room conf's True.  A conf on this base may set 'dtw_latent', adaptive.py:45-47)
     "gcp_adaptive": (dict(model="TreeModel", logger="HierarchyLogger"),
-                     dict(_BASE_TREE, matching_type="dtw_image", learn_matching_temp=False, attentive_inference=True)),
+                     dict(_BASE_TREE, matching_type="dtw_image", learn_matching_temp=False, attentive_inference=True,
+                          untied_layers=False)),
     "gcp_sequential": (dict(model="SequentialModel", logger="HierarchyLogger"),
                        dict(one_step_planner="continuous", dense_rec_type="svg", hierarchy_levels=0, add_weighted_pixel_copy=True)),
     # base_configs/vmpc.py:11-16: gcp_sequential made action-conditioned, deterministic and blind to the goal

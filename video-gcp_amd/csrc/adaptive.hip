@@ -118,13 +118,14 @@ __global__ void __launch_bounds__(256) attention_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) cdist_gemm_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                          float* __restrict__ P, const int B, const int N, const int T,
-                                                         const int K, const int kchunk, const int tiles_t) {
+                                                         const int K, const int kchunk, const int tiles_t, const long long xsb,
+                                                         const long long xsr) {
     __shared__ float sX[64][36];
     __shared__ float sY[64][36];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int n0 = (blockIdx.x / tiles_t) * 64, t0 = (blockIdx.x % tiles_t) * 64;
     const int ks = blockIdx.y, b = blockIdx.z;
-    const float* Xb = X + (size_t)b * N * K;
+    const float* Xb = X + (size_t)b * xsb;                // (dense: xsb = N K, xsr = K)
     const float* Yb = Y + (size_t)b * T * K;
     const int nsub = (wave >> 1) * 32, tsub = (wave & 1) * 32;
     const int li = lane & 15, kk = lane >> 4;
@@ -136,7 +137,7 @@ __global__ void __launch_bounds__(256) cdist_gemm_kernel(const float* __restrict
         for (int i = 0; i < 2; ++i) {
             const int idx = tid + 256 * i, row = idx >> 3, c4 = idx & 7;
             float4 vx = make_float4(0.f, 0.f, 0.f, 0.f), vy = vx;
-            if (n0 + row < N) vx = *reinterpret_cast<const float4*>(Xb + (size_t)(n0 + row) * K + k0 + 4 * c4);
+            if (n0 + row < N) vx = *reinterpret_cast<const float4*>(Xb + (size_t)(n0 + row) * xsr + k0 + 4 * c4);
             if (t0 + row < T) vy = *reinterpret_cast<const float4*>(Yb + (size_t)(t0 + row) * K + k0 + 4 * c4);
             *reinterpret_cast<float4*>(&sX[row][4 * c4]) = vx;
             *reinterpret_cast<float4*>(&sY[row][4 * c4]) = vy;
@@ -170,9 +171,11 @@ __global__ void __launch_bounds__(256) cdist_gemm_kernel(const float* __restrict
         }
 }
 
-__global__ void __launch_bounds__(256) row_sumsq_kernel(const float* __restrict__ x, const long long K4, float* __restrict__ out) {
+// row blockIdx.x = (b, n), n < rpb, starts at x + b sb + n sr (floats)
+__global__ void __launch_bounds__(256) row_sumsq_kernel(const float* __restrict__ x, const long long K4, float* __restrict__ out,
+                                                        const int rpb, const long long sb, const long long sr) {
     __shared__ float red[256];
-    const float4* xr = reinterpret_cast<const float4*>(x) + (size_t)blockIdx.x * K4;
+    const float4* xr = reinterpret_cast<const float4*>(x + (size_t)(blockIdx.x / rpb) * sb + (size_t)(blockIdx.x % rpb) * sr);
     float s = 0.f;
     for (long long i = threadIdx.x; i < K4; i += 256) {
         const float4 v = xr[i];
@@ -389,7 +392,8 @@ __global__ void dtw_dtemp_combine_kernel(const float* __restrict__ dsum, const f
                                          const int64_t* __restrict__ end_ind, const double* __restrict__ acc,
                                          const double* __restrict__ tan, const float* __restrict__ pad,
                                          const float* __restrict__ log_sigma, double* __restrict__ partial, const int B, const int r,
-                                         const int c) {
+                                         const int c, const float* __restrict__ lsum, const float LD) {
+    // lsum / LD: the matrix and the vector length of the criterion's per-cell value (gcpx_soft_dtw_dtemp: dsum / D themselves)
     extern __shared__ double red[];                     // [4][G][cp]
     const int b = blockIdx.x, t = threadIdx.x, g = threadIdx.y, cp = blockDim.x, G = blockDim.y;
     const float temp = temp_p[0];
@@ -399,10 +403,11 @@ __global__ void dtw_dtemp_combine_kernel(const float* __restrict__ dsum, const f
     const double* TF = tan + (size_t)b * rc;
     const double* TB = tan + (size_t)(B + b) * rc;
     const float* Cb = dsum + (size_t)b * rc;
+    const float* Lb = lsum + (size_t)b * rc;
     const size_t zo = (size_t)(r - 1) * c + (int)end_ind[b];
     const double z = F[zo], zdot = TF[zo];
     const float ls = log_sigma[0];
-    const double iv2 = exp(-2.0 * (double)ls), c0 = (double)D * ((double)ls + 0.91893853320467274178);
+    const double iv2 = exp(-2.0 * (double)ls), c0 = (double)LD * ((double)ls + 0.91893853320467274178);
     double s = 0.0, sd = 0.0, a = 0.0, q = 0.0;
     if (t < c) {
         for (int n = g; n < r; n += G) {
@@ -412,7 +417,7 @@ __global__ void dtw_dtemp_combine_kernel(const float* __restrict__ dsum, const f
             if (isinf(e) || isnan(e)) continue;         // unreachable cell: w = 0 for every temp
             const double wv = (double)(float)exp(e - z);
             const double wd = wv * (TF[o] + TB[o] - neg_cost_dtemp(craw, D, temp) - zdot);
-            const double gl = fma(0.5 * (double)craw, iv2, c0);
+            const double gl = fma(0.5 * (double)Lb[o], iv2, c0);
             s += wv;
             sd += wd;
             a = fma(gl, wd, a);
@@ -1093,6 +1098,22 @@ __global__ void __launch_bounds__(256) row_layernorm_bwd_kernel(const float* __r
     }
 }
 
+// dst[r][c] = ((src[r][c] + src[r][width + c]) + src[r][2 width + c]) + ...: the column blocks of one row summed left to right by
+// one thread (no atomics: the order is the blocks' order whatever the grid).  dst may be block 0 of src.
+__global__ void __launch_bounds__(256) add_col_blocks_kernel(const float* __restrict__ src, const long long ld, const int nblocks,
+                                                             float* __restrict__ dst, const long long ldd, const long long rows,
+                                                             const int width) {
+    const long long total = rows * width;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long r = i / width;
+        const int c = (int)(i % width);
+        const float* s = src + r * ld + c;
+        float acc = s[0];
+        for (int k = 1; k < nblocks; ++k) acc += s[(size_t)k * width];
+        dst[r * ldd + c] = acc;
+    }
+}
+
 }  // namespace
 
 extern "C" int gcpx_attention(const float* q, const float* k, const float* v, const int64_t* start_ind, const int64_t* end_ind,
@@ -1120,12 +1141,25 @@ extern "C" int gcpx_cdist(const float* x, const float* y, int32_t B, int32_t N, 
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     GCPX_CHECK_ARG(x && y && partial && xnorm && ynorm && out, "null pointer");
     GCPX_CHECK_ARG(B > 0 && N > 0 && T > 0 && K > 0 && K % 32 == 0, "K must be a positive multiple of 32");
+    return gcpx_cdist_strided(x, (int64_t)N * K, K, y, B, N, T, K, partial, xnorm, ynorm, out, stream_);
+}
+
+extern "C" int gcpx_cdist_strided(const float* x, int64_t x_sb, int64_t x_sr, const float* y, int32_t B, int32_t N, int32_t T,
+                                  int64_t K, float* partial, float* xnorm, float* ynorm, float* out, void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(x && y && partial && xnorm && ynorm && out, "null pointer");
+    GCPX_CHECK_ARG(B > 0 && N > 0 && T > 0 && K > 0 && K % 32 == 0, "K must be a positive multiple of 32");
+    // rows are read as float4: K floats from x + b x_sb + n x_sr, rows of one batch element K apart at the least
+    GCPX_CHECK_ARG(x_sr >= K && x_sr % 4 == 0 && x_sb % 4 == 0 && x_sb >= 0 && (B == 1 || x_sb >= (int64_t)(N - 1) * x_sr + K) &&
+                   reinterpret_cast<uintptr_t>(x) % 16 == 0, "x strides: multiples of 4 floats, rows that do not overlap, x 16-byte aligned");
     const int ns = gcpx_cdist_splits(K);
     const int tiles_n = (N + 63) / 64, tiles_t = (T + 63) / 64;
-    hipLaunchKernelGGL(row_sumsq_kernel, dim3(B * N), dim3(256), 0, stream, x, (long long)(K / 4), xnorm);
-    hipLaunchKernelGGL(row_sumsq_kernel, dim3(B * T), dim3(256), 0, stream, y, (long long)(K / 4), ynorm);
+    hipLaunchKernelGGL(row_sumsq_kernel, dim3(B * N), dim3(256), 0, stream, x, (long long)(K / 4), xnorm, N, (long long)x_sb,
+                       (long long)x_sr);
+    hipLaunchKernelGGL(row_sumsq_kernel, dim3(B * T), dim3(256), 0, stream, y, (long long)(K / 4), ynorm, T, (long long)T * K,
+                       (long long)K);
     hipLaunchKernelGGL(cdist_gemm_kernel, dim3(tiles_n * tiles_t, ns, B), dim3(256), 0, stream, x, y, partial, B, N, T, (int)K,
-                       (int)(K / ns), tiles_t);
+                       (int)(K / ns), tiles_t, (long long)x_sb, (long long)x_sr);
     const size_t total = (size_t)B * N * T;
     const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
     hipLaunchKernelGGL(cdist_finish_kernel, dim3(grid), dim3(256), 0, stream, partial, ns, xnorm, ynorm, out, B, N, T);
@@ -1155,19 +1189,29 @@ extern "C" int gcpx_soft_dtw(const float* dsum, float D, const float* temp, cons
 extern "C" int gcpx_soft_dtw_dtemp(const float* dsum, float D, const float* temp, const int64_t* end_ind, const double* acc,
                                    const float* pad_mask, const float* log_sigma, float coef, int32_t B, int32_t N, int32_t T,
                                    double* tangent, double* partial, float* dtemp, void* stream_) {
+    GCPX_CHECK_ARG(dsum, "null pointer");
+    return gcpx_soft_dtw_dtemp_split(dsum, D, dsum, D, temp, end_ind, acc, pad_mask, log_sigma, coef, B, N, T, tangent, partial, dtemp,
+                                     stream_);
+}
+
+extern "C" int gcpx_soft_dtw_dtemp_split(const float* cost_dsum, float cost_D, const float* loss_dsum, float loss_D, const float* temp,
+                                         const int64_t* end_ind, const double* acc, const float* pad_mask, const float* log_sigma,
+                                         float coef, int32_t B, int32_t N, int32_t T, double* tangent, double* partial, float* dtemp,
+                                         void* stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    GCPX_CHECK_ARG(dsum && temp && end_ind && acc && pad_mask && log_sigma && tangent && partial && dtemp, "null pointer");
+    GCPX_CHECK_ARG(cost_dsum && loss_dsum && temp && end_ind && acc && pad_mask && log_sigma && tangent && partial && dtemp,
+                   "null pointer");
     GCPX_CHECK_ARG(B > 0 && N >= T && T > 0, "needs at least as many nodes as frames (probabilistic_dtw.py:36)");
     if (T > 1024) {
         gcpx_set_error("gcpx_soft_dtw_dtemp: sequences longer than 1024 frames are not built");
         return GCPX_ERR_UNSUPPORTED;
     }
     const int threads = (T + 63) / 64 * 64;
-    hipLaunchKernelGGL(dtw_tangent_sweep_kernel, dim3(2 * B), dim3(threads), 4 * threads * sizeof(double), stream, dsum, D, temp,
-                       end_ind, acc, tangent, B, N, T);
+    hipLaunchKernelGGL(dtw_tangent_sweep_kernel, dim3(2 * B), dim3(threads), 4 * threads * sizeof(double), stream, cost_dsum, cost_D,
+                       temp, end_ind, acc, tangent, B, N, T);
     const int G = threads <= 256 ? 4 : (threads <= 512 ? 2 : 1);
-    hipLaunchKernelGGL(dtw_dtemp_combine_kernel, dim3(B), dim3(threads, G), 4 * G * threads * sizeof(double), stream, dsum, D, temp,
-                       end_ind, acc, tangent, pad_mask, log_sigma, partial, B, N, T);
+    hipLaunchKernelGGL(dtw_dtemp_combine_kernel, dim3(B), dim3(threads, G), 4 * G * threads * sizeof(double), stream, cost_dsum, cost_D,
+                       temp, end_ind, acc, tangent, pad_mask, log_sigma, partial, B, N, T, loss_dsum, loss_D);
     hipLaunchKernelGGL(dtw_dtemp_finish_kernel, dim3(1), dim3(1), 0, stream, partial, B, coef, dtemp);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
@@ -1290,6 +1334,19 @@ extern "C" int gcpx_row_layernorm_bwd(const float* dy, const float* y, const flo
     GCPX_CHECK_ARG(dy && y && rstd && dx, "null pointer");
     GCPX_CHECK_ARG(M > 0 && W > 0 && W % 4 == 0 && W <= 1024, "rows of 4 .. 1024 floats, a multiple of 4");
     hipLaunchKernelGGL(row_layernorm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, dy, y, rstd, dx, M, W);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_add_col_blocks(const float* src, int64_t ld, int32_t nblocks, float* dst, int64_t ldd, int64_t rows, int32_t width,
+                                   void* stream_) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    GCPX_CHECK_ARG(src && dst, "null pointer");
+    GCPX_CHECK_ARG(rows > 0 && width > 0 && nblocks > 0 && ld >= (int64_t)nblocks * width && ldd >= width, "bad sizes");
+    const long long total = (long long)rows * width;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(add_col_blocks_kernel, dim3(grid), dim3(256), 0, stream, src, (long long)ld, nblocks, dst, (long long)ldd,
+                       (long long)rows, width);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

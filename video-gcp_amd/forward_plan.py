@@ -681,14 +681,28 @@ class ForwardPlanMixin:
             row = hp.input_nc * S * S
             if matching:
                 # AdaptiveBinding.get_w (adaptive.py:32-60): image cost matrix -> soft-DTW posterior over alignments -> w
-                ns = lib.gcpx_cdist_splits(row)
-                dsum = self._buf("cdist.dsum", (B, N, T))
-                plan.add("cdist", lib.gcpx_cdist, images.data_ptr(), tin["traj_seq"].data_ptr(), B, N, T, row,
-                         self._buf("cdist.part", (ns, B, N, T)).data_ptr(), self._buf("cdist.xn", (B * N,)).data_ptr(),
-                         self._buf("cdist.yn", (B * T,)).data_ptr(), dsum.data_ptr())
+                latent = hp.matching_type == "dtw_latent"
+                dsum = None
+                if with_loss or not latent:
+                    # the image cost: the matching cost of 'dtw_image', and the criterion's distances in both forms
+                    # (LossAveragingCriterion.loss takes batch_cdist(predictions, targets), binding_loss.py:24)
+                    ns = lib.gcpx_cdist_splits(row)
+                    dsum = self._buf("cdist.dsum", (B, N, T))
+                    plan.add("cdist", lib.gcpx_cdist, images.data_ptr(), tin["traj_seq"].data_ptr(), B, N, T, row,
+                             self._buf("cdist.part", (ns, B, N, T)).data_ptr(), self._buf("cdist.xn", (B * N,)).data_ptr(),
+                             self._buf("cdist.yn", (B * T,)).data_ptr(), dsum.data_ptr())
+                cost, cost_D = dsum, row
+                if latent:
+                    # adaptive.py:45-47: cost between tree.df.e_g_prime and enc_traj_seq, 'mean' over nz_enc.  The node latents are
+                    # read where the tree left them: node n of the depth-first order is slot n + 1 of E
+                    ns = lib.gcpx_cdist_splits(nz)
+                    cost, cost_D = self._buf("cdist.lat.dsum", (B, N, T)), nz
+                    plan.add("cdist.latent", lib.gcpx_cdist_strided, _addr(E, nz), PS * nz, nz, enc_traj.data_ptr(), B, N, T, nz,
+                             self._buf("cdist.lat.part", (ns, B, N, T)).data_ptr(), self._buf("cdist.lat.xn", (B * N,)).data_ptr(),
+                             self._buf("cdist.lat.yn", (B * T,)).data_ptr(), cost.data_ptr())
                 wdf = self._buf("match_dist_df", (B, N, T))
                 temp = self.sd["tree_module.tree_modules.0.binding.temp"]
-                plan.add("soft_dtw", lib.gcpx_soft_dtw, dsum.data_ptr(), C.c_float(float(row)), temp.data_ptr(), tin["end_ind"].data_ptr(),
+                plan.add("soft_dtw", lib.gcpx_soft_dtw, cost.data_ptr(), C.c_float(float(cost_D)), temp.data_ptr(), tin["end_ind"].data_ptr(),
                          B, N, T, self._buf("dtw.acc", (2 * B, N, T), torch.float64).data_ptr(), wdf.data_ptr())
                 outs["dtw_acc"] = self._buf("dtw.acc", (2 * B, N, T), torch.float64)
                 matched_idx = self._buf("matched_idx", (B, T), torch.int32)
@@ -708,7 +722,8 @@ class ForwardPlanMixin:
                 ent_sum = self._buf("entropy_sum", (1,))
                 plan.add("entropy_sum", lib.gcpx_reduce_partials, entropy.data_ptr(), B * N, 1, 1, ent_sum.data_ptr(), 0)
                 outs["entropy_sum"] = ent_sum
-                outs.update(cdist_sum=dsum, match_dist_df=wdf, matched_idx=matched_idx, best_t=best_t, entropy_df=entropy, p_n_df=p_n,
+                plan.rec["match_cost_D"] = cost_D
+                outs.update(cdist_sum=dsum, match_cost_sum=cost, match_dist_df=wdf, matched_idx=matched_idx, best_t=best_t, entropy_df=entropy, p_n_df=p_n,
                             distance_target=dist_tgt, aux_len=seq_len)
             elif has_traj and phase == "train":
                 if rows_images is not None:

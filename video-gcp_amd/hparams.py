@@ -46,7 +46,8 @@ class GCPHParams:
     lstm_init: str = "mlp"
     seq_enc: str = "conv"
     context_every_step: bool = True
-    matching_type: str = "balanced"    # or "dtw_image" (adaptive binding, base_configs/gcp_adaptive.py:8)
+    matching_type: str = "balanced"    # or "dtw_image" (adaptive binding, base_configs/gcp_adaptive.py:8), or "dtw_latent" (the
+                                       # same binding with the matching cost between latents, adaptive.py:45-47)
     attentive_inference: bool = False  # base_configs/gcp_adaptive.py:10
     attention_temperature: float = 1.0  # hyperparameters.py:60 (learn_attn_temp=True: a parameter)
     matching_temp: float = 1.0         # hyperparameters.py:94
@@ -91,7 +92,7 @@ class GCPHParams:
         assert self.img_sz in (32, 64), "decoder kernels are built for 32x32 (reference default, base_model.py:41) and 64x64"
         assert self.nz_mid % self.gn_groups == 0 and self.init_mlp_mid_sz % self.gn_groups == 0
         assert self.decoder_distribution in ("discrete_logistic_mixture", "gaussian")
-        assert self.matching_type in ("balanced", "dtw_image")
+        assert self.matching_type in ("balanced", "dtw_image", "dtw_latent")
         assert self.var_inf in ("standard", "deterministic"), "var_inf '2layer' is not built"
         assert (self.var_inf == "deterministic") == (self.nz_vae == 0), "a deterministic predictor has no latent: nz_vae = 0 (vmpc.py:14-15)"
         assert self.nz_attn_key % self.n_attention_heads == 0 and self.nz_enc % self.n_attention_heads == 0

@@ -118,7 +118,7 @@ class GCPTreeModel(WeightsMixin, PlanOpsMixin, ForwardPlanMixin, ReplayMixin):
             self.cost_mdl = Hd.CostModelHandle(self)
 
     def _check_hp(self, hp):
-        assert hp.matching_type in ("balanced", "dtw_image")
+        assert hp.matching_type in ("balanced", "dtw_image", "dtw_latent")
         if hp.tree_lstm not in ("split_linear", "linear", "sum", ""):              # tree_lstm.py:52-60; '' = the non-LSTM subgoal
             raise ValueError("don't know this TreeLSTM type")                      # predictor (tree_module.py:45-46,109-110)
         if hp.seq_enc not in ("conv", "none"):

@@ -259,6 +259,10 @@ SYMBOLS = [
     ("gcpx_attention_bwd_heads", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     ("gcpx_row_layernorm", C.c_int, [vp, vp, vp, vp, i32, i32, C.c_float, vp]),
     ("gcpx_row_layernorm_bwd", C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
+    # tied tree levels under the attentive posterior; matching_type = 'dtw_latent' (adaptive.py:45-47)
+    ("gcpx_add_col_blocks", C.c_int, [vp, i64, i32, vp, i64, i64, i32, vp]),
+    ("gcpx_cdist_strided", C.c_int, [vp, i64, i64, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp]),
+    ("gcpx_soft_dtw_dtemp_split", C.c_int, [vp, C.c_float, vp, C.c_float, vp, vp, vp, vp, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp]),
     ("gcpx_dtw_align", C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     ("gcpx_graph_begin", C.c_int, [vp]),
     ("gcpx_graph_end", C.c_int, [vp, C.POINTER(vp)]),

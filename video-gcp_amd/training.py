@@ -72,7 +72,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         hp = model._hp
         if hp.decoder_distribution == "gaussian" and hp.adaptive:
             # (the averaging criterion's image gradient would have to go through tanh instead of through the mixture mean)
-            raise ValueError("training the adaptive (matching_type='dtw_image') model with decoder_distribution='gaussian' is not built: "
+            raise ValueError(f"training the adaptive (matching_type='{hp.matching_type}') model with decoder_distribution='gaussian' is not built: "
                              "its backward takes the image gradient through the mixture mean of the discrete_logistic_mixture head")
         self.m = model
         self.lr, self.betas, self.eps = lr, betas, eps
