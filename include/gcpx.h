@@ -897,6 +897,21 @@ int gcpx_grad_clip_coef(const float* grad, int64_t n, float grad_scale, float ma
    outside [dst, dst + n) is written.  max_blocks as in gcpx_optim_range (0 = full grid).  n = 0 is a no-op that returns 0.
    Memory bound: 12 n bytes of traffic (8 n with assign). */
 int gcpx_grad_accumulate(float* dst, const float* src, int64_t n, int32_t assign, int32_t max_blocks, void* stream);
+/* Exponential moving average of the weights (the trainer's ema_decay; no reference counterpart).  With omd = 1.0f - decay formed once
+   in float32 (exact for decay >= 0.5, Sterbenz), per element: d = theta[i] - ema[i] (one float32 rounding), ema[i] = fmaf(omd, d, ema[i])
+   (one rounding); nothing else is contracted or reassociated, so the result does not depend on how a vector is cut into calls, and
+   NaN / +-Inf propagate (the training guard, not this kernel, keeps them out).  gate: NULL = always update; otherwise one device float
+   read at kernel entry, non-zero = return having written nothing (the trainer passes opt_state + 3: a step gcpx_grad_health closed
+   moves the average no more than it moves theta or the moments).  ema and theta are any 4-byte aligned, non-overlapping slices: both
+   16-byte aligned takes four elements per access, two accesses in flight; the last n % 4 elements and unaligned slices a scalar loop.
+   Nothing outside [ema, ema + n) is written.  max_blocks as in gcpx_optim_range (0 = full grid).  n = 0 returns 0 and launches
+   nothing.  decay outside (0, 1) or NaN, n < 0, a null ema or theta with n > 0: GCPX_ERR_INVALID_ARG before any HIP call.
+   Memory bound: 12 n bytes of traffic. */
+int gcpx_ema_update(float* ema, const float* theta, int64_t n, float decay, const float* gate, int32_t max_blocks, void* stream);
+/* Exchanges [a, a + n) and [b, b + n) as 32-bit words (the trainer's ema_weights(): theta <-> average): NaN payloads and -0 keep
+   their bits.  Alignment, max_blocks, n = 0 and the argument checks as in gcpx_ema_update; nothing outside the two ranges is
+   written; overlapping ranges are the caller's error.  Memory bound: 16 n bytes of traffic. */
+int gcpx_swap_f32(float* a, float* b, int64_t n, int32_t max_blocks, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * hipGraph helpers: capture a launch sequence once, replay it per step.

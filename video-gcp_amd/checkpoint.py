@@ -17,8 +17,9 @@ def checkpoint_name(epoch):
     return f"weights_ep{epoch}.pth"
 
 
-def save_checkpoint(model, folder, epoch, global_step=0, optimizer_state=None, name=None):
-    """name: the file's name in `folder` instead of weights_ep{epoch}.pth (the guard's nan_debug_ckpt.pth, base_trainer.py:62-66)"""
+def save_checkpoint(model, folder, epoch, global_step=0, optimizer_state=None, name=None, ema_state=None):
+    """name: the file's name in `folder` instead of weights_ep{epoch}.pth (the guard's nan_debug_ckpt.pth, base_trainer.py:62-66)
+    ema_state: the trainer's ema_state() -- stored under the top-level key "ema", which exists only when a state is given"""
     os.makedirs(folder, exist_ok=True)
     state = {"epoch": epoch, "global_step": global_step,
              "state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
@@ -27,6 +28,8 @@ def save_checkpoint(model, folder, epoch, global_step=0, optimizer_state=None, n
     rng = model.rng_state() if hasattr(model, "rng_state") else None
     if rng is not None:
         state["rng_state"] = rng
+    if ema_state is not None:
+        state["ema"] = ema_state
     path = os.path.join(folder, checkpoint_name(epoch) if name is None else name)
     torch.save(state, path)
     return path
@@ -63,15 +66,30 @@ def resumed_rng_state(stored, own_key, world):
     return (key, offset) if world <= 1 else (int(own_key), offset)
 
 
-def load_weights(weights_file, model, submodule_name=None, strict=True):
-    """Returns (global_step, epoch, optimizer_state).  checkpoint_handler.py:45-74,133-143: with `submodule_name` only keys under
+def read_ema_state(weights_file):
+    """the "ema" entry of a checkpoint (the trainer's ema_state(): decay, warmup, updates, state_dict), or None when it was written
+    without a weight average"""
+    if not os.path.isfile(weights_file):
+        raise ValueError("Could not find checkpoint file in {}!".format(weights_file))
+    return torch.load(weights_file, map_location="cpu").get("ema")
+
+
+def load_weights(weights_file, model, submodule_name=None, strict=True, use_ema=False):
+    """Returns (global_step, epoch, optimizer_state).  use_ema: the averaged weights (ckpt["ema"]["state_dict"], BatchNorm running
+    statistics included) are loaded in place of ckpt["state_dict"], under the same `submodule_name` and `strict` rules; ValueError when
+    the checkpoint holds no average.  checkpoint_handler.py:45-74,133-143: with `submodule_name` only keys under
     that prefix are loaded.  (The reference strips the prefix because it loads INTO the sub-module; this model holds the
     sub-module under the same name, so the prefix stays.)  strict: every parameter of the model — of that sub-module, when one is
     named — must be in the checkpoint, and no key of the (filtered) checkpoint may be unknown to the model."""
     if not os.path.isfile(weights_file):
         raise ValueError("Could not find checkpoint file in {}!".format(weights_file))
     ckpt = torch.load(weights_file, map_location="cpu")
-    sd = ckpt["state_dict"]
+    if use_ema:
+        if not isinstance(ckpt.get("ema"), dict) or "state_dict" not in ckpt["ema"]:
+            raise ValueError("checkpoint {} holds no weight average (it was trained without ema_decay)".format(weights_file))
+        sd = ckpt["ema"]["state_dict"]
+    else:
+        sd = ckpt["state_dict"]
     own = set(model.state_dict())
     if submodule_name is not None:
         sd = {k: v for k, v in sd.items() if k.startswith(submodule_name + ".")}

@@ -562,14 +562,16 @@ def planner_from_control_conf(config, **over):
                     pairs=(config.get("start_index"), config.get("end_index")), ignored=ignored)
 
 
-def build_policy(description, device, weights=None, seed=0, random_weights=False, reference_rng=False, verbose=None):
+def build_policy(description, device, weights=None, seed=0, random_weights=False, reference_rng=False, verbose=None, use_ema=False):
     """(model, planner, policy) of a planner_from_control_conf description on `device`: the planning.* objects a user who owns an
     environment loop drives through `policy.act(t=..., images=..., goal_image=...)`.
     The model is GCPTreeModel, or GCPSequentialModel for policy.model_cls = SequentialModel: then the simulator is
     ActCondGCPImageSimulator under act_cond (visual MPC) and GCPImageSimulator without drawn lengths otherwise (CEM in its latents).
     weights: a checkpoint file instead of the conf's; random_weights: run on the seeded initialisation when no checkpoint resolves
     (otherwise that raises); seed: of the initialisation, and seed + 1 of the planner's draws; reference_rng: the hierarchical
-    planner replays the reference's np.random sequence; verbose: keep the per-iteration elites (default: the conf's `verbose`)."""
+    planner replays the reference's np.random sequence; verbose: keep the per-iteration elites (default: the conf's `verbose`);
+    use_ema: load the checkpoints' averaged weights (checkpoint.load_weights(use_ema=True)), the cost model's own checkpoint included --
+    a checkpoint without an average, or no checkpoint at all, raises."""
     from . import planning as P
     from .checkpoint import load_weights
     from .model import GCPTreeModel
@@ -583,12 +585,14 @@ def build_policy(description, device, weights=None, seed=0, random_weights=False
     else:
         model = GCPTreeModel(hp, params=init_params(hp, seed=seed), device=device)
     main = weights or d.weights["file"]
+    if use_ema and not main:
+        raise ValueError("use_ema needs a checkpoint: averaged weights exist only in one")
     if main:
-        load_weights(main, model)
+        load_weights(main, model, use_ema=bool(use_ema))
         if d.weights["cost_path"] and not weights:
             if not d.weights["cost_file"]:
                 raise ValueError(f"no checkpoint of the cost model at cost_config.checkpt_path = {d.weights['cost_path']}")
-            load_weights(d.weights["cost_file"], model, submodule_name="cost_mdl")
+            load_weights(d.weights["cost_file"], model, submodule_name="cost_mdl", use_ema=bool(use_ema))
     elif not random_weights:
         raise ValueError(f"no checkpoint at policy.checkpt_path = {d.weights['path']!r} (load_epoch = {d.weights['epoch'] or 'latest'}): "
                          "give a weights file, or ask for random weights")

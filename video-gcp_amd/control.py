@@ -197,6 +197,8 @@ def get_args(argv=None):
     p.add_argument("--random_weights", type=int, default=0, help="1 = run on the seeded initialisation when the conf's checkpoint does not "
                    "resolve (an error otherwise)")
     p.add_argument("--weights", default="", help="a checkpoint file instead of the conf's")
+    p.add_argument("--use_ema", type=int, default=0, choices=(0, 1), help="1 = act on the checkpoint's averaged weights (trained with "
+                   "--ema_decay), the cost model's own checkpoint included; an error when a checkpoint holds none")
     p.add_argument("--tasks", default="", help=".npz with `start` [K, 3] and `goal` [K, 2] in the environment's units")
     p.add_argument("--task_seed", type=int, default=0, help="without --tasks: the seed of the drawn tasks (NavGenerator.draw_task)")
     p.add_argument("--n_tasks", type=int, default=None, help="at most this many of the tasks start_index .. end_index of the conf")
@@ -232,7 +234,7 @@ def main(argv=None):
     for k in env_desc.ignored:
         print(f"[control] not used from {os.path.basename(args.experiment)}: {k}", flush=True)
     model, planner, _ = CL.build_policy(desc, dev, weights=args.weights or None, seed=args.seed, random_weights=bool(args.random_weights),
-                                        reference_rng=args.reference_rng, verbose=False)
+                                        reference_rng=args.reference_rng, verbose=False, use_ema=bool(args.use_ema))
     needs_inv = [k for k, v in (("policy.closed_loop_execution = True", desc.policy_args["closed_loop_execution"]),
                                 ("cem_params.use_inferred_actions = True", desc.get("action_source", "inverse_model") == "inverse_model")) if v]
     if needs_inv and not model._hp.attach_inv_mdl:

@@ -484,6 +484,72 @@ __global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict_
     for (long long i = done + first; i < n; i += stride) dst[i] = ASSIGN ? src[i] : dst[i] + src[i];
 }
 
+// Exponential moving average of the flat parameter vector: ema += (1 - decay) (theta - ema).  Two f32 roundings per element -- the
+// difference, then one fused multiply-add -- and nothing else to contract or reassociate, so, as above, a vector cut into slices leaves
+// the bits of one call.  `gate`: NULL, or one device float read at entry (the trainer passes opt_state + 3): non-zero returns with
+// nothing written, the branch uniform over the launch as in radam_kernel.  VEC as in grad_accumulate_kernel, component-wise (this
+// file: no packed f32).
+__device__ __forceinline__ float ema_one(const float e, const float t, const float omd) {
+    const float d = t - e;
+    return fmaf(omd, d, e);
+}
+__device__ __forceinline__ void ema_upd4(float4& e, const float4& t, const float omd) {
+    e.x = ema_one(e.x, t.x, omd); e.y = ema_one(e.y, t.y, omd); e.z = ema_one(e.z, t.z, omd); e.w = ema_one(e.w, t.w, omd);
+}
+template <bool VEC>
+__global__ void __launch_bounds__(256) ema_update_kernel(float* __restrict__ ema, const float* __restrict__ theta, const long long n,
+                                                         const float omd, const float* __restrict__ gate) {
+    if (gate != nullptr && gate[0] != 0.f) return;
+    const long long stride = (long long)gridDim.x * 256, first = (long long)blockIdx.x * 256 + threadIdx.x;
+    long long done = 0;
+    if (VEC) {
+        const long long n4 = n >> 2;
+        float4* __restrict__ e4 = reinterpret_cast<float4*>(ema);
+        const float4* __restrict__ t4 = reinterpret_cast<const float4*>(theta);
+        for (long long i = first; i < n4; i += 2 * stride) {
+            const long long j = i + stride;
+            const bool two = j < n4;
+            float4 ta = t4[i], tb = ta;
+            if (two) tb = t4[j];
+            float4 ea = e4[i], eb = ea;
+            if (two) eb = e4[j];
+            ema_upd4(ea, ta, omd);
+            e4[i] = ea;
+            if (two) { ema_upd4(eb, tb, omd); e4[j] = eb; }
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + first; i < n; i += stride) ema[i] = ema_one(ema[i], theta[i], omd);
+}
+
+// Exchange of two ranges as 32-bit words (the trainer's ema_weights(): theta <-> ema): integer loads and stores, so NaN payloads and
+// -0 keep their bits.  VEC as above.
+template <bool VEC>
+__global__ void __launch_bounds__(256) swap_words_kernel(unsigned int* __restrict__ a, unsigned int* __restrict__ b, const long long n) {
+    const long long stride = (long long)gridDim.x * 256, first = (long long)blockIdx.x * 256 + threadIdx.x;
+    long long done = 0;
+    if (VEC) {
+        const long long n4 = n >> 2;
+        uint4* __restrict__ a4 = reinterpret_cast<uint4*>(a);
+        uint4* __restrict__ b4 = reinterpret_cast<uint4*>(b);
+        for (long long i = first; i < n4; i += 2 * stride) {
+            const long long j = i + stride;
+            const bool two = j < n4;
+            uint4 xa = a4[i], ya = b4[i], xb = xa, yb = ya;
+            if (two) { xb = a4[j]; yb = b4[j]; }
+            a4[i] = ya;
+            b4[i] = xa;
+            if (two) { a4[j] = yb; b4[j] = xb; }
+        }
+        done = n4 << 2;
+    }
+    for (long long i = done + first; i < n; i += stride) {
+        const unsigned int x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
 int blocks_for(long long items, int cap = 4096) {
     long long b = (items + 255) / 256;
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
@@ -581,6 +647,45 @@ extern "C" int gcpx_grad_accumulate(float* dst, const float* src, int64_t n, int
     else if (vec) hipLaunchKernelGGL((grad_accumulate_kernel<true, false>), grid, block, 0, stream, dst, src, (long long)n);
     else if (assign) hipLaunchKernelGGL((grad_accumulate_kernel<false, true>), grid, block, 0, stream, dst, src, (long long)n);
     else hipLaunchKernelGGL((grad_accumulate_kernel<false, false>), grid, block, 0, stream, dst, src, (long long)n);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_ema_update(float* ema, const float* theta, int64_t n, float decay, const float* gate, int32_t max_blocks,
+                               void* stream_) {
+    STREAM();
+    GCPX_CHECK_ARG(decay > 0.f && decay < 1.f, "decay must lie in (0, 1)");          // (a NaN fails both comparisons)
+    GCPX_CHECK_ARG(n >= 0, "n >= 0");
+    GCPX_CHECK_ARG(max_blocks >= 0, "max_blocks: 0 (no limit) or a positive number of workgroups");
+    if (n == 0) return GCPX_OK;
+    GCPX_CHECK_ARG(ema && theta, "ema / theta: null with n > 0");
+    GCPX_CHECK_ARG(((((uintptr_t)ema | (uintptr_t)theta | (uintptr_t)gate) & 3) == 0), "ema / theta / gate: 4-byte aligned device pointers");
+    const float omd = 1.0f - decay;
+    const bool vec = ((((uintptr_t)ema | (uintptr_t)theta) & 15) == 0) && n >= 4;
+    int nb = blocks_for(vec ? (n + 7) / 8 : n, 16384);
+    if (max_blocks > 0) nb = std::min(nb, max_blocks);
+    const dim3 grid(nb), block(256);
+    if (vec) hipLaunchKernelGGL((ema_update_kernel<true>), grid, block, 0, stream, ema, theta, (long long)n, omd, gate);
+    else hipLaunchKernelGGL((ema_update_kernel<false>), grid, block, 0, stream, ema, theta, (long long)n, omd, gate);
+    GCPX_CHECK_LAUNCH();
+    return GCPX_OK;
+}
+
+extern "C" int gcpx_swap_f32(float* a, float* b, int64_t n, int32_t max_blocks, void* stream_) {
+    STREAM();
+    GCPX_CHECK_ARG(n >= 0, "n >= 0");
+    GCPX_CHECK_ARG(max_blocks >= 0, "max_blocks: 0 (no limit) or a positive number of workgroups");
+    if (n == 0) return GCPX_OK;
+    GCPX_CHECK_ARG(a && b, "a / b: null with n > 0");
+    GCPX_CHECK_ARG(((((uintptr_t)a | (uintptr_t)b) & 3) == 0), "a / b: 4-byte aligned device pointers");
+    const bool vec = ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) && n >= 4;
+    int nb = blocks_for(vec ? (n + 7) / 8 : n, 16384);
+    if (max_blocks > 0) nb = std::min(nb, max_blocks);
+    const dim3 grid(nb), block(256);
+    unsigned int* ua = reinterpret_cast<unsigned int*>(a);
+    unsigned int* ub = reinterpret_cast<unsigned int*>(b);
+    if (vec) hipLaunchKernelGGL((swap_words_kernel<true>), grid, block, 0, stream, ua, ub, (long long)n);
+    else hipLaunchKernelGGL((swap_words_kernel<false>), grid, block, 0, stream, ua, ub, (long long)n);
     GCPX_CHECK_LAUNCH();
     return GCPX_OK;
 }

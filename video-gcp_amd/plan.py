@@ -32,6 +32,8 @@ def get_args(argv=None):
                    "conf's checkpoint does not resolve (an error otherwise)")
     p.add_argument("--config", default="c4")
     p.add_argument("--weights", default="", help="checkpoint (weights_ep*.pth); random init when empty")
+    p.add_argument("--use_ema", type=int, default=0, choices=(0, 1), help="1 = plan on the checkpoint's averaged weights (trained with "
+                   "--ema_decay), the cost model's own checkpoint included; an error when a checkpoint holds none")
     p.add_argument("--pairs", default="", help=".npz with uint8 `start`, `goal` [K, H, W, 3]")
     p.add_argument("--nstart_goal_pairs", type=int, default=4)
     p.add_argument("--planner", default="cem", choices=["cem", "hierarchical"])
@@ -76,12 +78,14 @@ def main(argv=None):
         hp = desc.hp
         model, planner, _ = CL.build_policy(desc, dev, weights=args.weights or None, seed=args.seed,
                                             random_weights=bool(args.random_weights), reference_rng=args.reference_rng,
-                                            verbose=desc.verbose and bool(args.out))
+                                            verbose=desc.verbose and bool(args.out), use_ema=bool(args.use_ema))
     else:
         hp = config(args.config)
         model = GCPTreeModel(hp, params=init_params(hp, seed=args.seed), device=dev)
+        if args.use_ema and not args.weights:
+            raise ValueError("--use_ema 1 needs --weights: averaged weights exist only in a checkpoint")
         if args.weights:
-            load_weights(args.weights, model)
+            load_weights(args.weights, model, use_ema=bool(args.use_ema))
         model.eval()                                                 # planner_policy.py:51
     if args.pairs:
         z = np.load(args.pairs)

@@ -241,6 +241,8 @@ SYMBOLS = [
     ("gcpx_grad_clip_coef", C.c_int, [vp, i64, C.c_float, C.c_float, vp, i32, vp, vp]),
     ("gcpx_optim_range", C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, i32, vp]),
     ("gcpx_grad_accumulate", C.c_int, [vp, vp, i64, i32, i32, vp]),
+    ("gcpx_ema_update", C.c_int, [vp, vp, i64, C.c_float, vp, i32, vp]),
+    ("gcpx_swap_f32", C.c_int, [vp, vp, i64, i32, vp]),
     ("gcpx_repack_blocks", C.c_int, [vp, vp, vp, vp, i64, i32, vp]),
     ("gcpx_radam_step", C.c_int, [vp, vp, vp, vp, vp, i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]),
     ("gcpx_attention", C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

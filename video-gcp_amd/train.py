@@ -58,6 +58,12 @@ makes every optimizer step the mean gradient of k consecutive micro-batches, eac
 many data-parallel ranks compute, up to the summation order and the noise streams (training.py, dataset.accumulate_schedule).
 global_step, model.step() (KL burn-in), the picture-log interval and the print / scalar-log block count optimizer steps; the printed
 and logged loss terms are the cycle's means; `--nan_guard raise` dumps the inputs of the cycle's LAST micro-batch.  Defaults to 1.
+Weight average: `--ema_decay D` (no reference counterpart, a flag only) keeps an exponential moving average of the weights and BatchNorm
+running statistics on the device, moved once per optimizer step (training.py); `--ema_warmup 1` (default) uses min(D, (1 + t) / (10 + t))
+for update t.  With `--eval_ema 1` (default) every validation pass, `--metric 1` and the validation-phase picture logs run on the averaged
+weights (trainer.ema_weights()); checkpoints store the average under "ema" and `--resume` restores it (a checkpoint without one: the
+average starts from the loaded weights, with a warning).  `--metric 1 --resume CKPT` without `--ema_decay` evaluates the checkpoint's
+average when it holds one (`--eval_ema 0`: its weights).  Defaults to 0 = off: no allocation, no launch, no extra checkpoint key.
 """
 import argparse
 import json
@@ -104,10 +110,23 @@ def get_cmd_args(argv=None):
                    "'skip' drops the step and goes on")
     p.add_argument("--accumulate_steps", default=1, type=int, help="micro-batches of `batch_size` whose mean gradient makes one optimizer "
                    "step: one GPU then trains with the batch of k ranks")
+    p.add_argument("--ema_decay", default=0.0, type=float, help="decay in (0, 1) of an exponential moving average of the weights, moved on "
+                   "the device once per optimizer step; 0 = none")
+    p.add_argument("--ema_warmup", default=1, type=int, choices=(0, 1), help="if 1, update t uses min(ema_decay, (1 + t) / (10 + t))")
+    p.add_argument("--eval_ema", default=1, type=int, choices=(0, 1), help="if 1, validation, --metric and the validation picture logs "
+                   "run on the averaged weights (with --ema_decay, or under --metric on a resumed checkpoint that holds an average)")
     args = p.parse_args(argv)
     if args.accumulate_steps < 1:
         p.error("--accumulate_steps must be at least 1")
+    if args.ema_decay != 0.0 and not 0.0 < args.ema_decay < 1.0:
+        p.error("--ema_decay must be 0 (off) or lie in (0, 1)")
     return args
+
+
+def ema_kwargs(args):
+    """the trainer's weight-average arguments: none at all for --ema_decay 0, so that the trainer is built as it always was"""
+    decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
+    return dict(ema_decay=decay, ema_warmup=bool(getattr(args, "ema_warmup", 1))) if decay else {}
 
 
 def startup_line(micro_batch, accumulate, world):
@@ -249,6 +268,9 @@ class ModelTrainer:
         self.accumulate = k_acc = int(getattr(args, "accumulate_steps", 1) or 1)
         if k_acc > 1:
             guard_kw["accumulate"] = k_acc
+        guard_kw.update(ema_kwargs(args))
+        self.eval_ema = bool(getattr(args, "eval_ema", 1))
+        self._ema_loaded = False              # --metric on a checkpoint with an average: theta itself holds the averaged weights
         if self.rank == 0:
             print(startup_line(hp.batch_size, k_acc, max(self.world, 1)), flush=True)
         self.trainer = step_cls(self.model, lr=lr, betas=(conf.get("adam_beta", 0.9), 0.999), process_group=pg,
@@ -319,9 +341,17 @@ class ModelTrainer:
             f = CK.get_resume_ckpt_file(ckpt, folder)
         except CK.NoCheckpointsException:               # train.py:59-62: `--resume latest` on a fresh experiment starts at epoch 0
             return 0
-        self.global_step, epoch, opt = CK.load_weights(f, self.model, strict=bool(self.cmd_args.strict_weight_loading))
+        strict = bool(self.cmd_args.strict_weight_loading)
+        if getattr(self.cmd_args, "metric", False) and self.eval_ema and self.trainer.ema is None and CK.read_ema_state(f) is not None:
+            # an evaluation pass of a checkpoint that holds an average, by a trainer that keeps none: the averaged weights are loaded
+            self.global_step, epoch, opt = CK.load_weights(f, self.model, strict=strict, use_ema=True)
+            self._ema_loaded = True
+        else:
+            self.global_step, epoch, opt = CK.load_weights(f, self.model, strict=strict)
         if opt is not None:
             self.trainer.load_optimizer_state(opt)
+        if self.trainer.ema is not None:
+            self.trainer.load_ema_state(CK.read_ema_state(f))          # (none stored: starts from the loaded weights, and warns)
         # schedules follow the step counter (the KL-weight burn-in, base_gcp.py:121-128, counts model.step() calls)
         self.model.n_steps = int(self.global_step)
         self.model._set_kl_weight()
@@ -343,8 +373,9 @@ class ModelTrainer:
         from . import checkpoint as CK
         if self.nan_guard:
             self.check_weights()                       # never overwrite a good checkpoint with non-finite weights
+        ema_kw = {"ema_state": self.trainer.ema_state()} if self.trainer.ema is not None else {}
         return CK.save_checkpoint(self.model, os.path.join(self.exp_path, "weights"), epoch, self.global_step,
-                                  self.trainer.optimizer_state())
+                                  self.trainer.optimizer_state(), **ema_kw)
 
     def check_weights(self):
         """one gcpx_grad_health over theta -- parameters and BatchNorm running statistics -- and a sync: raises NonFiniteWeights when
@@ -453,6 +484,14 @@ class ModelTrainer:
 
     # ---- train.py:195-238: prior-sampled prediction (val_mode) + the training forward for the NLL, no gradient ----
     def val(self):
+        """with a weight average and --eval_ema 1 the whole pass -- prediction, metrics, picture logs, NLL -- runs on the averaged
+        weights (trainer.ema_weights(): exchanged on entry, exchanged back on exit)"""
+        if self.trainer.ema is not None and self.eval_ema:
+            with self.trainer.ema_weights():
+                return self._val()
+        return self._val()
+
+    def _val(self):
         tot, n = 0.0, 0
         slog, term_names, term_sum = self.scalar_log, None, None
         start = time.time()

@@ -18,6 +18,7 @@ call over one buffer) and the optimizer + the re-pack of the MFM
 import ctypes as C
 import os
 import re
+from contextlib import contextmanager
 
 import torch
 
@@ -31,6 +32,13 @@ from .backward_plan import BackwardPlanMixin
 from .backward_stages import BackwardStagesMixin
 
 
+def _numel(shape):
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
 class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, BackwardStagesMixin):
     """`step(inputs)` = one optimisation step of `model` (GCPTreeModel) on one minibatch; `backward(inputs)` stops
     after the gradients (tests)."""
@@ -40,9 +48,10 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
     _pending_slices = ()
     accumulate, micro_index, stepped, _accumulating, _grad_div = 1, 0, False, False, 1      # (see __init__: accumulate)
     NAN_GUARDS = (None, "raise", "skip")
+    ema, ema_decay, ema_warmup, ema_updates, _ema_swapped = None, None, True, 0, False      # (see __init__: ema_decay)
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, optimizer="radam", momentum=0.0,
-                 gradient_clip=None, nan_guard=None, accumulate=1):
+                 gradient_clip=None, nan_guard=None, accumulate=1, ema_decay=None, ema_warmup=True):
         """optimizer / momentum / gradient_clip: the trainer's `optimizer` ('radam' default, 'adam', 'rmsprop', 'sgd'), `momentum`
         (RMSprop / SGD) and `gradient_clip` settings (gcp_builder.py:174-186,255-263).
         nan_guard: None (nothing is tested: the step as it always was), "raise" or "skip" -- the reference's NanGradHook
@@ -57,13 +66,22 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         self.grad and runs the optimizer path as it stands with grad_scale = 1 / (k world).  The early optimizer slices and the overlap
         of the bucket all-reduces with the backward are off for k > 1 (as under gradient_clip: they need the cycle's whole sum).
         `micro_index`: position in the cycle; `stepped`: whether the last step() applied the optimizer; `mean_losses()`: the loss vector's
-        mean over the cycle.  1: the step as it always was -- no buffer, no launch."""
+        mean over the cycle.  1: the step as it always was -- no buffer, no launch.
+        ema_decay: a float in (0, 1) keeps an exponential moving average of theta -- parameters AND BatchNorm running statistics, one flat
+        vector `self.ema`, started as a copy of theta -- moved by one gcpx_ema_update per OPTIMIZER step, on the caller's stream behind
+        the step's last write to theta, gated like the step (a step the nan_guard drops leaves the average where it was).  The decay of
+        update t (0-based, t = `ema_updates`, a host count of ISSUED updates: the host never reads the gate, so a dropped step advances
+        it all the same) is `ema_decay`, or with ema_warmup (default) min(ema_decay, (1 + t) / (10 + t)) -- the num_updates rule of
+        TensorFlow's ExponentialMovingAverage, which keeps the random initialisation from dominating the first 1 / (1 - decay) steps.
+        `with trainer.ema_weights():` runs its body on the averaged weights.  None: the trainer as it was -- no vector, no launch."""
         if int(accumulate) != accumulate or int(accumulate) < 1:
             raise ValueError("accumulate must be a positive number of micro-batches, not {!r}".format(accumulate))
         self.accumulate, self.micro_index, self.stepped = int(accumulate), 0, False
         self._accumulating, self._grad_div, self._acc, self._loss_acc = False, 1, None, None
         if optimizer not in self.OPTIMIZERS:
             raise ValueError("Optimizer '{}' not supported!".format(optimizer))          # gcp_builder.py:185
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must be None or lie in (0, 1), not {!r}".format(ema_decay))
         if nan_guard not in self.NAN_GUARDS:
             raise ValueError("nan_guard must be None, 'raise' or 'skip', not {!r}".format(nan_guard))
         self.nan_guard, self._health, self._health_extra = nan_guard, None, None
@@ -86,6 +104,9 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
         if self.accumulate > 1:
             self._acc = torch.zeros_like(model.theta)          # the sum of the cycle's earlier micro-gradients
             self._loss_acc = torch.zeros(16, device=model.device)          # ... and of its loss vectors (out.raw["losses"])
+        if ema_decay is not None:
+            self.ema_decay, self.ema_warmup, self.ema_updates, self._ema_swapped = float(ema_decay), bool(ema_warmup), 0, False
+            self.ema = model.theta.clone()
         from .dist import GradBuckets, gradient_bucket_ranges
         ranges = gradient_bucket_ranges(model._poff, hp.hierarchy_levels, hp.untied_layers)
         self._ranges = ranges
@@ -167,6 +188,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
     def backward(self, inputs, noise=None):
         """forward (phase 'train', losses on device) + backward; gradients in self.grad.  Returns the forward outputs."""
         m = self.m
+        self._refuse_on_ema_weights("backward()")
         if self.buckets is not None and not self._accumulating:
             self.buckets.begin()          # a backward without an optimizer step in between must exchange its buckets again
         self._grad_div = 1                # self.grad is one batch's gradient again (gradient_stats)
@@ -296,6 +318,7 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
 
     def _optimizer_step(self):
         m = self.m
+        self._refuse_on_ema_weights("the optimizer step")
         st = torch.cuda.current_stream(m.device).cuda_stream
         scale = 1.0
         if self.buckets is not None:
@@ -317,6 +340,8 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             todo = [i for i in range(len(self._ranges)) if i not in applied]
             for j, i in enumerate(todo):
                 self._apply_slice(i, tick=(j == len(todo) - 1), on=self._caller)
+            if self.ema is not None:
+                self._ema_update(st)          # behind the last slice (the early ones went out on this stream too)
             return
         n = m.theta.numel()
         if self.gradient_clip:
@@ -342,6 +367,80 @@ class GCPTrainStep(BackwardWeightsMixin, BackwardOpsMixin, BackwardPlanMixin, Ba
             rt.check(m.lib.gcpx_optim_step(m.theta.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                                            self.opt_state.data_ptr(), n, kind, self.lr, p1, p2, self.eps, scale, st), "optim_step")
         m.repack(st)
+        if self.ema is not None:
+            self._ema_update(st)
+
+    # ---- the weight average (ema_decay) ----
+    def ema_decay_at(self, t):
+        """the decay of update t (0-based)"""
+        d = self.ema_decay
+        return min(d, (1.0 + t) / (10.0 + t)) if self.ema_warmup else d
+
+    def _ema_update(self, st):
+        """one gated gcpx_ema_update over the whole vector on stream `st` -- the caller's, on which the step's every write to theta was
+        issued and behind which the next forward orders itself: the average has read theta before anything of the next step writes it"""
+        m = self.m
+        rt.check(m.lib.gcpx_ema_update(self.ema.data_ptr(), m.theta.data_ptr(), m.theta.numel(), self.ema_decay_at(self.ema_updates),
+                                       self.opt_state.data_ptr() + 12, 0, st), "ema_update")
+        self.ema_updates += 1
+
+    def _refuse_on_ema_weights(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): theta holds the averaged weights; leave the context before training on")
+
+    def _swap_ema(self):
+        m = self.m
+        st = torch.cuda.current_stream(m.device).cuda_stream
+        rt.check(m.lib.gcpx_swap_f32(m.theta.data_ptr(), self.ema.data_ptr(), m.theta.numel(), 0, st), "swap_f32")
+        m.repack(st)
+
+    @contextmanager
+    def ema_weights(self):
+        """Runs the body on the averaged weights: gcpx_swap_f32(theta, ema) + a re-pack of everything on entry, the same on exit (also
+        when the body raises).  Contents move, addresses do not: every captured plan and graph stays valid.  BatchNorm running statistics
+        live in theta and are averaged and exchanged with it.  step() / backward() inside raise RuntimeError."""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight average (ema_decay=None)")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is already active")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swapped = False
+            self._swap_ema()
+
+    def ema_state(self):
+        """checkpoint entry "ema": the average cut with the offsets model.state_dict() uses (so sub-module prefix filters work on it as
+        on the weights), and where the warm-up stands"""
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight average (ema_decay=None)")
+        self._refuse_on_ema_weights("ema_state()")
+        flat = self.ema.detach().cpu()
+        sd = {k: flat[o:o + _numel(shp)].view(shp).clone() for k, (o, shp) in self.m._poff.items()}
+        return {"decay": self.ema_decay, "warmup": self.ema_warmup, "updates": int(self.ema_updates), "state_dict": sd}
+
+    def load_ema_state(self, st):
+        """the inverse of ema_state().  None (a checkpoint written without an average): the average starts again from the model's
+        weights as they are now, with updates = 0, and says so.  decay / warmup stay the trainer's own (as momentum does)."""
+        import warnings
+        if self.ema is None:
+            raise ValueError("this trainer keeps no weight average (ema_decay=None)")
+        self._refuse_on_ema_weights("load_ema_state()")
+        if st is None:
+            warnings.warn("the checkpoint holds no weight average: it starts again from the loaded weights, ema_updates = 0")
+            self.ema.copy_(self.m.theta)
+            self.ema_updates = 0
+            return
+        for k, (o, shp) in self.m._poff.items():
+            if k not in st["state_dict"]:
+                raise KeyError(f"the checkpoint's weight average has no entry {k}")
+            self.ema[o:o + _numel(shp)].view(shp).copy_(st["state_dict"][k])
+        self.ema_updates = int(st["updates"])
+        for k, own in (("decay", self.ema_decay), ("warmup", self.ema_warmup)):
+            if k in st and st[k] != own:
+                warnings.warn(f"checkpoint was averaged with ema {k}={st[k]!r}, this trainer runs {k}={own!r}")
 
     def step(self, inputs, noise=None):
         if self.accumulate > 1:
