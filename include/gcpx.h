@@ -1534,6 +1534,33 @@ int gcpx_cem_elites(const float* scores, int32_t* idx, float* elite_scores, int3
 int gcpx_cem_refit(const float* samples, const int32_t* idx, float* mean, float* std, float* best, int32_t K, int32_t n, int32_t n_elite,
                    int32_t D, void* stream);
 
+/* Receding-horizon additions to the loop above (CEMPlanner(noise_rho, keep_elites, warm_std), plan_batch(warm=); the reference's CEM has
+ * none of them; iCEM, Pinneri et al. 2020).  A sample is S steps of A values, D = S * A, a population [K][n][S][A].  The same rule: every
+ * float operation rounded on its own, in the order written; mirrors cem_warm_start_torch, cem_population_ex_torch.
+ *
+ * gcpx_cem_warm_start: the Gaussian a re-plan starts from.  prev [K][S][A] the previous best sample of each task, shift int32 [K] the
+ *   steps executed since.  Task k with s = shift[k]: s < 0 (no previous plan): mean = 0, std = init_std.  Otherwise, where t + s < S:
+ *   mean[k][t] = prev[k][t + s], std = warm_std * init_std (one float32 product, formed once); behind that, t + s >= S: mean = 0,
+ *   std = init_std (so s >= S is a cold start).  No load is made through a shifted index outside [0, S), prev of a task with s < 0 is not
+ *   read, a NaN in prev stays a NaN.  One thread per (task, column).
+ * gcpx_cem_population_ex: gcpx_cem_population with carried rows and temporally correlated noise.
+ *   rows j < m:  out[k][j] = prev_pop[k][prev_idx[k][j]], prev_pop [K][n_prev][S][A], prev_idx int32 [K][m]: copied as 32-bit words,
+ *     not clamped and not re-noised.  Every index is range-checked before it is used: a task with an index outside [0, n_prev) gets NaN
+ *     in its m carried rows, no load is made through it.  m == 0: prev_pop, prev_idx and n_prev are not looked at (may be null / 0).
+ *   rows j >= m: xi_0 = eps_0, xi_t = (rho * xi_{t-1}) + (c * eps_t) along the steps of each column, c = (float) sqrt(1 - (double) rho *
+ *     rho) formed once on the host: unit variance at every step.  out = clamp(mean + std * xi, -clip, clip) as in gcpx_cem_population.
+ *     rho == 0: xi = eps, the bits of gcpx_cem_population (nothing is multiplied by 0).
+ *   out may be eps (in place; rows < m of eps are not read); it may not overlap prev_pop.  A thread owns whole columns of a row: one
+ *   column for A = 1 and A >= 5, all A of them for A = 2 .. 4.
+ *
+ * GCPX_ERR_INVALID_ARG, nothing launched: a null pointer, a size <= 0 or S * A >= 2^31, m < 0, m > n, m > n_prev, rho outside [0, 1) or
+ *   NaN, warm_std outside (0, 1] or NaN, out overlapping prev_pop, more than 2^30 workgroups. */
+int gcpx_cem_warm_start(const float* prev, const int32_t* shift, float init_std, float warm_std, float* mean, float* std, int32_t K,
+                        int32_t S, int32_t A, void* stream);
+int gcpx_cem_population_ex(const float* mean, const float* std, const float* eps, float clip, float rho, const float* prev_pop,
+                           const int32_t* prev_idx, int32_t m, int32_t n_prev, float* out, int32_t K, int32_t n, int32_t S, int32_t A,
+                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * The inference-mode encoder of F frames in one launch, each frame on its own (csrc/enc_frames.hip): what the closed-loop policy
  * computes one frame per call, gcp/planning/planner_policy.py:222-227 (`self.planner.encoder(img)[0][:, :, 0, 0]`), for the frames of

@@ -9,6 +9,8 @@ executed steps of all E tasks advance together on the device (nav_env.NavEnvBatc
               length is known on the host when it is made, so the execution counters are host integers.  A re-plan reads that episode's
               current frame back: the only read-back of the loop.  With batch_plans (--batch_plans 1) the episodes that plan at a step
               plan together: one read-back of their frames, one planner.plan_batch call (HierarchicalCEMPlanner or the flat CEMPlanner).
+              With the flat planner a re-plan can start from the episode's previous best sample (--warm_start 1, with --warm_std,
+              --keep_elites, --noise_rho: receding-horizon CEM, which the reference does not have).
   plans       padded device tensors: latents [E, Lmax, nz], actions [E, Lmax, 2]
   a step      gather the next planned latent (closed loop) or the planned action (open loop) of every row; the encoder on the current
               frames; inv_mdl.run_single on all rows; env.step; env.observe
@@ -41,12 +43,18 @@ class ControlRunner:
     one `model.encode` call per frame.  An error if the model's encoder shape is not one `encode_frames` takes.
     keep_plans: `plans` holds a host copy of every plan made (the default); off, `dict(t, cost)` per plan, and with batch_plans and a
     planner that hands its plans over on the device (CEMPlanner.plan_batch(device=True)) neither frames nor plans visit the host: what
-    a loop that re-plans at every step (visual MPC, replan_interval = 1) needs."""
+    a loop that re-plans at every step (visual MPC, replan_interval = 1) needs.
+    warm_start (with batch_plans, the flat CEMPlanner): `best` [E, n_steps, dim] keeps every episode's last best sample on the device, and a
+    re-plan starts from it moved up by the steps executed since: plan_batch(warm=(best[due], shift)), shift the episode's exec_step, -1
+    for an episode without a plan.  The shifts go up as one small int32 tensor per planning step; the samples never visit the host."""
 
     def __init__(self, model, planner, env, replan_interval=1, num_max_replans=10, closed_loop_execution=False, batch_plans=False,
-                 batch_encode=False, keep_plans=True):
+                 batch_encode=False, keep_plans=True, warm_start=False):
         self.model, self.planner, self.env = model, planner, env
         self.batch_plans, self.batch_encode, self.keep_plans = bool(batch_plans), bool(batch_encode), bool(keep_plans)
+        self.warm_start, self.best = bool(warm_start), None
+        if self.warm_start and not self.batch_plans:
+            raise ValueError("warm_start re-plans through planner.plan_batch(warm=...): it needs batch_plans")
         if closed_loop_execution and not model._hp.attach_inv_mdl:
             raise ValueError("closed_loop_execution needs the model's inverse model (attach_inv_mdl)")
         if self.batch_encode:
@@ -84,12 +92,30 @@ class ControlRunner:
         image_plan, action_plan, latent_plan, cost = self.planner(frame[None], goal[None])
         self._record(e, t, image_plan, action_plan, latent_plan, cost)
 
+    def _warm(self, idx, due):
+        """warm_start: plan_batch's `warm` for the episodes `due` (read before their counters are reset), as keyword arguments"""
+        if not self.warm_start:
+            return {}
+        shift = torch.tensor([-1 if self.plan_len[e] is None else self.exec_step[e] for e in due], dtype=torch.int32).to(self.env.device)
+        return dict(warm=(None if self.best is None else self.best[idx], shift))
+
+    def _keep_best(self, idx):
+        if not self.warm_start:
+            return
+        best = self.planner.batch_best
+        if self.best is None:                               # the first plan gives the samples' shape
+            self.best = torch.zeros((self.env.E,) + tuple(best.shape[1:]), device=best.device)
+        self.best[idx.to(best.device)] = best
+
     def _plan_batch(self, due, t):
         """the episodes `due` at step t through one planner.plan_batch call; their frames come back in one copy"""
         if self._device_plans:
             return self._plan_batch_device(due, t)
-        frames = self.env.frames[torch.as_tensor(due, device=self.env.device), t].cpu().numpy()
-        for e, r in zip(due, self.planner.plan_batch(frames, self.goal_frames_np[due])):
+        idx = torch.as_tensor(due, device=self.env.device)
+        frames = self.env.frames[idx, t].cpu().numpy()
+        plans = self.planner.plan_batch(frames, self.goal_frames_np[due], **self._warm(idx, due))
+        self._keep_best(idx)
+        for e, r in zip(due, plans):
             self._record(e, t, r.predictions, r.actions, r.latents, r.cost)
 
     def _plan_batch_device(self, due, t):
@@ -98,7 +124,9 @@ class ControlRunner:
         plans' costs and lengths (2 numbers per episode: the execution counters are host integers)"""
         dev = self.env.device
         idx = torch.as_tensor(due, device=dev)
-        r = self.planner.plan_batch(self.env.frames[idx, t], self.env.goal_frames[idx], device=True, latents=self.closed_loop_execution)
+        r = self.planner.plan_batch(self.env.frames[idx, t], self.env.goal_frames[idx], device=True, latents=self.closed_loop_execution,
+                                    **self._warm(idx, due))
+        self._keep_best(idx)
         K, A = len(due), r.actions.shape[1]
         L = r.latents.shape[1] if r.latents is not None else 0
         if self.act is None or self.act.shape[1] < max(A, L):
@@ -160,7 +188,7 @@ class ControlRunner:
         self._lmax, self.lat, self.act = hp.max_seq_len + 2, None, None
         self.plan_len, self.exec_step, self.num_replans = [None] * E, [None] * E, [0] * E
         self.lat_len, self.act_len = [0] * E, [0] * E
-        self.plans = [[] for _ in range(E)]
+        self.plans, self.best = [[] for _ in range(E)], None
         self.goal_frames_np = env.goal_frames.cpu().numpy()
         # plans per step that nobody keeps stay on the device, with a planner that can hand them over there
         self._device_plans = self.batch_plans and not self.keep_plans and bool(getattr(self.planner, "device_plans", False))
@@ -216,13 +244,47 @@ def get_args(argv=None):
                    "closed_loop_execution; an error if the model's encoder shape is unsupported")
     p.add_argument("--keep_plans", type=int, default=1, help="0 = keep only the step and the cost of every plan (ControlRunner.plans); with "
                    "--batch_plans 1 and a flat planner the plans then stay on the device: no image plan is decoded or copied to the host")
+    p.add_argument("--warm_start", type=int, default=0, choices=(0, 1), help="1 = a re-plan starts from the episode's previous best sample, moved "
+                   "up by the steps executed since (ControlRunner(warm_start=True), DESIGN.md 5.7); with --batch_plans 1 and a flat planner")
+    p.add_argument("--warm_std", type=float, default=None, help="in (0, 1]: the std of a warm start on the steps the previous plan covers, in "
+                   "units of the sampler's initial std (CEMPlanner.warm_std)")
+    p.add_argument("--keep_elites", type=float, default=None, help="in [0, 1): this fraction of an iteration's elites are candidates of the next "
+                   "(CEMPlanner.keep_elites)")
+    p.add_argument("--noise_rho", type=float, default=None, help="in [0, 1): AR(1) correlation of a candidate's noise along its steps "
+                   "(CEMPlanner.noise_rho)")
     return p.parse_args(argv)
+
+
+RECEDING_FLAGS = ("warm_start", "warm_std", "keep_elites", "noise_rho")
+
+
+def receding_options(args):
+    """the receding-horizon flags that were given, refused where they cannot apply: {flag: value}"""
+    given = {k: getattr(args, k) for k in RECEDING_FLAGS if getattr(args, k) not in (None, 0)}
+    if given and not args.batch_plans:
+        raise ValueError(f"--{' --'.join(given)}: options of the flat planner's plan_batch, which plans per step: they need --batch_plans 1")
+    if given and args.reference_rng:
+        raise ValueError(f"--{' --'.join(given)}: plan_batch draws from a device generator; the reference's np.random stream "
+                         "(--reference_rng) is defined per plan")
+    return given
+
+
+def apply_receding_options(planner, given):
+    """hands --warm_std, --keep_elites and --noise_rho to the planner; refuses a planner whose plan_batch is not the flat CEMPlanner's"""
+    from .planning import CEMPlanner
+    if not given:
+        return
+    if getattr(type(planner), "plan_batch", None) is not CEMPlanner.plan_batch:
+        raise ValueError(f"--{' --'.join(given)}: options of the flat CEMPlanner's plan_batch (warm starts, carried elites, correlated noise); "
+                         f"the conf builds {type(planner).__name__}, which has none of them")
+    planner.set_receding(**{k: v for k, v in given.items() if k != "warm_start"})
 
 
 def main(argv=None):
     from . import conf_loader as CL
     from . import nav_env as NE
     args = get_args(argv)
+    receding = receding_options(args)
     if args.batch_plans and args.reference_rng:
         raise ValueError("--batch_plans 1 plans on a device generator; the reference's np.random stream (--reference_rng) is defined per plan")
     dev = torch.device("cuda", 0)
@@ -235,6 +297,7 @@ def main(argv=None):
         print(f"[control] not used from {os.path.basename(args.experiment)}: {k}", flush=True)
     model, planner, _ = CL.build_policy(desc, dev, weights=args.weights or None, seed=args.seed, random_weights=bool(args.random_weights),
                                         reference_rng=args.reference_rng, verbose=False, use_ema=bool(args.use_ema))
+    apply_receding_options(planner, receding)
     needs_inv = [k for k, v in (("policy.closed_loop_execution = True", desc.policy_args["closed_loop_execution"]),
                                 ("cem_params.use_inferred_actions = True", desc.get("action_source", "inverse_model") == "inverse_model")) if v]
     if needs_inv and not model._hp.attach_inv_mdl:
@@ -265,8 +328,8 @@ def main(argv=None):
     env = NE.NavEnvBatch(env_desc.n_rooms, env_desc.crop_window, T, env_desc.img_sz, dev, assets=assets)
     if args.batch_plans and not hasattr(planner, "plan_batch"):
         raise ValueError(f"--batch_plans 1 needs a planner with plan_batch; the conf builds {type(planner).__name__}, which has none")
-    runner = ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), batch_encode=bool(args.batch_encode),
-                           keep_plans=bool(args.keep_plans), **desc.policy_args)
+    runner =ControlRunner(model, planner, env, batch_plans=bool(args.batch_plans), batch_encode=bool(args.batch_encode),
+                           keep_plans=bool(args.keep_plans), warm_start=bool(args.warm_start), **desc.policy_args)
     parts = []
     for s in range(0, len(idx), max(args.batch, 1)):
         parts.append(runner.run({k: v[s:s + max(args.batch, 1)] for k, v in tasks.items()}))

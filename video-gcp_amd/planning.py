@@ -469,7 +469,8 @@ def select_elites(scores, n_elite):
 
 # ---- the flat CEM loop for K tasks at once: csrc/cem_batch.hip and its torch mirrors -----------------------------------------------------
 # Each mirror is the kernel's checker (tests/test_gpu_cem_batch.py: equal bit for bit) and what runs when the tensors are on the CPU
-# (tests/test_cem_batch_cpu.py); tensors on a device always go through the library.
+# (tests/test_cem_batch_cpu.py); tensors on a device always go through the library.  cem_warm_start and cem_population_ex are what
+# receding-horizon planning adds (tests/test_cem_warm_cpu.py, tests/test_gpu_cem_warm.py); the default loop does not call them.
 def cem_population_torch(mean, std, eps, clip):
     """gcpx_cem_population: mean, std [K, ...], eps [K, n, ...] -> clamp(mean + std * eps, -clip, clip) [K, n, ...]; block k is
     FlatCEMSampler.from_unit_noise(eps[k]) of a sampler holding task k's mean and std"""
@@ -512,8 +513,89 @@ def cem_refit_torch(samples, idx):
     return mean, std, best
 
 
+def cem_warm_start_torch(prev, shift, init_std, warm_std):
+    """gcpx_cem_warm_start: prev [K, S, ...] the previous best samples, shift int [K] the steps executed since -> mean, std [K, S, ...].
+    Task k with s = shift[k] >= 0: mean[k, t] = prev[k, t + s] and std = warm_std * init_std (one float32 product) where t + s < S; mean = 0
+    and std = init_std behind that, and everywhere for s < 0, whose prev is not looked at (a NaN there does not spread)."""
+    K, S = prev.shape[:2]
+    s = torch.as_tensor(shift, device=prev.device).long()
+    src = torch.arange(S, device=prev.device)[None] + s[:, None]
+    take = ((s[:, None] >= 0) & (src < S)).reshape((K, S) + (1,) * (prev.ndim - 2)).expand(prev.shape)
+    moved = prev[torch.arange(K, device=prev.device)[:, None], src.clamp(0, S - 1)]
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=prev.device)
+    mean = torch.where(take, moved, f32(0.0))
+    std = torch.where(take, f32(warm_std) * f32(init_std), f32(init_std))
+    return mean, std
+
+
+def cem_noise_c(rho):
+    """the weight of the fresh draw in the AR(1) noise: (float) sqrt(1 - (double) rho * rho) of the float32 rho, as the entry point forms it"""
+    r = float(np.float32(rho))
+    return float(np.float32(np.sqrt(1.0 - r * r)))
+
+
+def cem_population_ex_torch(mean, std, eps, clip, rho=0.0, prev_pop=None, prev_idx=None, m=0):
+    """gcpx_cem_population_ex: mean, std [K, S, ...], eps [K, n, S, ...] -> the K populations [K, n, S, ...].
+    rows j >= m: clamp(mean + std * xi, -clip, clip) with xi_0 = eps_0, xi_t = (rho * xi_{t-1}) + (c * eps_t) along the steps, each a
+    float32 operation of its own; rho = 0: xi = eps, cem_population_torch.
+    rows j < m:  prev_pop[k, prev_idx[k, j]] (prev_pop [K, n_prev, S, ...], prev_idx int32 [K, m]) as they are; a task with an index outside
+    [0, n_prev) gets NaN in these rows."""
+    K, n, S = eps.shape[:3]
+    if not 0.0 <= rho < 1.0:
+        raise ValueError(f"rho = {rho} outside [0, 1)")
+    if not 0 <= m <= n or (m > 0 and (prev_pop is None or prev_idx is None or m > prev_pop.shape[1] or prev_idx.shape[1] != m)):
+        raise ValueError(f"m = {m} carried rows need 0 <= m <= n, m <= n_prev and prev_idx [K, m]")
+    if float(np.float32(rho)) == 0.0:
+        xi = eps
+    else:
+        r, c = (torch.tensor(v, dtype=torch.float32, device=eps.device) for v in (float(np.float32(rho)), cem_noise_c(rho)))
+        steps = [eps[:, :, 0]]
+        for t in range(1, S):
+            steps.append((r * steps[-1]) + (c * eps[:, :, t]))
+        xi = torch.stack(steps, dim=2)
+    raw = mean[:, None] + std[:, None] * xi
+    out = raw.clamp(-clip, clip) if np.isfinite(clip) else raw
+    if m > 0:
+        i, n_prev = prev_idx.long(), prev_pop.shape[1]
+        bad = ((i < 0) | (i >= n_prev)).any(dim=1)
+        out[:, :m] = prev_pop[torch.arange(K, device=eps.device)[:, None], i.clamp(0, n_prev - 1)]
+        if bool(bad.any()):
+            out[bad, :m] = float("nan")
+    return out
+
+
 def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def cem_warm_start(prev, shift, init_std, warm_std):
+    """the K Gaussians mean, std [K, S, ...] a re-plan starts from: the previous best samples prev moved up by shift int32 [K] steps"""
+    if not prev.is_cuda:
+        return cem_warm_start_torch(prev, shift, init_std, warm_std)
+    K, S = prev.shape[:2]
+    prev, shift = prev.contiguous(), torch.as_tensor(shift).to(device=prev.device, dtype=torch.int32).contiguous()
+    mean, std = torch.empty_like(prev), torch.empty_like(prev)
+    rt.check(rt.load_library().gcpx_cem_warm_start(prev.data_ptr(), shift.data_ptr(), float(init_std), float(warm_std), mean.data_ptr(),
+                                                   std.data_ptr(), K, S, prev[0, 0].numel(), _stream(prev)), "cem_warm_start")
+    return mean, std
+
+
+def cem_population_ex(mean, std, eps, clip, rho=0.0, prev_pop=None, prev_idx=None, m=0, inplace=False):
+    """the K populations [K, n, S, ...] with m carried rows and AR(1) noise along the steps; inplace: written over eps"""
+    if not eps.is_cuda:
+        return cem_population_ex_torch(mean, std, eps, clip, rho, prev_pop, prev_idx, m)
+    K, n, S = eps.shape[:3]
+    mean, std, eps = mean.contiguous(), std.contiguous(), eps.contiguous()
+    out = eps if inplace else torch.empty_like(eps)
+    pp = pi = n_prev = 0
+    if m > 0:
+        prev_pop, prev_idx = prev_pop.contiguous(), prev_idx.contiguous()
+        if prev_idx.shape[1] != m or prev_idx.dtype != torch.int32:
+            raise ValueError("prev_idx is int32 [K, m]")
+        pp, pi, n_prev = prev_pop.data_ptr(), prev_idx.data_ptr(), prev_pop.shape[1]
+    rt.check(rt.load_library().gcpx_cem_population_ex(mean.data_ptr(), std.data_ptr(), eps.data_ptr(), float(clip), float(rho), pp, pi, int(m),
+                                                      n_prev, out.data_ptr(), K, n, S, eps[0, 0, 0].numel(), _stream(eps)), "cem_population_ex")
+    return out
 
 
 def cem_population(mean, std, eps, clip, inplace=False):
@@ -609,7 +691,8 @@ class CEMPlanner:
     """Flat CEM over tree latents with device-resident rollouts and sharded candidates (cem_planner.py:55-135)."""
 
     def __init__(self, simulator, cost, sampler, n_iters=3, batch_size=512, elite_frac=0.1, max_seq_len=80,
-                 goal_in_cost=True, decode_candidates=False, verbose=False, horizon=None, use_inferred_actions=True):
+                 goal_in_cost=True, decode_candidates=False, verbose=False, horizon=None, use_inferred_actions=True,
+                 noise_rho=0.0, keep_elites=0.0, warm_std=1.0):
         # decode_candidates: also decode the images of every candidate while scoring (what the reference's simulator does,
         # cem_simulator.py:29-59).  The learned cost reads latents only, so by default the images are decoded once, for the
         # plan that is returned; scores, elites and the returned plan are the same either way.
@@ -629,6 +712,22 @@ class CEMPlanner:
         # verbose (cem_params.verbose, cem_planner.py:72-88): every call appends to `verbose_logs` one list holding, per iteration, the
         # elites' rollouts and states, and last the final rollout (`elite_log_entry`).  Off: nothing is kept, copied or launched for it
         self.verbose, self.verbose_logs, self._last_eval = bool(verbose), [], None
+        # receding-horizon options of plan_batch, which the reference's CEM does not have (all off by default):
+        # noise_rho in [0, 1): AR(1) correlation of the noise along the steps; keep_elites in [0, 1): the fraction of the elites carried
+        # into the next iteration's population; warm_std in (0, 1]: the std, in units of the initial one, on the steps of a warm start
+        self.noise_rho, self.keep_elites, self.warm_std = 0.0, 0.0, 1.0
+        self.set_receding(noise_rho=noise_rho, keep_elites=keep_elites, warm_std=warm_std)
+        self.batch_best = None
+
+    def set_receding(self, noise_rho=None, keep_elites=None, warm_std=None):
+        """the receding-horizon options, validated; None leaves one as it is"""
+        for name, v, ok, rng in (("noise_rho", noise_rho, lambda x: 0.0 <= x < 1.0, "[0, 1)"), ("keep_elites", keep_elites, lambda x: 0.0 <= x < 1.0, "[0, 1)"),
+                                 ("warm_std", warm_std, lambda x: 0.0 < x <= 1.0, "(0, 1]")):
+            if v is None:
+                continue
+            if not ok(float(v)):                             # (a NaN fails every comparison)
+                raise ValueError(f"CEMPlanner: {name} = {v} outside {rng}")
+            setattr(self, name, float(v))
 
     def _shard(self, n):
         world = D.dist.get_world_size() if D.dist.is_initialized() else 1
@@ -757,7 +856,7 @@ class CEMPlanner:
     MAX_ROWS = 1000
     device_plans = True           # plan_batch(device=True) hands the plans over on the device (control.ControlRunner(keep_plans=False))
 
-    def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None, device=False, latents=True):
+    def plan_batch(self, states, goals, record=False, max_rows=None, len_u=None, device=False, latents=True, warm=None):
         """K tasks planned together: states, goals [K, H, W, 3] env images -> a list of K Outputs with the fields of `plan`.
         device: the plans stay on the device (`_device_plans`: no decoded final rollout, no host lists; states and goals may be device
         tensors, which then never visit the host); latents: whether the caller reads the plans' latents (closed-loop acting).
@@ -777,7 +876,19 @@ class CEMPlanner:
         stds after the refit, the scoring rollouts' (latents, lengths) and goal latents, and `best_samples` [K, n_steps, dim].
         len_u: f(rows) -> the length draws of a forward of that many rows; default, for a simulator that predicts lengths:
         sampler.sample_uniform(rows) per forward.
-        self.logs: per iteration Outputs(elite_scores [K, n_elite], mean_score [K])."""
+        self.logs: per iteration Outputs(elite_scores [K, n_elite], mean_score [K]).  self.batch_best: `best` [K, n_steps, dim] of the call,
+        on the sampler's device.
+
+        Receding-horizon options (none in the reference; all off by default, and then the launches and draws are the ones above):
+        warm = (prev [K, n_steps, dim] float32 on the sampler's device, shift int32 [K]): the search starts at the previous best samples
+        moved up by the steps executed since (gcpx_cem_warm_start: std warm_std * initial_std on the steps the old plan covers, the cold
+        start behind them and for a task with shift < 0); prev None: nobody has a previous plan, a cold start for all.
+        keep_elites: from the second iteration on, rows 0 .. m-1 of a task's population, m = floor(keep_elites * n_elite), are the previous
+        iteration's elites in rank order, read from the previous population (kept alive until then) through the previous idx; in a call
+        with `warm` and m >= 1, row 0 of the first population is the task's starting mean itself.  Carried rows are rolled out and scored
+        like every other row.  noise_rho: the noise of a candidate is an AR(1) sequence along the steps.  Both through
+        gcpx_cem_population_ex; the noise draw stays randn(K, n, n_steps, dim) per iteration whatever m is (rows < m of it are ignored), so
+        the generator's position does not depend on the options.  record also keeps `start_mean`, `start_std` and `m`."""
         s = self._sampler
         if self.verbose:
             raise ValueError("plan_batch keeps no verbose logs (they are defined per plan): use plan()")
@@ -804,9 +915,22 @@ class CEMPlanner:
         elif not getattr(sim, "pred_length", False):
             len_u = None
         learned = hasattr(self._cost, "sequence_cost_device")
-        mean = torch.zeros(K, s._n_steps, s._action_dim, device=dev)
-        std = s._initial_std * torch.ones(K, s._n_steps, s._action_dim, device=dev)
-        rec = Outputs(noise=[], populations=[], scores=[], elite_idx=[], means=[], stds=[], rollouts=[], goal_latents=[], best_samples=None)
+        m = int(self.keep_elites * n_elite)
+        extended = self.noise_rho != 0.0 or m > 0                # the default goes through gcpx_cem_population, as it always has
+        if warm is not None and warm[0] is not None:
+            prev, shift = warm
+            if not torch.is_tensor(prev) or prev.dtype != torch.float32 or tuple(prev.shape) != (K, s._n_steps, s._action_dim) \
+                    or prev.device.type != dev.type:
+                raise ValueError(f"plan_batch: warm[0] is the previous best samples, float32 [K, n_steps, dim] = {(K, s._n_steps, s._action_dim)} "
+                                 f"on {dev}")
+            if not torch.is_tensor(shift) or shift.dtype != torch.int32 or tuple(shift.shape) != (K,):
+                raise ValueError("plan_batch: warm[1] is the executed steps of every task, int32 [K]")
+            mean, std = cem_warm_start(prev, shift.to(dev), s._initial_std, self.warm_std)
+        else:
+            mean = torch.zeros(K, s._n_steps, s._action_dim, device=dev)
+            std = s._initial_std * torch.ones(K, s._n_steps, s._action_dim, device=dev)
+        rec = Outputs(noise=[], populations=[], scores=[], elite_idx=[], means=[], stds=[], rollouts=[], goal_latents=[], best_samples=None,
+                      start_mean=mean, start_std=std, m=m)
         kept, task0 = [], [0]
 
         def score(r, chunk_goals):
@@ -821,9 +945,21 @@ class CEMPlanner:
                                                        [g[None] for g in cost_goals[lo:lo + len(chunk_goals)]], repeat=n)
 
         self.logs, best, elite_scores = [], None, None
-        for _ in range(self.n_iters):
+        pop = idx = None
+        for it in range(self.n_iters):
             eps = torch.randn(K, n, s._n_steps, s._action_dim, device=dev, generator=s._gen)
-            pop = cem_population(mean, std, eps, s._clip_val, inplace=not record)
+            if not extended:
+                pop = cem_population(mean, std, eps, s._clip_val, inplace=not record)
+            else:
+                # `pop` and `idx` are still the previous iteration's here: eps is a buffer of its own, and the old population stays
+                # referenced until the launch that reads it has been issued
+                if it > 0:
+                    carry = (pop, idx[:, :m], m)
+                elif warm is not None and m >= 1:            # the starting mean itself is a candidate: one row, index 0
+                    carry = (mean[:, None], torch.zeros(K, 1, dtype=torch.int32, device=dev), 1)
+                else:
+                    carry = (None, None, 0)
+                pop = cem_population_ex(mean, std, eps, s._clip_val, self.noise_rho, *carry, inplace=not record)
             parts = rollout_chunks(sim, self.max_seq_len, states, goals, pop.reshape((K * n,) + tuple(pop.shape[2:])), n, max_rows, False,
                                    len_u, each=score, decode_device=self.decode_candidates)
             scores = (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(K, n)
@@ -836,7 +972,7 @@ class CEMPlanner:
                                ("goal_latents", torch.cat([p[2] for p in kept]))):
                     rec[key].append(v)
                 kept.clear()
-        rec.best_samples = best
+        rec.best_samples = self.batch_best = best
         self.batch_record = rec if record else None
         if device:
             return self._device_plans(states, goals, best, elite_scores[:, 0], max_rows, len_u, latents)

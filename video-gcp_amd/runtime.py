@@ -315,6 +315,8 @@ SYMBOLS = [
     ("gcpx_cem_population", C.c_int, [vp, vp, vp, C.c_float, vp, i32, i32, i32, vp]),
     ("gcpx_cem_elites", C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     ("gcpx_cem_refit", C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    ("gcpx_cem_warm_start", C.c_int, [vp, vp, C.c_float, C.c_float, vp, vp, i32, i32, i32, vp]),
+    ("gcpx_cem_population_ex", C.c_int, [vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp]),
     ("gcpx_encode_frames", C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, C.c_float, vp]),
 ]
 
